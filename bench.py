@@ -8,14 +8,21 @@ Workload (config.workload): ogbn-products-shaped synthetic power-law CSR (2,449,
   N>1   1-D row split over N ranks (BalancedSplitter rows): exchange of the Split(0) dense
         shards (RCCL all-gather, or the halo rows only; the fastest kept at setup) + local SpMM
         (strong scaling: the same matrix is divided across ranks).  config.parallelism names the
-        exchange that ran; 2-D grids are measured but only reported (extra.grid_best).
+        exchange that ran; with --full 2-D grids are measured too, but only reported
+        (extra.grid_best).
 value = 2*nnz*N FLOPs per step (whole job) / max-over-ranks step time, in GFLOP/s.
 
-Extra objects: `roofline` (dominant kernel spmm_main, HIP events on its stream, algorithmic
-gather-model bytes) and `cpu_baseline` (the operator's kCPU kernel, SURVEY.md §8d
-row a2, on the host cores this process may use, plus a 1-thread run; rank 0 at N=1 only).
+A plain run sets up, warms up, times the K steps and prints the line; its `roofline` object (N=1:
+dominant kernel spmm_main, the HIP events that bracket the timed steps on its stream, algorithmic
+gather-model bytes) costs no run of its own.  --dump-outputs DIR also writes the
+output of the last timed step (a seeded sample of its rows) as .npy files.  --full adds every
+measurement that takes runs of its own: the separate-run, cold-cache and static_csr kernel times
+(`extra`), `cpu_baseline` (the operator's kCPU kernel, SURVEY.md §8d row a2, on the host cores this
+process may use, plus a 1-thread run; rank 0 at N=1 only) and, at N>1, the per-phase times and the
+2-D grid candidates of the exchange tune.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config products] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config products] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline]]
 """
 from __future__ import annotations
 
@@ -134,6 +141,26 @@ class Mark:
         return self.ev.elapsed_time(later.ev) if self.on_gpu else (later.t - self.t) * 1e3
 
 
+DUMP_BYTES = 32 << 20  # per run, all ranks together (the row indices add 1/n of it again)
+
+
+def dump_outputs(path: str, out: "torch.Tensor", rank: int, world: int):
+    """Write this rank's output of the last timed step as float32 (float64 for f64) .npy files:
+    `out` (N=1) or `out_rank<r>`, and beside it `<name>_rows`, the rows of the output that were
+    kept.  A large output is sampled: the same sorted rows in every run (seeded by the rank)."""
+    os.makedirs(path, exist_ok=True)
+    rows, n = out.shape
+    keep = max(1, DUMP_BYTES // world // (max(n, 1) * 8))
+    idx = np.arange(rows, dtype=np.int64)
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(rank).choice(rows, keep, replace=False))
+    wide = torch.float64 if out.dtype == torch.float64 else torch.float32
+    sample = out[torch.from_numpy(idx).to(out.device)].to(wide).cpu().numpy()
+    name = "out" if world == 1 else f"out_rank{rank}"
+    np.save(os.path.join(path, f"{name}.npy"), sample)
+    np.save(os.path.join(path, f"{name}_rows.npy"), idx.astype(np.float64))
+
+
 def _claim_stdout():
     """Route fd 1 to stderr for the whole run (RCCL and the HIP runtime print banners on stdout)
     and return a writer on the real stdout for the one JSON line of the bench contract."""
@@ -167,7 +194,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="products")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their "
+                         "own after the timed steps: the separate event-bracketed and cold-cache "
+                         "kernel timings, static_csr, the CPU baselines and, at N>1, the per-phase "
+                         "times and the 2-D grid candidates of the exchange tune")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to "
+                         "DIR/<name>.npy (a fixed, seeded sample of rows where the output is large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "16")),
                     help="host threads for input generation and the secondary CPU numbers")
     ap.add_argument("--cpu-baseline-threads", type=int, default=0,
@@ -181,9 +217,9 @@ def main():
     ap.add_argument("--exchange", default="auto",
                     help="B exchange for N>1: auto | any | allgather | halo | nsplit | grid<R>x<C>"
                          "[/s<S>].  auto (default): the fastest 1-D row-split exchange measured at "
-                         "setup (all-gather or halo, the north star's partition); the 2-D grids "
-                         "are measured too but only reported (extra.grid_best).  any: the fastest "
-                         "of all, grids included")
+                         "setup (all-gather or halo, the north star's partition); with --full the "
+                         "2-D grids are measured too but only reported (extra.grid_best).  any: "
+                         "the fastest of all, grids included")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="process-group backend at N>1; gloo is a rehearsal of the multi-rank code "
                          "path on fewer GPUs (ranks share devices, bytes are host-staged: not a "
@@ -308,8 +344,10 @@ def main():
         pinned_sub = int(args.exchange.split("/s")[1]) if "/s" in args.exchange else 1
         auto = args.exchange in ("auto", "any")
         full = None
-        if auto or args.exchange.startswith(("nsplit", "grid")):
-            # the grid / column-split candidates need the whole CSR on every rank
+        if (auto and (args.full or args.exchange == "any")) \
+                or args.exchange.startswith(("nsplit", "grid")):
+            # the grid / column-split candidates need the whole CSR on every rank; under auto
+            # they are only reported (extra.grid_best), so a plain run neither builds nor times them
             f_ci = torch.from_numpy(synth.columns(m, k, rp_full, threads=threads)).to(device)
             full = (torch.from_numpy(rp_full.astype(np.int32)).to(device), f_ci,
                     synth.values(0, nnz, dt).to(device))
@@ -418,77 +456,81 @@ def main():
     flops = 2.0 * nnz * n
     value = flops * args.steps / elapsed / 1e9
 
+    if args.dump_outputs:
+        enter_phase("dump outputs", 300)
+        dump_outputs(args.dump_outputs, out, rank, world)
+
     enter_phase("phase timing and report", 600)
-    # ---- dominant-kernel timing: events on the launch stream around the SpMM launches ---------
-    # N=1: the op call (plan + main + reduce; main dominates).  N>1: the local SpMM after the
-    # gather.  Measured over a separate short run so the timed region above has no extra events.
-    sync()
-    spmm_ms, gather_ms = [], []
-    for _ in range(max(args.steps, 5)):
-        if not rowsplit:
-            events[1].record()
-            step()
-            events[2].record()
-        else:
-            events[0].record()
-            rs.gather_phase()
-            events[1].record()
-            rs.compute_phase(out)
-            events[2].record()
+    # N=1: the op's launches are the only work on the launch stream, so the HIP events that
+    # bracket the timed region on that stream give the average op duration directly (plan + main
+    # + reduce; main dominates).  N>1: the local SpMM after the gather, which only the separate
+    # run of --full brackets.
+    kern_ms = ev_start.ms_to(ev_end) / args.steps if not rowsplit else None
+    kern_ms_separate, gather_mean, phase, cold, cold_ms, static_ms = None, 0.0, None, [], None, None
+    if args.full:
+        # ---- dominant-kernel timing: events on the launch stream around the SpMM launches -----
+        # Measured over a separate short run so the timed region above has no extra events.
         sync()
-        spmm_ms.append(events[1].ms_to(events[2]))
+        spmm_ms, gather_ms = [], []
+        for _ in range(max(args.steps, 5)):
+            if not rowsplit:
+                events[1].record()
+                step()
+                events[2].record()
+            else:
+                events[0].record()
+                rs.gather_phase()
+                events[1].record()
+                rs.compute_phase(out)
+                events[2].record()
+            sync()
+            spmm_ms.append(events[1].ms_to(events[2]))
+            if rowsplit:
+                gather_ms.append(events[0].ms_to(events[1]))
+        kern_ms_separate = float(np.mean(spmm_ms))
         if rowsplit:
-            gather_ms.append(events[0].ms_to(events[1]))
-    kern_ms_separate = float(np.mean(spmm_ms))
-    kern_ms = kern_ms_separate
-    if not rowsplit:
-        # N=1: the op's launches are the only work on the launch stream, so the HIP events that
-        # bracket the timed region on that stream give the average op duration directly
-        kern_ms = ev_start.ms_to(ev_end) / args.steps
-    gather_mean = float(np.mean(gather_ms)) if gather_ms else 0.0
-    phase = {"spmm_ms_max": kern_ms, "gather_ms_max": gather_mean}
-    if rowsplit and world > 1:
-        t = torch.tensor([kern_ms, gather_mean], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        phase = {"spmm_ms_max": float(t[0]), "gather_ms_max": float(t[1])}
-    # cold-cache SpMM: a 512 MB scratch write evicts the 256 MB Infinity Cache
-    # and the L2s before each launch; median of 5.  The timed region above is the warm number.
-    cold = []
-    scratch = torch.empty(512 << 20, dtype=torch.uint8, device=device) if on_gpu else None
-    for i in range(5 if on_gpu else 0):
-        scratch.fill_(i)
-        if not rowsplit:
+            kern_ms = kern_ms_separate
+        gather_mean = float(np.mean(gather_ms)) if gather_ms else 0.0
+        phase = {"spmm_ms_max": kern_ms, "gather_ms_max": gather_mean}
+        if rowsplit and world > 1:
+            t = torch.tensor([kern_ms, gather_mean], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            phase = {"spmm_ms_max": float(t[0]), "gather_ms_max": float(t[1])}
+        # cold-cache SpMM: a 512 MB scratch write evicts the 256 MB Infinity Cache
+        # and the L2s before each launch; median of 5.  The timed region above is the warm number.
+        scratch = torch.empty(512 << 20, dtype=torch.uint8, device=device) if on_gpu else None
+        for i in range(5 if on_gpu else 0):
+            scratch.fill_(i)
             events[1].record()
-            step()
+            if not rowsplit:
+                step()
+            else:
+                rs.compute_phase(out)
             events[2].record()
-        else:
-            events[1].record()
-            rs.compute_phase(out)
-            events[2].record()
-        sync()
-        cold.append(events[1].ms_to(events[2]))
-    del scratch
-    cold_ms = float(np.median(cold)) if cold else float("nan")
-    # N=1, reported beside the value (never the value): the same op with attr static_csr, whose
-    # kernel state keeps the work-list plan across calls (a GNN's constant graph)
-    static_ms = None
-    if not rowsplit and on_gpu and opts is None:
-        fs.spmm(d_rp, d_ci, d_v, m, k, d_b, out=out, static_csr=True)  # plans once
-        sync()
-        e0, e1 = Mark(on_gpu), Mark(on_gpu)
-        e0.record()
-        for _ in range(args.steps):
-            fs.spmm(d_rp, d_ci, d_v, m, k, d_b, out=out, static_csr=True)
-        e1.record()
-        sync()
-        static_ms = e0.ms_to(e1) / args.steps
-        fs._C.static_plans(release=True)
+            sync()
+            cold.append(events[1].ms_to(events[2]))
+        del scratch
+        cold_ms = float(np.median(cold)) if cold else float("nan")
+        # N=1, reported beside the value (never the value): the same op with attr static_csr,
+        # whose kernel state keeps the work-list plan across calls (a GNN's constant graph;
+        # DESIGN.md §3)
+        if not rowsplit and on_gpu and opts is None:
+            fs.spmm(d_rp, d_ci, d_v, m, k, d_b, out=out, static_csr=True)  # plans once
+            sync()
+            e0, e1 = Mark(on_gpu), Mark(on_gpu)
+            e0.record()
+            for _ in range(args.steps):
+                fs.spmm(d_rp, d_ci, d_v, m, k, d_b, out=out, static_csr=True)
+            e1.record()
+            sync()
+            static_ms = e0.ms_to(e1) / args.steps
+            fs._C.static_plans(release=True)
     bytes_launch = alg_bytes(rows, nnz_local, n, s_v)
     if rowsplit and rs.exchange in rs.grids:  # the grid's SpMM: its row group x N/C columns
         gp = rs.grids[rs.exchange]
         bytes_launch = gp.sub * alg_bytes(gp.ghi - gp.glo, int(rp_full[gp.ghi] - rp_full[gp.glo]),
                                           gp.w, s_v)
-    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
+    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9 if kern_ms else None
 
     # HBM-side traffic of the dominant kernel per launch from the committed rocprofv3 PMC summary
     # of this same workload (scripts/profile.sh + scripts/rocprof_summary.py; beyond-L2 bytes =
@@ -522,24 +564,27 @@ def main():
                    (f"REHEARSAL with gloo on {torch.cuda.device_count() if on_gpu else 0} GPU(s), "
                     f"host-staged bytes, not a performance number: {rs.describe()}")
                    if rehearsal else rs.describe()},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "traffic_unit": "bytes per launch (beyond L2: Infinity Cache + HBM)",
-                     "traffic_source": traffic_src,
-                     # the algorithmic (gather-model) rate can exceed what HBM alone delivers when
-                     # hot B rows are served by the 256 MB Infinity Cache
-                     "model": ("effective (gather model; beyond-L2 traffic includes Infinity-Cache "
-                               "hits)" if achieved > HBM_MEASURED_GBS else "gather model"),
-                     "kernel": "spmm_main_kernel (+plan/reduce, timed together; HIP events "
-                               "on the launch stream around the timed region at N=1)",
-                     "alg_bytes_per_launch": bytes_launch, "kernel_ms": round(kern_ms, 4)},
     }
-    result["extra"] = {"kernel_ms_events_separate_run": round(kern_ms_separate, 4),
-                       "kernel_ms_cold_median": round(cold_ms, 4) if cold else None,
-                       "static_csr_ms_per_step": round(static_ms, 4) if static_ms else None,
-                       "static_csr_gflops": round(flops / (static_ms * 1e-3) / 1e9, 2)
-                       if static_ms else None,
-                       "gbs_cold": round(bytes_launch / (cold_ms * 1e-3) / 1e9, 1) if cold else None}
+    if achieved is not None:  # N=1, or the SpMM phase of N>1 that --full timed
+        result["roofline"] = {
+            "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "traffic_unit": "bytes per launch (beyond L2: Infinity Cache + HBM)",
+            "traffic_source": traffic_src,
+            # the algorithmic (gather-model) rate can exceed what HBM alone delivers when
+            # hot B rows are served by the 256 MB Infinity Cache
+            "model": ("effective (gather model; beyond-L2 traffic includes Infinity-Cache "
+                      "hits)" if achieved > HBM_MEASURED_GBS else "gather model"),
+            "kernel": "spmm_main_kernel (+plan/reduce, timed together; HIP events "
+                      "on the launch stream around the timed region at N=1)",
+            "alg_bytes_per_launch": bytes_launch, "kernel_ms": round(kern_ms, 4)}
+    # what --full measured in runs of its own; a plain run reports none of it
+    result["extra"] = {} if not args.full else {
+        "kernel_ms_events_separate_run": round(kern_ms_separate, 4),
+        "kernel_ms_cold_median": round(cold_ms, 4) if cold else None,
+        "static_csr_ms_per_step": round(static_ms, 4) if static_ms else None,
+        "static_csr_gflops": round(flops / (static_ms * 1e-3) / 1e9, 2) if static_ms else None,
+        "gbs_cold": round(bytes_launch / (cold_ms * 1e-3) / 1e9, 1) if cold else None}
     if rowsplit:
         nz = torch.tensor([nnz_local, nnz_local], dtype=torch.float64, device=red_dev)
         if world > 1:
@@ -558,19 +603,6 @@ def main():
             # the whole CSR on every rank and is not the north star's 1-D row split)
             "grid_best": ({"exchange": g2d[0], "ms": round(g2d[1], 4),
                            "gflops": round(flops / (g2d[1] * 1e-3) / 1e9, 2)} if g2d else None),
-            "allgather_ms_rank0": round(gather_mean, 4),
-            "spmm_ms_rank0": round(kern_ms, 4),
-            "allgather_ms_max": round(phase["gather_ms_max"], 4),
-            "spmm_ms_max": round(phase["spmm_ms_max"], 4),
-            # SpMM phase alone with the gathered B resident (SURVEY.md §8e reports it separately)
-            "spmm_phase_gflops_aggregate": round(flops / (phase["spmm_ms_max"] * 1e-3) / 1e9, 2),
-            # B bytes this rank receives in the exchange phase / its time
-            "allgather_gbs_per_rank": round(((rs.halo.halo_rows * n if rs.exchange == "halo" else
-                                              rs.grids[rs.exchange].exchange_rows()[0]
-                                              if rs.exchange in rs.grids
-                                              else (rs.k_padded - rs.pad) * n) * s_v) /
-                                            (phase["gather_ms_max"] * 1e-3) / 1e9, 2)
-            if phase["gather_ms_max"] > 0 else None,
             "rows_rank0": rows, "nnz_rank0": nnz_local,
             "exchange": rs.exchange, "allgather_schedule": rs.comm_kind,
             "pipeline_blocks": rs.halo_chunks if rs.exchange == "halo" else rs.chunks,
@@ -595,6 +627,20 @@ def main():
             "tune_seconds": round(tune_s, 2) if tune_s is not None else None,
             "setup_seconds": round(setup_s, 2),
             "nnz_per_rank_max_over_mean": round(float(nz[0]) / (float(nz[1]) / world), 4)})
+        if args.full:  # the gather and SpMM phases, bracketed in the separate run
+            exchanged = (rs.halo.halo_rows * n if rs.exchange == "halo" else
+                         rs.grids[rs.exchange].exchange_rows()[0] if rs.exchange in rs.grids
+                         else (rs.k_padded - rs.pad) * n) * s_v
+            result["extra"].update({
+                "allgather_ms_rank0": round(gather_mean, 4),
+                "spmm_ms_rank0": round(kern_ms, 4),
+                "allgather_ms_max": round(phase["gather_ms_max"], 4),
+                "spmm_ms_max": round(phase["spmm_ms_max"], 4),
+                # SpMM phase alone with the gathered B resident (SURVEY.md §8e reports it separately)
+                "spmm_phase_gflops_aggregate": round(flops / (phase["spmm_ms_max"] * 1e-3) / 1e9, 2),
+                # B bytes this rank receives in the exchange phase / its time
+                "allgather_gbs_per_rank": round(exchanged / (phase["gather_ms_max"] * 1e-3) / 1e9, 2)
+                if phase["gather_ms_max"] > 0 else None})
         # memory of the run: peak device memory (torch's allocator, this process) and peak host
         # RSS per rank, max and sum over ranks
         import resource
@@ -613,7 +659,7 @@ def main():
         result["extra"]["wall_seconds_to_line"] = round(time.time() - t_wall0, 1)
 
     # ---- CPU baseline (rank 0, N=1 only): the operator's own kCPU kernel ------
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         from oracle import oracle
         # bounded sample: the first rows holding <= 130M nonzeros (all of products; rows are
         # randomly permuted, so a leading block is representative), B whole on the host

@@ -5,7 +5,7 @@
 # usage: scripts/profile.sh <tag> [bench args...]
 set -u
 TAG=${1:-r01}; shift || true
-ARGS=${@:---steps 10 --warmup 3 --no-cpu-baseline}
+ARGS=${@:---steps 10 --warmup 3}
 PROG=${PROG:-bench.py}  # or e.g. PROG=scripts/bench_config.py for the non-bench configurations
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG

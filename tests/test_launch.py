@@ -95,7 +95,7 @@ def test_bench_multi_rank_rehearsal_on_one_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     p = _bench(["--gpus", "2", "--backend", "gloo", "--config", "plaw1m", "--steps", "2",
-                "--warmup", "1"], {},
+                "--warmup", "1", "--full"], {},
                drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"))
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -135,7 +135,7 @@ def test_bench_eight_rank_tune_is_ordered_and_bounded():
     model time, and a zero budget stops after that first measurement (the rest 'skipped:
     budget'); the line reports the all-gather's number beside the winner."""
     p = _bench(["--gpus", "8", "--backend", "gloo", "--device", "cpu", "--config", "tiny",
-                "--steps", "1", "--warmup", "0", "--tune-budget", "0"],
+                "--steps", "1", "--warmup", "0", "--tune-budget", "0", "--full"],
                {"OMP_NUM_THREADS": "1"}, drop=_SPAWN_ENV_DROP)
     line = _bench_line(p)
     cands = line["extra"]["tune_candidates"]
@@ -163,7 +163,7 @@ def test_bench_eight_rank_value_is_the_rowsplit_even_when_a_grid_is_faster():
     built from the kept exchange, the grid is reported under extra.grid_best, and every rank
     joined the exchange's communicator."""
     p = _bench(["--gpus", "8", "--backend", "gloo", "--device", "cpu", "--config", "tiny",
-                "--steps", "2", "--warmup", "1", "--tune-budget", "600"],
+                "--steps", "2", "--warmup", "1", "--tune-budget", "600", "--full"],
                {"OMP_NUM_THREADS": "1", "OFX_TUNE_TEST_SCALE": "grid:1e-4,nsplit:1e-4"},
                drop=_SPAWN_ENV_DROP)
     line = _bench_line(p)
@@ -264,3 +264,95 @@ def test_bench_exchange_that_never_completes_is_named_and_fails():
     assert "all-gather of B" in p.stderr and "not complete after 3.0 s" in p.stderr
     assert p.stdout == ""
     assert time.monotonic() - t0 < 90
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ofx_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _dump_bytes(d):
+    return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+
+
+def test_dump_outputs_samples_a_large_output_the_same_way_every_time(tmp_path):
+    """--dump-outputs: an output past the cap is cut to a fixed, seeded, sorted sample of its rows
+    (the rows kept are written beside it), float32 on disk (float64 for f64), at most 64 MB in
+    all; a small output is written whole."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    rows, n = 70_000, 128  # 36 MB of fp32: past the cap
+    out = torch.arange(rows * n, dtype=torch.float32).reshape(rows, n)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, 0, 1)
+    a, ra = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "a" / "out_rows.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == ["out.npy", "out_rows.npy"]
+    assert a.dtype == np.float32 and ra.dtype == np.float64
+    assert a.shape == (bench.DUMP_BYTES // (n * 8), n) and ra.shape == (a.shape[0],)
+    assert _dump_bytes(tmp_path / "a") <= 64 << 20
+    idx = ra.astype(np.int64)
+    assert (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < rows  # sorted, no row twice
+    assert np.array_equal(a, out.numpy()[idx])
+    assert np.array_equal(a, np.load(tmp_path / "b" / "out.npy"))
+    assert np.array_equal(ra, np.load(tmp_path / "b" / "out_rows.npy"))
+    # per rank at N>1: its own file, its share of the cap; f64 stays f64, bf16 widens to f32
+    bench.dump_outputs(str(tmp_path / "c"), out.double(), 1, 2)
+    c = np.load(tmp_path / "c" / "out_rank1.npy")
+    assert c.dtype == np.float64 and c.shape == (bench.DUMP_BYTES // 2 // (n * 8), n)
+    small = torch.arange(24, dtype=torch.float32).reshape(6, 4).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "d"), small, 0, 1)
+    s = np.load(tmp_path / "d" / "out.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "d" / "out_rows.npy"), np.arange(6.0))
+
+
+_FULL_ONLY_KEYS = ("kernel_ms_events_separate_run", "kernel_ms_cold_median", "static_csr_ms_per_step",
+                   "allgather_ms_max", "spmm_ms_max", "spmm_phase_gflops_aggregate")
+
+
+def test_bench_plain_two_rank_run_is_lean_and_its_dump_repeats(tmp_path):
+    """A plain N>1 run measures no 2-D grid and no phase on its own (those keys come with --full)
+    and still reports the line's figures; --dump-outputs writes every rank's rows of the last
+    timed step, float32, bit-identical between two runs with different step counts."""
+    import numpy as np
+    lines = []
+    for d, steps in (("a", "2"), ("b", "3")):
+        p = _bench(["--gpus", "2", "--backend", "gloo", "--device", "cpu", "--config", "tiny",
+                    "--steps", steps, "--warmup", "1", "--dump-outputs", str(tmp_path / d)],
+                   {"OMP_NUM_THREADS": "1"}, drop=_SPAWN_ENV_DROP)
+        lines.append(_bench_line(p))
+    line = lines[0]
+    assert line["steps"] == 2 and lines[1]["steps"] == 3
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert abs(line["value"] - 2 * 200_000 * 32 / (line["ms_per_step"] * 1e-3) / 1e9) \
+        <= 1e-3 * line["value"] + 0.02
+    ex = line["extra"]
+    assert not any(k in ex for k in _FULL_ONLY_KEYS) and "cpu_baseline" not in line
+    assert ex["tune_candidates"] and ex["grid_best"] is None
+    assert not any(k.startswith(("grid", "nsplit")) for k in ex["tune_candidates"])
+    assert ex["exchange_is_rowsplit"] and ex["ranks_seen"] == 2
+    assert sorted(os.listdir(tmp_path / "a")) == ["out_rank0.npy", "out_rank0_rows.npy",
+                                                  "out_rank1.npy", "out_rank1_rows.npy"]
+    for f in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b), f
+        if not f.endswith("_rows.npy"):
+            assert a.dtype == np.float32 and a.shape == (10_000, 32)  # tiny: m = 20000 over 2 ranks
+            assert np.isfinite(a).all() and np.abs(a).sum() > 0
+
+
+def test_bench_plain_one_rank_line_has_no_extras():
+    """A plain N=1 run (here on host tensors) prints the line's figures with an empty `extra` and no
+    cpu_baseline; with --full both are there."""
+    args = ["--gpus", "1", "--backend", "gloo", "--device", "cpu", "--config", "tiny",
+            "--steps", "2", "--warmup", "1"]
+    line = _bench_line(_bench(args, {"OMP_NUM_THREADS": "1"}, drop=_SPAWN_ENV_DROP))
+    assert line["extra"] == {} and "cpu_baseline" not in line
+    assert line["steps"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+    full = _bench_line(_bench([*args, "--full"], {"OMP_NUM_THREADS": "1"}, drop=_SPAWN_ENV_DROP))
+    assert full["extra"]["kernel_ms_events_separate_run"] > 0
+    assert full["cpu_baseline"]["bitexact_vs_gpu"] is True
