@@ -292,6 +292,116 @@ int ofx_sddmm_csr_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, 
                       const void* a, int64_t lda, const void* b, int64_t ldb, void* out,
                       int64_t row_begin, int64_t row_end);
 
+/* ---- max / min / mean aggregation (op "spmm_csr_reduce") -------------------------------------
+ * PyG's reduce="max" / DGL's u_mul_e_max (GraphSAGE-pool, PNA) and GraphSAGE-mean, which the
+ * reference would compose from gather -> multiply -> a segment reduction over the materialised
+ * nnz x N products.  Numeric contract, identical in the CPU kernel and the HIP kernels:
+ *
+ *   p_j[c] = mul(val[j], B[col[j], c]): the sum contract's product, rounded to T; a column outside
+ *   [0, k) reads a zero row.
+ *
+ *   OFX_REDUCE_MAX (MIN is the mirror image): out[r, c] = max_j p_j[c] over the nonzeros j of row r,
+ *   compared in the accumulation type, walking j upwards: a candidate replaces the running best
+ *   only if it is strictly greater, or if it is NaN and the best is not.  So the lowest j wins
+ *   ties, +0 and -0 tie, and the first NaN wins and propagates.  The winner's own bits are stored
+ *   (no second rounding); a NaN winner is stored as the canonical quiet NaN of T (f32 0x7fc00000,
+ *   f64 0x7ff8000000000000, bf16 0x7fc0, f16 0x7e00), since which NaN a multiply returns differs
+ *   between host and device arithmetic.  arg[r, c] is the winning GLOBAL nonzero index j (the
+ *   position in col_idx / values, not rebased to the row or the row range), in the index dtype.
+ *   An empty row gives out = +0 and arg = -1.  The result is a function of the row alone: the
+ *   device cuts long rows into chunks and combines the chunk winners in chunk order with the same
+ *   strict rule, which cannot change out or arg, so the schedule options have NO numeric effect.
+ *
+ *   OFX_REDUCE_MEAN: out[r, c] = store(load(s) / acc(deg_r)), s the ofx_spmm_csr result element
+ *   (already rounded to T, the sum op's schedule) and deg_r = row_ptr[r+1] - row_ptr[r]; deg_r = 0
+ *   gives +0.  That is spmm_csr followed by a broadcast divide, each op rounding to T (IEEE
+ *   division).  The device runs the untouched sum kernels, then ofx_row_scale_by_degree in place.
+ *
+ *   OFX_REDUCE_SUM forwards to ofx_spmm_csr.
+ *
+ * Gradients of max / min for upstream g = d(out) (of mean: g' = ofx_row_scale_by_degree(g), then
+ * the sum op's gradients on g'):
+ *   d(b)[k, c] (ofx_spmm_csr_select): row k of A^T (ofx_csr_transpose) walked in ascending A-row
+ *     order with exactly the order and hub-chunk schedule of ofx_spmm_csr on A^T at width n; entry
+ *     t (j = perm[t], r = col_idx_T[t]) adds mul(val[j], g[r, c]) if arg[r, c] == j and is skipped
+ *     otherwise (nothing is added, not even a zero).  One lane writes each element in that fixed
+ *     order: no atomics, deterministic.  With at most one nonzero per row of A the result is the
+ *     sum op's d(b) bit for bit.
+ *   d(values)[j] (ofx_sddmm_csr_select): the order contract and the product of ofx_sddmm_csr
+ *     (8-element leaves, pairwise tree), the term of column c being g[r, c] * b[col[j], c] if
+ *     arg[r, c] == j and +0 otherwise, whatever b holds.
+ * Loud failures: the max / min forward and both gradients read the shared work list; with no valid
+ * plan they fill their output with the canonical NaN (arg with -1) and raise the device-error
+ * word, as ofx_spmm_csr does.  opts->planned is honoured: the workspace then holds the plan
+ * ofx_spmm_csr_plan built with the same arguments (the layouts agree up to the partials).        */
+#define OFX_REDUCE_SUM 0
+#define OFX_REDUCE_MEAN 1
+#define OFX_REDUCE_MAX 2
+#define OFX_REDUCE_MIN 3
+/* Bytes of device workspace ofx_spmm_csr_reduce needs (sum / mean: ofx_spmm_csr's).             */
+int ofx_spmm_csr_reduce_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                       int64_t n, int64_t nnz, int reduce,
+                                       const ofx_spmm_options* opts, size_t* bytes);
+/* C[r - row_begin, :] = reduce_j values[j] * B[col_idx[j], :] for r in [row_begin, row_end) and
+ * arg[r - row_begin, :] = the winning global j (contract above).  arg: idx_dtype, rows of stride
+ * ldarg (>= n); it may be NULL (not written) and is ignored for sum and mean.  Other arguments as
+ * ofx_spmm_csr.  Device pointers; asynchronous; no allocation; no host synchronisation.
+ * OFX_EINVAL: an unknown reduce code, ldarg < n, a bad row range, int32 indices that cannot
+ * address the problem.                                                                          */
+int ofx_spmm_csr_reduce(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                        int64_t nnz, const void* row_ptr, const void* col_idx, const void* values,
+                        const void* b, int64_t ldb, void* c, int64_t ldc, void* arg, int64_t ldarg,
+                        int64_t row_begin, int64_t row_end, int reduce, void* workspace,
+                        size_t workspace_bytes, const ofx_spmm_options* opts);
+/* kCPU version: host pointers, synchronous, the same bits and the same arg.                     */
+int ofx_spmm_csr_reduce_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                            int64_t n, int64_t nnz, const void* row_ptr, const void* col_idx,
+                            const void* values, const void* b, int64_t ldb, void* c, int64_t ldc,
+                            void* arg, int64_t ldarg, int64_t row_begin, int64_t row_end,
+                            int reduce, const ofx_spmm_options* opts);
+/* d(b) of max / min (contract above).  A is m x k: row_ptr_t I[k+1], col_idx_t I[nnz], perm I[nnz]
+ * are A^T from ofx_csr_transpose; values T[nnz] are A's; arg I[m, n] (stride ldarg) and g T[m, n]
+ * (stride ldg) are the forward's arg and the upstream gradient over all m rows;
+ * db[kk - row_begin, :] (stride lddb) for the rows kk in [row_begin, row_end) of A^T, 0 <= .. <= k.
+ * opts: the schedule of the forward call (it is numeric here, as in ofx_spmm_csr).  arg must not be
+ * NULL (OFX_EINVAL).                                                                            */
+int ofx_spmm_csr_select_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                       int64_t n, int64_t nnz, const ofx_spmm_options* opts,
+                                       size_t* bytes);
+int ofx_spmm_csr_select(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                        int64_t nnz, const void* row_ptr_t, const void* col_idx_t, const void* perm,
+                        const void* values, const void* arg, int64_t ldarg, const void* g,
+                        int64_t ldg, void* db, int64_t lddb, int64_t row_begin, int64_t row_end,
+                        void* workspace, size_t workspace_bytes, const ofx_spmm_options* opts);
+int ofx_spmm_csr_select_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                            int64_t n, int64_t nnz, const void* row_ptr_t, const void* col_idx_t,
+                            const void* perm, const void* values, const void* arg, int64_t ldarg,
+                            const void* g, int64_t ldg, void* db, int64_t lddb, int64_t row_begin,
+                            int64_t row_end, const ofx_spmm_options* opts);
+/* d(values) of max / min (contract above): out[j] for the nonzeros of rows [row_begin, row_end);
+ * arg I and a (= g) T hold those rows from row_begin on (strides ldarg, lda), as a of
+ * ofx_sddmm_csr.  Workspace: ofx_sddmm_csr_workspace_size.  The device version takes n <= 2048
+ * (OFX_EUNSUPPORTED beyond).  arg must not be NULL (OFX_EINVAL).                                */
+int ofx_sddmm_csr_select(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                         int64_t nnz, const void* row_ptr, const void* col_idx, const void* arg,
+                         int64_t ldarg, const void* a, int64_t lda, const void* b, int64_t ldb,
+                         void* out, int64_t row_begin, int64_t row_end, void* workspace,
+                         size_t workspace_bytes);
+int ofx_sddmm_csr_select_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                             int64_t n, int64_t nnz, const void* row_ptr, const void* col_idx,
+                             const void* arg, int64_t ldarg, const void* a, int64_t lda,
+                             const void* b, int64_t ldb, void* out, int64_t row_begin,
+                             int64_t row_end);
+/* dst[r - row_begin, :] = store(load(src[r - row_begin, :]) / acc(deg_r)) for r in [row_begin,
+ * row_end), deg_r = row_ptr[r+1] - row_ptr[r]; deg_r = 0 gives +0.  Rows of stride ldsrc / lddst
+ * (>= n); dst may be src (in place).  The mean's forward (on the sum) and backward (on g).      */
+int ofx_row_scale_by_degree(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t n,
+                            const void* row_ptr, const void* src, int64_t ldsrc, void* dst,
+                            int64_t lddst, int64_t row_begin, int64_t row_end);
+int ofx_row_scale_by_degree_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t n,
+                                const void* row_ptr, const void* src, int64_t ldsrc, void* dst,
+                                int64_t lddst, int64_t row_begin, int64_t row_end);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -641,6 +751,36 @@ int ofx_functional_spmm_csr_gathered_attrs(void* stream, const ofx_tensor_desc* 
                                            int64_t a_num_cols, ofx_tensor_desc* out, void* tmp,
                                            size_t tmp_bytes, size_t* tmp_size_out,
                                            const ofx_spmm_attrs* attrs);
+/* functional::SpmmCsrReduce: op "spmm_csr_reduce" (oneflow/user/ops/spmm_reduce_op.cpp) through the
+ * op-registry dispatch, on one rank of a 1-D placement as ofx_functional_spmm_csr_ex
+ * (parallel_num 1: a local call; out_split_axis 0 rows / 1 columns / -1 broadcast; b_logical_cols
+ * the logical N of a column split, -1: b's own width).  reduce: OFX_REDUCE_*.  out [M_phys, N] in
+ * b's dtype; arg [M_phys, N] in the index dtype for max / min (global nonzero indices, so a row
+ * split needs no fix-up), an empty [0, N] tensor for sum / mean.  tmp_size_out != NULL: only the
+ * tmp size is computed.  num_threads: CPU kernel only.                                          */
+int ofx_functional_spmm_csr_reduce(void* stream, const ofx_tensor_desc* row_ptr,
+                                   const ofx_tensor_desc* col_idx, const ofx_tensor_desc* values,
+                                   int64_t a_num_rows, int64_t a_num_cols, const ofx_tensor_desc* b,
+                                   int reduce, ofx_tensor_desc* out, ofx_tensor_desc* arg,
+                                   void* tmp, size_t tmp_bytes, int64_t parallel_id,
+                                   int64_t parallel_num, int out_split_axis,
+                                   int64_t b_logical_cols, int num_threads, size_t* tmp_size_out);
+/* Gradient functors of max / min (ops "spmm_csr_reduce_grad_b": A^T from csr_transpose, A's
+ * values, the forward's arg and dy -> d(b) [K, N]; "spmm_csr_reduce_grad_values": -> d(values)
+ * [nnz]); the contracts of ofx_spmm_csr_select / ofx_sddmm_csr_select.  arg must not be NULL.   */
+int ofx_functional_spmm_csr_reduce_grad_b(void* stream, const ofx_tensor_desc* at_row_ptr,
+                                          const ofx_tensor_desc* at_col_idx,
+                                          const ofx_tensor_desc* at_perm,
+                                          const ofx_tensor_desc* values, const ofx_tensor_desc* arg,
+                                          const ofx_tensor_desc* dy, int64_t a_num_rows,
+                                          int64_t a_num_cols, ofx_tensor_desc* out, void* tmp,
+                                          size_t tmp_bytes, size_t* tmp_size_out);
+int ofx_functional_spmm_csr_reduce_grad_values(void* stream, const ofx_tensor_desc* row_ptr,
+                                               const ofx_tensor_desc* col_idx,
+                                               const ofx_tensor_desc* arg, const ofx_tensor_desc* dy,
+                                               const ofx_tensor_desc* b, int64_t a_num_rows,
+                                               int64_t a_num_cols, ofx_tensor_desc* out, void* tmp,
+                                               size_t tmp_bytes, size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

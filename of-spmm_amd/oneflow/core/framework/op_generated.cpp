@@ -80,6 +80,53 @@ REGISTER_USER_OP("csr_transpose")
     .SetGetSbpFn(CsrTransposeOp::GetSbp)
     .SetDataTypeInferFn(CsrTransposeOp::InferDataType);
 
+// attr `reduce`: "sum" / "mean" / "max" / "min" in the ODS record; this registry's attribute map
+// holds integers, so it carries the OFX_REDUCE_* code (0..3) of include/ofx_spmm.h.
+REGISTER_USER_OP("spmm_csr_reduce")
+    .Input("a_csr_row_ptr")
+    .Input("a_csr_col_idx")
+    .Input("a_csr_values")
+    .Input("b")
+    .Output("out")
+    .Output("arg")
+    .Attr<int64_t>("a_num_rows", 0)
+    .Attr<int64_t>("a_num_cols", 0)
+    .Attr<int64_t>("reduce", 0)
+    .SetLogicalTensorDescInferFn(SpmmCsrReduceOp::InferLogicalTensorDesc)
+    .SetPhysicalTensorDescInferFn(SpmmCsrReduceOp::InferPhysicalTensorDesc)
+    .SetGetSbpFn(SpmmCsrReduceOp::GetSbp)
+    .SetDataTypeInferFn(SpmmCsrReduceOp::InferDataType)
+    .SetInputArgModifyFn(SpmmCsrReduceOp::ModifyInputArg);
+
+REGISTER_USER_OP("spmm_csr_reduce_grad_b")
+    .Input("at_row_ptr")
+    .Input("at_col_idx")
+    .Input("at_perm")
+    .Input("a_csr_values")
+    .Input("arg")
+    .Input("dy")
+    .Output("out")
+    .Attr<int64_t>("a_num_rows", 0)
+    .Attr<int64_t>("a_num_cols", 0)
+    .SetLogicalTensorDescInferFn(SpmmCsrReduceGradBOp::InferLogicalTensorDesc)
+    .SetPhysicalTensorDescInferFn(SpmmCsrReduceGradBOp::InferPhysicalTensorDesc)
+    .SetGetSbpFn(SpmmCsrReduceGradBOp::GetSbp)
+    .SetDataTypeInferFn(SpmmCsrReduceGradBOp::InferDataType);
+
+REGISTER_USER_OP("spmm_csr_reduce_grad_values")
+    .Input("a_csr_row_ptr")
+    .Input("a_csr_col_idx")
+    .Input("arg")
+    .Input("dy")
+    .Input("b")
+    .Output("out")
+    .Attr<int64_t>("a_num_rows", 0)
+    .Attr<int64_t>("a_num_cols", 0)
+    .SetLogicalTensorDescInferFn(SpmmCsrReduceGradValuesOp::InferLogicalTensorDesc)
+    .SetPhysicalTensorDescInferFn(SpmmCsrReduceGradValuesOp::InferPhysicalTensorDesc)
+    .SetGetSbpFn(SpmmCsrReduceGradValuesOp::GetSbp)
+    .SetDataTypeInferFn(SpmmCsrReduceGradValuesOp::InferDataType);
+
 REGISTER_USER_OP("eager_ccl_all_gather")
     .Input("in")
     .Output("out")

@@ -486,7 +486,12 @@ struct Arg {
 
 Maybe<void> RunUserOp(const std::string& op_name, const std::vector<Arg>& ins,
                       const std::vector<Arg>& outs, const user_op::AttrMap& call_attrs, void* stream,
-                      void* tmp, size_t tmp_bytes, size_t* tmp_size_out) {
+                      void* tmp, size_t tmp_bytes, size_t* tmp_size_out,
+                      const Placement* pl = nullptr, int64_t b_logical_cols = -1,
+                      int num_threads = 0) {
+  // pl != NULL: a global op on one rank of a placement (input "b" and every output follow the
+  // placement's NdSbp, the other inputs are broadcast): logical inference on the logical b, then
+  // the op's physical inference, and the kernel's OpKernelCache from the same placement.
   const user_op::OpRegistryResult* op = user_op::UserOpRegistryMgr::Get().GetOpRegistryResult(op_name);
   CHECK_OR_RETURN(op != nullptr) << Error::RuntimeError() << "op " << op_name << " is not registered";
   // the op's attributes: the registered defaults, then this call's values
@@ -506,7 +511,30 @@ Maybe<void> RunUserOp(const std::string& op_name, const std::vector<Arg>& ins,
     in[{a.name, 0}] = user_op::TensorDesc(ShapeOf(a.d), (DataType)a.d->dtype);
   }
   user_op::InferContext ictx(in, attrs);
-  JUST(op->logical_infer(&ictx));
+  std::map<std::string, NdSbp> nd_sbp;
+  std::map<std::string, user_op::TensorDesc> logical;
+  if (pl == nullptr) {
+    JUST(op->logical_infer(&ictx));
+  } else {
+    DescMap logical_in = in;
+    auto b_it = logical_in.find({"b", 0});
+    if (b_it != logical_in.end() && b_it->second.shape().NumAxes() == 2 && b_logical_cols >= 0) {
+      Shape b_logical = b_it->second.shape();
+      b_logical.Set(1, b_logical_cols);
+      b_it->second = user_op::TensorDesc(b_logical, b_it->second.data_type());
+    }
+    user_op::InferContext lctx(logical_in, attrs);
+    JUST(op->logical_infer(&lctx));
+    JUST(op->dtype_infer(&lctx));
+    nd_sbp["b"] = pl->b_sbp;
+    for (const std::string& o : op->outputs) {
+      nd_sbp[o] = pl->out_sbp;
+      logical[o] = lctx.OutputTensorDesc(o, 0);
+    }
+    ictx.SetParallel(ParallelContext(pl->parallel_id, pl->parallel_num()),
+                     ParallelDesc(pl->hierarchy), nd_sbp, logical);
+    JUST(op->physical_infer(&ictx));
+  }
   JUST(op->dtype_infer(&ictx));
   user_op::KernelRegContext rc;
   rc.device_type_ = device < 0 ? DeviceType::kCPU : DeviceType::kHIP;
@@ -518,6 +546,7 @@ Maybe<void> RunUserOp(const std::string& op_name, const std::vector<Arg>& ins,
     user_op::InferSizeContext sc;
     sc.descs = in;
     sc.attrs = attrs;
+    sc.logical = logical;
     *tmp_size_out = reg->infer_tmp_size ? reg->infer_tmp_size(&sc) : 0;
     return Maybe<void>::Ok();
   }
@@ -542,18 +571,25 @@ Maybe<void> RunUserOp(const std::string& op_name, const std::vector<Arg>& ins,
   }
   user_op::Tensor t_tmp(Shape({(int64_t)tmp_bytes}), kChar, tmp);
   if (tmp) tensors[{"tmp_buffer", 0}] = &t_tmp;
-  ep::CpuStream cpu_stream(0);
+  ep::CpuStream cpu_stream(num_threads);
   ep::HipStream hip_stream(stream, device);
   ep::Stream* s = device < 0 ? static_cast<ep::Stream*>(&cpu_stream) : static_cast<ep::Stream*>(&hip_stream);
   user_op::KernelComputeContext ctx(s, tensors, attrs, rc.device_type());
   const user_op::OpKernel* kernel = GetKernel(reg);
+  std::shared_ptr<user_op::OpKernelCache> cache;
   // a static CSR's plan lives in the eager op's kernel state (per registration and device)
   auto sc = attrs.find("static_csr");
   user_op::OpKernelState* kstate = nullptr;
   if (sc != attrs.end() && static_cast<int64_t>(sc->second) != 0)
     kstate = EagerKernelState(reg, kernel, device, rc.device_type());
   try {
-    kernel->Compute(&ctx, kstate, nullptr);
+    if (pl != nullptr) {
+      user_op::KernelCacheContext cache_ctx(ParallelContext(pl->parallel_id, pl->parallel_num()),
+                                            ParallelDesc(pl->hierarchy), nd_sbp, logical,
+                                            rc.device_type());
+      cache = kernel->InitOpKernelCache(&cache_ctx);
+    }
+    kernel->Compute(&ctx, kstate, cache.get());
   } catch (const KernelCheckError& e) {
     return Maybe<void>("KernelCheckError", e.msg);
   }
@@ -690,5 +726,74 @@ extern "C" int ofx_functional_fused_spmm_csr_attrs(
                               {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols},
                                {"relu", relu ? 1 : 0}, {"static_csr", static_csr}},
                               stream, tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
+// ---- functional::SpmmCsrReduce and its gradient functors ----------------------------------------
+// Ops "spmm_csr_reduce" (sum / mean / max / min with the arg output), "spmm_csr_reduce_grad_b" and
+// "spmm_csr_reduce_grad_values" through the same op-registry dispatch.
+extern "C" int ofx_functional_spmm_csr_reduce(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* values, int64_t a_num_rows, int64_t a_num_cols, const ofx_tensor_desc* b,
+    int reduce, ofx_tensor_desc* out, ofx_tensor_desc* arg, void* tmp, size_t tmp_bytes,
+    int64_t parallel_id, int64_t parallel_num, int out_split_axis, int64_t b_logical_cols,
+    int num_threads, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(reduce >= OFX_REDUCE_SUM && reduce <= OFX_REDUCE_MIN, OFX_EINVAL,
+                "spmm_csr_reduce: unknown reduce code %d (OFX_REDUCE_SUM/MEAN/MAX/MIN)", reduce);
+    // an earlier launch's loud failure comes back here as OFX_EPLAN (as for spmm_csr)
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_reduce");
+    Placement pl;
+    const int64_t hierarchy = parallel_num;
+    const int32_t axis = out_split_axis;
+    int rc = ToStatus(MakePlacement(1, &hierarchy, &axis, parallel_id, &pl));
+    if (rc) return rc;
+    std::vector<Arg> outs;
+    if (tmp_size_out == nullptr) outs = {{"out", out}, {"arg", arg}};
+    return ToStatus(RunUserOp("spmm_csr_reduce",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                               {"a_csr_values", values}, {"b", b}},
+                              outs,
+                              {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols},
+                               {"reduce", reduce}},
+                              stream, tmp, tmp_bytes, tmp_size_out, &pl, b_logical_cols,
+                              num_threads));
+  });
+}
+
+extern "C" int ofx_functional_spmm_csr_reduce_grad_b(
+    void* stream, const ofx_tensor_desc* at_row_ptr, const ofx_tensor_desc* at_col_idx,
+    const ofx_tensor_desc* at_perm, const ofx_tensor_desc* values, const ofx_tensor_desc* arg,
+    const ofx_tensor_desc* dy, int64_t a_num_rows, int64_t a_num_cols, ofx_tensor_desc* out,
+    void* tmp, size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(arg != nullptr, OFX_EINVAL,
+                "spmm_csr_reduce_grad_b: arg is NULL (the gradient of max / min needs it)");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_reduce_grad_b");
+    return ToStatus(RunUserOp("spmm_csr_reduce_grad_b",
+                              {{"at_row_ptr", at_row_ptr}, {"at_col_idx", at_col_idx},
+                               {"at_perm", at_perm}, {"a_csr_values", values}, {"arg", arg},
+                               {"dy", dy}},
+                              {{"out", out}},
+                              {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols}}, stream,
+                              tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
+extern "C" int ofx_functional_spmm_csr_reduce_grad_values(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* arg, const ofx_tensor_desc* dy, const ofx_tensor_desc* b,
+    int64_t a_num_rows, int64_t a_num_cols, ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+    size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(arg != nullptr, OFX_EINVAL,
+                "spmm_csr_reduce_grad_values: arg is NULL (the gradient of max / min needs it)");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_reduce_grad_values");
+    return ToStatus(RunUserOp("spmm_csr_reduce_grad_values",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                               {"arg", arg}, {"dy", dy}, {"b", b}},
+                              {{"out", out}},
+                              {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols}}, stream,
+                              tmp, tmp_bytes, tmp_size_out));
   });
 }

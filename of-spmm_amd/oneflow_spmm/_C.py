@@ -291,6 +291,117 @@ def spmm_csr_gathered(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     return out
 
 
+REDUCE_CODES = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN, "max": _lib.REDUCE_MAX,
+                "min": _lib.REDUCE_MIN}
+
+
+def reduce_code(reduce: str) -> int:
+    try:
+        return REDUCE_CODES[reduce]
+    except (KeyError, TypeError):
+        raise ValueError(f"spmm: reduce must be one of {sorted(REDUCE_CODES)}, got {reduce!r}") \
+            from None
+
+
+def spmm_csr_reduce(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                    a_csr_values: torch.Tensor, a_num_rows: int, a_num_cols: int, b: torch.Tensor,
+                    reduce: str = "sum", *, out: torch.Tensor | None = None, _parallel=None,
+                    num_threads: int = 0):
+    """Op "spmm_csr_reduce": (out, arg) with out[r, :] = reduce_j values[j] * b[col_idx[j], :],
+    reduce in {"sum", "mean", "max", "min"} (contract in include/ofx_spmm.h).  arg[r, c] is the
+    winning GLOBAL nonzero index of max / min in the index dtype (-1 for an empty row, whose out
+    is +0); for sum / mean it is an empty [0, N] tensor.  `_parallel=(parallel_id, parallel_num,
+    out_split_axis[, logical_n])` as for spmm_csr: this rank's rows (axis 0) or columns (axis 1)
+    of out and arg; arg keeps global nonzero indices under a row split."""
+    code = reduce_code(reduce)
+    rp = _prep(a_csr_row_ptr, "a_csr_row_ptr")
+    ci = _prep(a_csr_col_idx, "a_csr_col_idx")
+    vals = _prep(a_csr_values, "a_csr_values")
+    bb = _prep(b, "b", matrix=True)
+    pid, pnum, axis, logical_n = 0, 1, -1, -1
+    if _parallel is not None:
+        pid, pnum, axis = (int(x) for x in _parallel[:3])
+        logical_n = int(_parallel[3]) if len(_parallel) > 3 else -1
+    rows = int(a_num_rows)
+    if axis == 0 and pnum > 1 and rows > 0:
+        lo, hi = balanced_range(rows, pnum, pid)
+        rows = hi - lo
+    n = bb.shape[1] if bb.dim() == 2 else 0
+    if out is None:
+        out = torch.empty((rows, n), dtype=bb.dtype, device=bb.device)
+    has_arg = code in (_lib.REDUCE_MAX, _lib.REDUCE_MIN)
+    arg = torch.empty((rows if has_arg else 0, n), dtype=rp.dtype, device=bb.device)
+    d_in = [desc(t) for t in (rp, ci, vals)]
+    d_b, d_o, d_a = desc(bb), desc(out), desc(arg)
+    head = (*(ctypes.byref(d) for d in d_in), int(a_num_rows), int(a_num_cols), ctypes.byref(d_b),
+            code)
+    tail = (pid, pnum, axis, logical_n, int(num_threads))
+    size = ctypes.c_size_t(0)
+    check(LIB.ofx_functional_spmm_csr_reduce(None, *head, None, None, None, 0, *tail,
+                                             ctypes.byref(size)), "spmm_csr_reduce")
+    tmp = None
+    if size.value:
+        tmp = torch.empty(size.value, dtype=torch.uint8, device=bb.device)
+    check(LIB.ofx_functional_spmm_csr_reduce(current_stream_handle(bb), *head, ctypes.byref(d_o),
+                                             ctypes.byref(d_a),
+                                             tmp.data_ptr() if tmp is not None else None,
+                                             size.value if tmp is not None else 0, *tail, None),
+          "spmm_csr_reduce")
+    return out, arg
+
+
+def spmm_csr_reduce_grad_b(at_row_ptr: torch.Tensor, at_col_idx: torch.Tensor,
+                           at_perm: torch.Tensor, a_csr_values: torch.Tensor, arg: torch.Tensor,
+                           dy: torch.Tensor, a_num_rows: int, a_num_cols: int) -> torch.Tensor:
+    """Op "spmm_csr_reduce_grad_b": d(b) [K, N] of reduce = max / min from A^T's structure
+    (csr_transpose), A's values, the forward's arg and the upstream gradient dy; deterministic,
+    in the sum op's order on A^T (include/ofx_spmm.h ofx_spmm_csr_select)."""
+    rp, ci, perm = (_prep(t, n) for t, n in ((at_row_ptr, "at_row_ptr"), (at_col_idx, "at_col_idx"),
+                                             (at_perm, "at_perm")))
+    vals = _prep(a_csr_values, "a_csr_values")
+    arg, dy = _prep(arg, "arg", matrix=True), _prep(dy, "dy", matrix=True)
+    out = torch.empty((int(a_num_cols), dy.shape[1]), dtype=dy.dtype, device=dy.device)
+    _run_grad_op(LIB.ofx_functional_spmm_csr_reduce_grad_b, dy, [rp, ci, perm, vals, arg, dy],
+                 [out], [int(a_num_rows), int(a_num_cols)])
+    return out
+
+
+def spmm_csr_reduce_grad_values(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                                arg: torch.Tensor, dy: torch.Tensor, b: torch.Tensor,
+                                a_num_rows: int, a_num_cols: int) -> torch.Tensor:
+    """Op "spmm_csr_reduce_grad_values": d(values) [nnz] of reduce = max / min, the SDDMM of dy
+    and b restricted to the columns each nonzero won (ofx_sddmm_csr_select)."""
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    arg, dy = _prep(arg, "arg", matrix=True), _prep(dy, "dy", matrix=True)
+    bb = _prep(b, "b", matrix=True)
+    if bb.dim() == 2 and bb.shape[1] == 0:  # empty inner dimension: every dot product is +0
+        return torch.zeros(ci.numel(), dtype=bb.dtype, device=bb.device)
+    out = torch.empty(ci.numel(), dtype=bb.dtype, device=bb.device)
+    _run_grad_op(LIB.ofx_functional_spmm_csr_reduce_grad_values, bb, [rp, ci, arg, dy, bb], [out],
+                 [int(a_num_rows), int(a_num_cols)])
+    return out
+
+
+def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the
+    mean's divide, forward (on the sum) and backward (on the upstream gradient)."""
+    rp = _prep(a_csr_row_ptr, "a_csr_row_ptr")
+    x = _prep(x, "x", matrix=True)
+    if out is None:
+        out = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
+    m, n = x.shape
+    common = (dtype_code(rp.dtype), dtype_code(x.dtype), m, n, rp.data_ptr(),
+              x.data_ptr() if x.numel() else None, x.stride(0) if m else n,
+              out.data_ptr() if out.numel() else None, out.stride(0) if m else n, 0, m)
+    if x.device.type == "cpu":
+        check(LIB.ofx_row_scale_by_degree_cpu(0, *common), "row_scale_by_degree")
+    else:
+        check(LIB.ofx_row_scale_by_degree(current_stream_handle(x), *common),
+              "row_scale_by_degree")
+    return out
+
+
 def csr_transpose(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a_num_rows: int,
                   a_num_cols: int):
     """Structure of A^T (op "csr_transpose"): (row_ptr [K+1], col_idx [nnz], perm [nnz])."""

@@ -19,6 +19,7 @@ DT_FLOAT, DT_DOUBLE, DT_INT32, DT_INT64, DT_FLOAT16, DT_BFLOAT16 = 2, 3, 5, 6, 9
  OFX_EINTERNAL) = range(9)
 # test knobs of ofx_debug_set (include/ofx_spmm.h)
 DEBUG_PLAN_SPIN_LIMIT, DEBUG_THROW_IN_COMPUTE, DEBUG_EXCHANGE_STALL = 1, 2, 3
+REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 0, 1, 2, 3  # OFX_REDUCE_*
 MEMCPY_H2D, MEMCPY_D2H, MEMCPY_D2D, MEMCPY_DEFAULT = 1, 2, 3, 4
 UNIQUE_ID_BYTES = 128
 PEER_HANDLE_BYTES = 96   # OFX_PEER_HANDLE_BYTES
@@ -138,6 +139,25 @@ def _load():
                               popt], i32),
         "ofx_sddmm_csr_plan": ([p, i32, i32, i64, i64, i64, p, i64, i64, p, sz], i32),
         "ofx_sddmm_csr_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, i64, p, i64, p, i64, i64], i32),
+        "ofx_spmm_csr_reduce_workspace_size": ([i32, i32, i64, i64, i64, i64, i32, popt,
+                                                ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_reduce": ([p, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, p, i64, p, i64,
+                                 i64, i64, i32, p, sz, popt], i32),
+        "ofx_spmm_csr_reduce_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, p, i64, p,
+                                     i64, i64, i64, i32, popt], i32),
+        "ofx_spmm_csr_select_workspace_size": ([i32, i32, i64, i64, i64, i64, popt,
+                                                ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_select": ([p, i32, i32, i64, i64, i64, i64, p, p, p, p, p, i64, p, i64, p,
+                                 i64, i64, i64, p, sz, popt], i32),
+        "ofx_spmm_csr_select_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, p, p, i64, p, i64,
+                                     p, i64, i64, i64, popt], i32),
+        "ofx_sddmm_csr_select": ([p, i32, i32, i64, i64, i64, i64, p, p, p, i64, p, i64, p, i64, p,
+                                  i64, i64, p, sz], i32),
+        "ofx_sddmm_csr_select_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, i64, p, i64, p,
+                                      i64, p, i64, i64], i32),
+        "ofx_row_scale_by_degree": ([p, i32, i32, i64, i64, p, p, i64, p, i64, i64, i64], i32),
+        "ofx_row_scale_by_degree_cpu": ([i32, i32, i32, i64, i64, p, p, i64, p, i64, i64, i64],
+                                        i32),
         "ofx_coo_to_csr_workspace_size": ([i32, i64, i64, i64, ctypes.POINTER(sz)], i32),
         "ofx_coo_to_csr": ([p, i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, p, p, p, sz], i32),
         "ofx_coo_to_csr_cpu": ([i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, ctypes.POINTER(i64)], i32),
@@ -221,6 +241,14 @@ def _load():
                                                     pdesc, p, sz, ctypes.POINTER(sz), pattrs], i32),
         "ofx_functional_csr_transpose": ([p, pdesc, pdesc, i64, i64, pdesc, pdesc, pdesc, p, sz,
                                           ctypes.POINTER(sz)], i32),
+        "ofx_functional_spmm_csr_reduce": ([p, pdesc, pdesc, pdesc, i64, i64, pdesc, i32, pdesc,
+                                            pdesc, p, sz, i64, i64, i32, i64, i32,
+                                            ctypes.POINTER(sz)], i32),
+        "ofx_functional_spmm_csr_reduce_grad_b": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, pdesc, i64,
+                                                   i64, pdesc, p, sz, ctypes.POINTER(sz)], i32),
+        "ofx_functional_spmm_csr_reduce_grad_values": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64,
+                                                        i64, pdesc, p, sz, ctypes.POINTER(sz)],
+                                                       i32),
         "ofx_op_spmm_csr_sbp_signatures": ([ctypes.c_char_p, sz], i32),
         "ofx_process_ctx_init": ([i64, i64, KV_PUSH_FN, KV_PULL_FN, SENDRECV_FN, p], i32),
         "ofx_ccl_registered": ([i32, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),

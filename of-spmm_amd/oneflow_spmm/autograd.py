@@ -147,12 +147,76 @@ class SpmmCsrFunction(torch.autograd.Function):
         return None, None, d_values, None, None, d_b, None
 
 
+class SpmmCsrReduceFunction(torch.autograd.Function):
+    """(out, arg) = spmm_csr_reduce(..., reduce) for reduce in {"mean", "max", "min"},
+    differentiable in `a_csr_values` and `b`; `arg` is not differentiable.
+
+    max / min: the forward's arg is saved; d(b) is the masked SpMM on the cached A^T
+    (TRANSPOSE_CACHE, op "spmm_csr_reduce_grad_b": deterministic, no atomics) and d(values) the
+    masked SDDMM (op "spmm_csr_reduce_grad_values").  mean: the upstream gradient is divided by
+    the row degrees (the forward's row scale), then the sum op's gradients run on it."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, values, m, k, b, reduce):
+        out, arg = _C.spmm_csr_reduce(row_ptr, col_idx, values, m, k, b, reduce)
+        ctx.save_for_backward(row_ptr, col_idx, values, b, arg)
+        ctx.m, ctx.k, ctx.reduce = m, k, reduce
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, d_out, _d_arg):
+        row_ptr, col_idx, values, b, arg = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_values = d_b = None
+        if ctx.reduce == "mean":
+            g = _C.row_scale_by_degree(row_ptr, d_out)
+            if ctx.needs_input_grad[2]:
+                d_values = sddmm(row_ptr, col_idx, g, b)
+            if ctx.needs_input_grad[5]:
+                d_b = TRANSPOSE_CACHE.grad_b(row_ptr, col_idx, values.detach(), ctx.m, ctx.k, g)
+            return None, None, d_values, None, None, d_b, None
+        if ctx.needs_input_grad[2]:
+            d_values = _C.spmm_csr_reduce_grad_values(row_ptr, col_idx, arg, d_out, b, ctx.m, ctx.k)
+        if ctx.needs_input_grad[5]:
+            rp_t, ci_t, perm = TRANSPOSE_CACHE.get(row_ptr, col_idx, ctx.k)
+            d_b = _C.spmm_csr_reduce_grad_b(rp_t, ci_t, perm, values.detach(), arg, d_out, ctx.m,
+                                            ctx.k)
+        return None, None, d_values, None, None, d_b, None
+
+
+def spmm_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b,
+                reduce="sum", *, out=None):
+    """(out, arg) of `spmm(..., reduce=reduce)`: arg[r, c] is the global nonzero index that won
+    column c of row r for "max" / "min" (-1 for an empty row), an empty [0, N] tensor for "sum" /
+    "mean".  With autograd, as `spmm`; `out=` only when no gradient is being recorded."""
+    _C.reduce_code(reduce)  # ValueError for an unknown name, before anything runs
+    if torch.is_grad_enabled() and (a_csr_values.requires_grad or b.requires_grad):
+        if out is not None:
+            raise RuntimeError("spmm_reduce: out= is not supported when gradients are required")
+        if reduce == "sum":
+            res = SpmmCsrFunction.apply(a_csr_row_ptr, a_csr_col_idx, a_csr_values,
+                                        int(a_num_rows), int(a_num_cols), b, 0)
+            return res, torch.empty((0, res.shape[1]), dtype=a_csr_row_ptr.dtype,
+                                    device=res.device)
+        return SpmmCsrReduceFunction.apply(a_csr_row_ptr, a_csr_col_idx, a_csr_values,
+                                           int(a_num_rows), int(a_num_cols), b, reduce)
+    return _C.spmm_csr_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols,
+                              b, reduce, out=out)
+
+
 def spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b, *, out=None,
-         static_csr=0):
+         static_csr=0, reduce="sum"):
     """`oneflow.spmm` with autograd: differentiable in `a_csr_values` and `b`.
     `out=` (a preallocated result) is only accepted when no gradient is being recorded.
     `static_csr` (op attr; True = 1): the CSR is not rewritten while calls carry this value, so
-    the forward plans its work list once (_C.spmm_csr)."""
+    the forward plans its work list once (_C.spmm_csr).
+    `reduce`: "sum" (the default: the op as it always was), "mean", "max" or "min" (PyG's
+    reduce=, DGL's u_mul_e_max / _min / copy-mean); `spmm_reduce` also returns max / min's arg.
+    static_csr applies to "sum" only."""
+    if reduce != "sum":
+        return spmm_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b,
+                           reduce, out=out)[0]
     if torch.is_grad_enabled() and (a_csr_values.requires_grad or b.requires_grad):
         if out is not None:
             raise RuntimeError("spmm: out= is not supported when gradients are required")
@@ -208,4 +272,4 @@ def fused_spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_col
 
 
 __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm", "TRANSPOSE_CACHE", "ops",
-           "FusedSpmmCsrFunction", "fused_spmm"]
+           "FusedSpmmCsrFunction", "fused_spmm", "SpmmCsrReduceFunction", "spmm_reduce"]

@@ -66,3 +66,49 @@ add_docstr(
     for ``oneflow.spmm``: a non-zero value keeps the plan of an unchanged CSR across calls.
     """,
 )
+
+add_docstr(
+    oneflow._C.spmm_csr_reduce,
+    r"""
+    spmm_csr_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b, reduce="sum") -> (Tensor, Tensor)
+
+    ``oneflow.spmm`` with another aggregation over each row's products
+    :math:`p_j = values[j] \cdot b[col[j], :]` (each rounded to the dtype of ``b``), as
+    ``reduce=`` of a message-passing layer; ``oneflow.spmm(..., reduce=...)`` returns ``out`` alone.
+
+    * ``"sum"``: ``oneflow.spmm``.
+    * ``"mean"``: the sum divided by the row's number of nonzeros and rounded again (the bits of
+      ``spmm`` followed by a broadcast divide); an empty row gives ``+0``.
+    * ``"max"`` / ``"min"``: the elementwise extremum over the row's nonzeros.  Among equal
+      candidates the lowest nonzero index wins (``+0`` and ``-0`` are equal); the first NaN wins
+      and propagates, stored as the canonical quiet NaN.  An empty row gives ``+0``.  The result
+      does not depend on any schedule and is identical on CPU and GPU.
+
+    Returns:
+        ``out`` of shape ``[M, N]`` and ``arg``: for ``"max"`` / ``"min"`` an ``[M, N]`` tensor of
+        the index dtype holding the position in ``a_csr_col_idx`` / ``a_csr_values`` of the winning
+        nonzero (``-1`` for an empty row); for ``"sum"`` / ``"mean"`` an empty ``[0, N]`` tensor.
+
+    Differentiable in ``a_csr_values`` and ``b``; ``arg`` is not differentiable.  The gradient of
+    ``"max"`` / ``"min"`` flows to the winning nonzero only and is deterministic: ``d(b)`` is
+    accumulated in the order of ``spmm`` on :math:`A^T`, without atomics.
+
+    For example:
+
+    .. code-block:: python
+
+        >>> import oneflow as flow
+        >>> row_ptr = flow.tensor([0, 2, 3], dtype=flow.int32)
+        >>> col_idx = flow.tensor([0, 2, 1], dtype=flow.int32)
+        >>> values = flow.tensor([1.0, 2.0, 3.0])
+        >>> b = flow.tensor([[1.0, 0.0], [0.0, 1.0], [1.0, 1.0]])
+        >>> out, arg = flow._C.spmm_csr_reduce(row_ptr, col_idx, values, 2, 3, b, reduce="max")
+        >>> out
+        tensor([[2., 2.],
+                [0., 3.]], dtype=oneflow.float32)
+        >>> arg
+        tensor([[1, 1],
+                [2, 2]], dtype=oneflow.int32)
+
+    """,
+)
