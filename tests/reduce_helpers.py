@@ -84,11 +84,17 @@ def ref_mean(rp, ci, vals, b, split=0, chunk=0, row_begin=0, row_end=None):
     if b.dtype == torch.bfloat16:
         s = oracle.bf16_bits_to_f32(s)
     s = s.astype(np.float64 if b.dtype == torch.float64 else np.float32)
-    deg = np.diff(rp_np)[row_begin:row_end].astype(s.dtype)
+    return ref_row_scale(s, np.diff(rp_np)[row_begin:row_end], b.dtype)
+
+
+def ref_row_scale(s: np.ndarray, deg: np.ndarray, dtype: torch.dtype) -> np.ndarray:
+    """store(s / deg) per row: s in the accumulation type, one IEEE division there, one rounding to
+    the storage type; a row of degree 0 gives +0."""
+    deg = np.asarray(deg).astype(s.dtype)
     with np.errstate(divide="ignore", invalid="ignore"):
         out = (s / deg[:, None]).astype(s.dtype)
     out[deg == 0] = 0
-    return store(out, b.dtype)
+    return store(out, dtype)
 
 
 def ref_grad_b(rp, ci, vals, arg, g, k, n_sched=None, split=0, chunk=0):
@@ -134,23 +140,76 @@ def ref_grad_values(rp, ci, arg, g, b):
 
 
 # ---- C-ABI callers --------------------------------------------------------------------------------
-def options(split=0, chunk=0, ordered=False):
+def options(split=0, chunk=0, ordered=False, planned=False, range_nnz=0):
     o = Options()
     o.split_threshold, o.chunk, o.ordered = split, chunk, 1 if ordered else 0
+    o.planned, o.range_nnz = 1 if planned else 0, range_nnz
     return o
 
 
-def padded(t: torch.Tensor, pad: int) -> torch.Tensor:
-    """A copy of the 2-D tensor t as a view of a buffer with `pad` more elements per row."""
-    if pad == 0:
+def _fill(buf: torch.Tensor) -> torch.Tensor:
+    """NaN (with sentinel()'s payload, so that is_sentinel tells it from a kernel's NaN) or -7."""
+    if not buf.dtype.is_floating_point:
+        return buf.fill_(-7)
+    it, bits = SENTINEL[buf.dtype]
+    buf.view(it).fill_(bits)
+    return buf
+
+
+def padded(t: torch.Tensor, pad: int, shift: int = 0) -> torch.Tensor:
+    """A copy of the 2-D tensor t as a view of a buffer with `pad` more elements per row (filled
+    with NaN / -7); the view starts `shift` elements into its buffer (a base pointer that is not
+    aligned to a lane's load)."""
+    if pad == 0 and shift == 0:
         return t.contiguous()
-    buf = torch.empty((t.shape[0], t.shape[1] + pad), dtype=t.dtype, device=t.device)
-    if t.dtype.is_floating_point:
-        buf.fill_(float("nan"))
-    else:
-        buf.fill_(-7)
-    buf[:, :t.shape[1]] = t
+    rows, n = t.shape
+    flat = _fill(torch.empty(rows * (n + pad) + shift, dtype=t.dtype, device=t.device))
+    view = flat[shift:].view(rows, n + pad)[:, :n]
+    view.copy_(t)
+    return view
+
+
+def padding_of(view: torch.Tensor, pad: int) -> torch.Tensor:
+    """The `pad` extra elements per row of the buffer behind padded(t, pad)."""
+    rows, n = view.shape
+    return view._base.view(rows, n + pad)[:, n:]
+
+
+def rebased(t: torch.Tensor, row_begin: int, row_end: int, pad: int) -> torch.Tensor:
+    """Rows [row_begin, row_end) of t at the start of a buffer of t's own row count (and `pad`
+    more elements per row); the other rows hold padded()'s fill.  A kernel that indexed such a
+    buffer by the global row would read the fill, inside the buffer."""
+    if row_begin == 0 and row_end == t.shape[0]:
+        return padded(t, pad)
+    buf = _fill(torch.empty((t.shape[0], t.shape[1] + pad), dtype=t.dtype, device=t.device))
+    buf[:row_end - row_begin, :t.shape[1]] = t[row_begin:row_end]
     return buf[:, :t.shape[1]]
+
+
+# A NaN payload no kernel writes (the canonical quiet NaN of a loud failure has none).
+SENTINEL = {torch.float32: (torch.int32, 0x7FC0DEAD),
+            torch.float64: (torch.int64, 0x7FF80000DEADBEEF),
+            torch.bfloat16: (torch.int16, 0x7FCD), torch.float16: (torch.int16, 0x7EAD)}
+POISON = {torch.float32: (torch.int32, 0x7FC00000),
+          torch.float64: (torch.int64, 0x7FF8000000000000),
+          torch.bfloat16: (torch.int16, 0x7FC0), torch.float16: (torch.int16, 0x7E00)}
+
+
+def sentinel(shape, dtype, dev) -> torch.Tensor:
+    it, bits = SENTINEL[dtype]
+    return torch.full(shape, bits, dtype=it, device=dev).view(dtype)
+
+
+def is_sentinel(t: torch.Tensor) -> torch.Tensor:
+    """Elementwise: the element still holds sentinel()'s bits."""
+    it, bits = SENTINEL[t.dtype]
+    return t.contiguous().view(it) == bits
+
+
+def poisoned(t: torch.Tensor) -> bool:
+    """Every element is the canonical quiet NaN of its dtype (a loud failure's fill)."""
+    it, bits = POISON[t.dtype]
+    return bool((t.contiguous().view(it) == bits).all().item())
 
 
 def _ptr(t):
@@ -163,17 +222,26 @@ def _workspace(query, dev):
     return torch.empty(max(size.value, 1), dtype=torch.uint8, device=dev), size.value
 
 
+def _device_workspace(query, dev, ws):
+    """The caller's workspace `ws` (a planned launch's), or a fresh one of the queried size."""
+    if ws is not None:
+        return ws, ws.numel()
+    return _workspace(query, dev)
+
+
 def run_reduce(rp, ci, vals, b, m, k, reduce, *, pad=0, row_begin=0, row_end=None, opts=None,
-               want_arg=True):
+               want_arg=True, shift=0, ws=None):
     """ofx_spmm_csr_reduce(_cpu) on the tensors' device: (out, arg) for rows [row_begin, row_end),
-    with leading dimensions n + pad."""
+    with leading dimensions n + pad; b, out and arg start `shift` elements into their buffers.
+    ws: the device workspace to launch on (else one of the queried size)."""
     row_end = m if row_end is None else row_end
     code = REDUCE_CODES[reduce]
     dev, n = b.device, b.shape[1]
-    bb = padded(b, pad)
+    bb = padded(b, pad, shift)
     rows = row_end - row_begin
-    out = padded(torch.empty((rows, n), dtype=b.dtype, device=dev), pad)
-    arg = padded(torch.full((rows, n), -9, dtype=rp.dtype, device=dev), pad) if want_arg else None
+    out = padded(torch.empty((rows, n), dtype=b.dtype, device=dev), pad, shift)
+    arg = padded(torch.full((rows, n), -9, dtype=rp.dtype, device=dev), pad, shift) \
+        if want_arg else None
     it, vt, nnz = dtype_code(rp.dtype), dtype_code(b.dtype), ci.numel()
     o = ctypes.byref(opts) if opts is not None else None
     tail = (_ptr(rp), _ptr(ci), _ptr(vals), _ptr(bb), n + pad, _ptr(out), n + pad, _ptr(arg),
@@ -181,40 +249,48 @@ def run_reduce(rp, ci, vals, b, m, k, reduce, *, pad=0, row_begin=0, row_end=Non
     if dev.type == "cpu":
         check(LIB.ofx_spmm_csr_reduce_cpu(0, it, vt, m, k, n, nnz, *tail, o), "reduce_cpu")
     else:
-        ws, size = _workspace(lambda s: check(LIB.ofx_spmm_csr_reduce_workspace_size(
-            it, vt, m, k, n, nnz, code, o, s)), dev)
+        ws, size = _device_workspace(lambda s: check(LIB.ofx_spmm_csr_reduce_workspace_size(
+            it, vt, m, k, n, nnz, code, o, s)), dev, ws)
         check(LIB.ofx_spmm_csr_reduce(current_stream_handle(b), it, vt, m, k, n, nnz, *tail,
                                       ws.data_ptr(), size, o), "reduce")
     return out, arg
 
 
-def run_grad_b(rp_t, ci_t, perm, vals, arg, g, m, k, *, pad=0, opts=None):
-    """ofx_spmm_csr_select(_cpu): d(b) [k, n] with leading dimensions n + pad."""
+def run_grad_b(rp_t, ci_t, perm, vals, arg, g, m, k, *, pad=0, opts=None, row_begin=0,
+               row_end=None, ws=None):
+    """ofx_spmm_csr_select(_cpu): d(b) of A^T's rows [row_begin, row_end) (all k by default),
+    row_end - row_begin rows with leading dimensions n + pad; arg and g over all m rows."""
+    row_end = k if row_end is None else row_end
     dev, n = g.device, g.shape[1]
     aa, gg = padded(arg, pad), padded(g, pad)
-    db = padded(torch.empty((k, n), dtype=g.dtype, device=dev), pad)
+    db = padded(torch.empty((row_end - row_begin, n), dtype=g.dtype, device=dev), pad)
     it, vt, nnz = dtype_code(rp_t.dtype), dtype_code(g.dtype), perm.numel()
     o = ctypes.byref(opts) if opts is not None else None
     tail = (_ptr(rp_t), _ptr(ci_t), _ptr(perm), _ptr(vals), _ptr(aa), n + pad, _ptr(gg), n + pad,
-            _ptr(db), n + pad, 0, k)
+            _ptr(db), n + pad, row_begin, row_end)
     if dev.type == "cpu":
         check(LIB.ofx_spmm_csr_select_cpu(0, it, vt, m, k, n, nnz, *tail, o), "select_cpu")
     else:
-        ws, size = _workspace(lambda s: check(LIB.ofx_spmm_csr_select_workspace_size(
-            it, vt, m, k, n, nnz, o, s)), dev)
+        ws, size = _device_workspace(lambda s: check(LIB.ofx_spmm_csr_select_workspace_size(
+            it, vt, m, k, n, nnz, o, s)), dev, ws)
         check(LIB.ofx_spmm_csr_select(current_stream_handle(g), it, vt, m, k, n, nnz, *tail,
                                       ws.data_ptr(), size, o), "select")
     return db
 
 
-def run_grad_values(rp, ci, arg, g, b, m, k, *, pad=0):
-    """ofx_sddmm_csr_select(_cpu): d(values) [nnz] with leading dimensions n + pad."""
+def run_grad_values(rp, ci, arg, g, b, m, k, *, pad=0, row_begin=0, row_end=None, out=None):
+    """ofx_sddmm_csr_select(_cpu) over A's rows [row_begin, row_end) (all m by default), with
+    leading dimensions n + pad: all nnz entries of d(values), those outside the range still
+    holding sentinel()'s bits (is_sentinel).  arg and g are given over all m rows; the entry gets
+    them rebased to the range, in buffers of m rows (rebased()).  out: the buffer to write to."""
+    row_end = m if row_end is None else row_end
     dev, n = b.device, b.shape[1]
-    aa, gg, bb = padded(arg, pad), padded(g, pad), padded(b, pad)
-    out = torch.empty(ci.numel(), dtype=b.dtype, device=dev)
+    aa, gg = rebased(arg, row_begin, row_end, pad), rebased(g, row_begin, row_end, pad)
+    bb = padded(b, pad)
+    out = sentinel((ci.numel(),), b.dtype, dev) if out is None else out
     it, vt, nnz = dtype_code(rp.dtype), dtype_code(b.dtype), ci.numel()
     tail = (_ptr(rp), _ptr(ci), _ptr(aa), n + pad, _ptr(gg), n + pad, _ptr(bb), n + pad, _ptr(out),
-            0, m)
+            row_begin, row_end)
     if dev.type == "cpu":
         check(LIB.ofx_sddmm_csr_select_cpu(0, it, vt, m, k, n, nnz, *tail), "sddmm_select_cpu")
     else:
@@ -223,6 +299,24 @@ def run_grad_values(rp, ci, arg, g, b, m, k, *, pad=0):
         check(LIB.ofx_sddmm_csr_select(current_stream_handle(b), it, vt, m, k, n, nnz, *tail,
                                        ws.data_ptr(), size), "sddmm_select")
     return out
+
+
+def run_row_scale(rp, src, m, *, row_begin=0, row_end=None, pad_src=0, pad_dst=0):
+    """ofx_row_scale_by_degree(_cpu) out of place on src's device: src holds the rows
+    [row_begin, row_end) (leading dimension n + pad_src); returns dst (n + pad_dst), a view of a
+    NaN-filled buffer (dst._base)."""
+    row_end = m if row_end is None else row_end
+    dev, n = src.device, src.shape[1]
+    ss = padded(src, pad_src)
+    dst = padded(torch.empty_like(src), pad_dst)
+    it, vt = dtype_code(rp.dtype), dtype_code(src.dtype)
+    tail = (it, vt, m, n, _ptr(rp), _ptr(ss), n + pad_src, _ptr(dst), n + pad_dst, row_begin,
+            row_end)
+    if dev.type == "cpu":
+        check(LIB.ofx_row_scale_by_degree_cpu(0, *tail), "row_scale_cpu")
+    else:
+        check(LIB.ofx_row_scale_by_degree(current_stream_handle(src), *tail), "row_scale")
+    return dst
 
 
 def transpose_t(rp, ci, k):

@@ -47,9 +47,28 @@ def test_special_values(dt):
     rc.check_special(DEV, DTYPES[dt])
 
 
+@pytest.mark.parametrize("dt,n", rc.WIDE_WIDTHS)
+def test_wide_widths(dt, n):
+    # the kCPU kernels at the widths of the GPU's test_wide_widths (its reference there)
+    rp, ci, vals, b, g = rc.base_problem(n, DTYPES[dt])
+    rc.check_all(DEV, rp, ci, vals, b, g, rc.M, rc.K, pad=PAD, what=f"wide {dt} n={n}")
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_wide_random_values(dt):
+    rp, ci, vals, b, g = rc.base_problem(1030, DTYPES[dt], seed=5, exact=False)
+    rc.check_all(DEV, rp, ci, vals, b, g, rc.M, rc.K, pad=PAD, what=f"wide random {dt}")
+
+
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 def test_hub_tiny(dt):
     rc.check_hub_tiny(DEV, DTYPES[dt])
+
+
+@pytest.mark.parametrize("dt,it", [("f64", torch.int32), ("f16", torch.int32),
+                                   ("f32", torch.int64), ("f64", torch.int64)])
+def test_hub_tiny_other_types(dt, it):
+    rc.check_hub_tiny(DEV, DTYPES[dt], idx_dtype=it)
 
 
 @pytest.mark.parametrize("n", [16, 128, 256])
@@ -65,6 +84,22 @@ def test_binned_work_list_shape():
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 def test_row_ranges(dt):
     rc.check_row_ranges(DEV, DTYPES[dt])
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_gradient_row_ranges(dt):
+    rc.check_gradient_row_ranges(DEV, DTYPES[dt])
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_hub_row_ranges(dt):
+    rc.check_hub_ranges(DEV, DTYPES[dt])
+
+
+@pytest.mark.parametrize("it", [torch.int32, torch.int64])
+@pytest.mark.parametrize("dt", ["f32", "f64", "bf16", "f16"])
+def test_row_scale_out_of_place_range(dt, it):
+    rc.check_row_scale(DEV, DTYPES[dt], it)
 
 
 def test_degenerate_sizes():
