@@ -3,7 +3,8 @@
 // For C = A @ B with A in CSR (values v):
 //   dB = A^T @ dC       -> ofx_csr_transpose (structure, once per graph) + ofx_gather_values
 //                          (A^T values = v[perm]) + the forward SpMM kernel on A^T
-//   dv[j] = <dC[row(j),:], B[col(j),:]>  (SDDMM on A's pattern) -> ofx_sddmm_csr
+//   dv[j] = <dC[row(j),:], B[col(j),:]>  (SDDMM on A's pattern) -> ofx_sddmm_csr, and its masked
+//                          form for the max / min reductions -> ofx_sddmm_csr_select
 // Reference anchors: the gradient-function pattern of matrix_vector_product
 // (oneflow/core/autograd/gradient_funcs/matrix_vector_product.cpp:26-91: dA = dy x b^T restricted,
 // db = a^T x dy) and the transpose-by-sort building blocks the reference keeps for CUDA
@@ -20,16 +21,13 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <climits>
-
-#include "ofx_internal.h"
-#include "spmm_common.h"
-#include "spmm_plan.h"
+#include "spmm_extremum.h"
+#include "spmm_items_dev.h"
 
 namespace ofx {
 namespace {
 
-constexpr int kBlock = 256;
+using namespace item;
 
 template <typename I>
 __global__ void iota_kernel(I* __restrict__ out, int64_t n) {
@@ -156,153 +154,164 @@ int transpose(hipStream_t s, int64_t m, int64_t k, int64_t nnz, const I* rp, con
 // L contiguous 8-element leaves [t*L, (t+1)*L) of the N-vector: it keeps dC[row] in registers
 // for the whole row and streams B[col] rows, U nonzeros in flight.  In-lane pairwise over its L
 // leaves, then an xor butterfly over the LG lanes = the pairwise tree over LG*L leaves.
+//
+// The masked SDDMM (ofx_sddmm_csr_select, d(values) of the max / min reductions) is the same walk
+// with the lane's leaves of arg[row] kept beside dC[row]:
+//   d(values)[j] = sum over columns c of (arg[r, c] == j ? g[r, c] * b[col[j], c] : +0).
+// A column the nonzero did not win contributes +0 whatever b holds (an inf or NaN there does not
+// leak into the gradient).  Padding the leaves to a larger power of two adds +0 to sums that are
+// never -0, so its lane-group widths (a subset of the plain ones) give the same bits.
 constexpr int kLeaf = 8;
 
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void load_leaf(const T* __restrict__ p, int64_t base, int64_t n,
-                                          typename Num<T>::acc (&x)[kLeaf]) {
-  using A = typename Num<T>::acc;
-  if constexpr (ALIGNED) {  // n % 8 == 0, rows 16-B aligned: a leaf is all in or all out
-    if (base >= n) {
+// The masked SDDMM's extra kernel argument: arg and its leading dimension.  The plain SDDMM
+// passes NoMask, so that it carries no unused arguments.
+template <typename I>
+struct ArgMask {
+  const I* arg;
+  int64_t ld;
+};
+struct NoMask {};
+
+// A lane's leaf as it sits in registers.  R = T: the storage type, converted in the term (the
+// masked SDDMM, which keeps its arg leaves too: for 16-bit types the form decides the register
+// count).  R = the accumulation type: converted pack by pack as it is loaded (the plain SDDMM;
+// converting a whole leaf after its loads costs the unaligned kernels two VGPRs and a wave).
+template <typename T, typename R, bool ALIGNED>
+__device__ __forceinline__ void load_regs(const T* __restrict__ row, int64_t cb, int64_t n,
+                                          R (&x)[kLeaf]) {
+  if constexpr (std::is_same_v<R, T>) {
+    load_cols<T, kLeaf, ALIGNED>(row, cb, n, Num<T>::store(typename Num<T>::acc(0)), x);
+  } else if constexpr (ALIGNED) {
+    if (cb >= n) {
 #pragma unroll
-      for (int e = 0; e < kLeaf; ++e) x[e] = A(0);
+      for (int e = 0; e < kLeaf; ++e) x[e] = R(0);
       return;
     }
-    struct alignas(16) P16 {
-      T v[16 / sizeof(T) < kLeaf ? 16 / sizeof(T) : kLeaf];
-    };
-    constexpr int per = sizeof(P16) / sizeof(T);
+    constexpr int per = 16 / sizeof(T) < kLeaf ? 16 / sizeof(T) : kLeaf;
 #pragma unroll
     for (int q = 0; q < kLeaf / per; ++q) {
-      const P16 v = *reinterpret_cast<const P16*>(p + base + q * per);
+      const Pack<T, per> p = *reinterpret_cast<const Pack<T, per>*>(row + cb + q * per);
 #pragma unroll
-      for (int e = 0; e < per; ++e) x[q * per + e] = Num<T>::load(v.v[e]);
+      for (int e = 0; e < per; ++e) x[q * per + e] = Num<T>::load(p.v[e]);
     }
   } else {
 #pragma unroll
-    for (int e = 0; e < kLeaf; ++e) x[e] = base + e < n ? Num<T>::load(p[base + e]) : A(0);
+    for (int e = 0; e < kLeaf; ++e) x[e] = cb + e < n ? Num<T>::load(row[cb + e]) : R(0);
   }
 }
 
-// Work item of lane-group g: (local row, nonzero range) of a row or hub chunk; false if none.
-template <typename I>
-__device__ __forceinline__ bool sddmm_item(const I* __restrict__ rp, int64_t g, int64_t row_begin,
-                                           int64_t nrows, int64_t chunk,
-                                           const unsigned long long* __restrict__ counters,
-                                           const int64_t* __restrict__ items,
-                                           const int64_t* __restrict__ order, int64_t* lr_out,
-                                           int64_t* j0_out, int64_t* j1_out) {
-  int64_t lr, c = -1;
-  if (order == nullptr) {
-    if (g >= nrows) return false;
-    lr = g;
-  } else {
-    const int64_t nchunks = (int64_t)counters[0];
-    if (g < nchunks) {
-      lr = items[2 * g];
-      c = items[2 * g + 1];
-    } else {
-      const int64_t q = g - nchunks;
-      if (q >= nrows - (int64_t)counters[1]) return false;
-      lr = plan::order_row(order, nrows, (int64_t)counters[3] - (int64_t)counters[2], q);
-    }
-  }
-  const int64_t r = row_begin + lr;
-  const int64_t rs = (int64_t)rp[r], re = (int64_t)rp[r + 1];
-  int64_t j0 = rs, j1 = re;
-  if (c >= 0) {  // chunk c of len / chunk; the last takes the remainder
-    j0 = rs + c * chunk;
-    j1 = (re - j0 - chunk < chunk) ? re : j0 + chunk;
-  }
-  *lr_out = lr;
-  *j0_out = j0;
-  *j1_out = j1;
-  return j0 < j1;
+template <typename T, typename R>
+__device__ __forceinline__ typename Num<T>::acc as_acc(R v) {
+  if constexpr (std::is_same_v<R, T>) return Num<T>::load(v);
+  else return v;
 }
 
-// A work list from a failed, superseded or never-built plan: the launch fills its output (the
-// nonzeros of its rows, out[rp[row_begin] .. rp[row_begin + nrows])) with the canonical quiet NaN
-// and reports it (spmm_plan.h plan_valid; the host's next entry returns OFX_EPLAN).  Every launch
-// of a cut grid poisons the whole range (idempotent).
-template <typename T, typename I>
-__device__ __forceinline__ bool sddmm_plan_invalid(const unsigned long long* __restrict__ counters,
-                                                   int64_t block_base, unsigned* err,
-                                                   const I* __restrict__ rp, int64_t row_begin,
-                                                   int64_t nrows, T* __restrict__ out) {
-  if (counters == nullptr || plan::plan_valid(counters)) return false;
-  if (block_base + blockIdx.x == 0 && threadIdx.x == 0)
-    plan::raise_device_error(err, plan::kErrPlanInvalid);
-  const int64_t j0 = (int64_t)rp[row_begin], j1 = (int64_t)rp[row_begin + nrows];
-  const T p = poison_value<T>();
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = j0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < j1; j += stride) out[j] = p;
-  return true;
+// One nonzero's value over a group of LG lanes, each holding L leaves of both rows: the leaf sums
+// (sequential from +0), the in-lane pairwise tree and the xor butterfly of the contract.
+template <typename T, int LG, int L>
+__device__ __forceinline__ typename Num<T>::acc sddmm_dot(
+    const typename Num<T>::acc (&a)[L][kLeaf], const typename Num<T>::acc (&b)[L][kLeaf]) {
+#pragma clang fp contract(off)
+  using A = typename Num<T>::acc;
+  A leaf[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    A s = A(0);
+#pragma unroll
+    for (int e = 0; e < kLeaf; ++e) s = s + a[l][e] * b[l][e];
+    leaf[l] = s;
+  }
+#pragma unroll
+  for (int x = 1; x < L; x <<= 1)
+#pragma unroll
+    for (int l = 0; l < L; l += 2 * x) leaf[l] = leaf[l] + leaf[l + x];
+  A t = leaf[0];
+#pragma unroll
+  for (int x = 1; x < LG; x <<= 1) t = t + __shfl_xor(t, x, 64);
+  return t;
 }
 
-// Grid pieces: a launch holds fewer than 2^32 threads (papers-scale row counts would not).
-constexpr int64_t kLaunchBlocks = ((int64_t)1 << 31) / kBlock;
-
-template <typename T, typename I, int LG, int L, int U, bool ALIGNED>
+template <typename T, typename I, int LG, int L, int U, bool ALIGNED, typename M>
 __global__ void __launch_bounds__(kBlock)
     sddmm_kernel(const I* __restrict__ rp, const I* __restrict__ col, const T* __restrict__ dC,
                  int64_t ldc, const T* __restrict__ B, int64_t ldb, int64_t kb,
                  T* __restrict__ out, int64_t row_begin, int64_t nrows, int64_t n, int64_t chunk,
                  const unsigned long long* __restrict__ counters, const int64_t* __restrict__ items,
-                 const int64_t* __restrict__ order, int64_t block_base, unsigned* err) {
+                 const int64_t* __restrict__ order, int64_t block_base, unsigned* err, M mask) {
 #pragma clang fp contract(off)
+  constexpr bool MASKED = !std::is_same_v<M, NoMask>;
   using A = typename Num<T>::acc;
+  using R = std::conditional_t<MASKED, T, A>;
   constexpr int GPW = 64 / LG;
-  if (sddmm_plan_invalid(counters, block_base, err, rp, row_begin, nrows, out)) return;
+  if (poison_nonzeros(counters, block_base, err, rp, row_begin, nrows, out)) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int gl = lane & (LG - 1);
-  const int64_t g = ((block_base + (int64_t)blockIdx.x) * (kBlock / 64) + wave) * GPW + lane / LG;
-  int64_t lr, j0, j1;
-  if (!sddmm_item<I>(rp, g, row_begin, nrows, chunk, counters, items, order, &lr, &j0, &j1)) return;
-  // dC row, this lane's leaves
-  A a[L][kLeaf];
-  const T* arow = dC + lr * ldc;
-#pragma unroll
-  for (int l = 0; l < L; ++l) load_leaf<T, ALIGNED>(arow, (int64_t)(gl * L + l) * kLeaf, n, a[l]);
   const int gbase = lane & ~(LG - 1);
+  const int64_t g = ((block_base + (int64_t)blockIdx.x) * (kBlock / 64) + wave) * GPW + lane / LG;
+  Item it;
+  if (!work_item<I>(rp, g, row_begin, nrows, chunk, counters, items, order, &it, true)) return;
+  // this lane's leaves of the dC row (and of arg), kept for the whole item
+  R a[L][kLeaf];
+  std::conditional_t<MASKED, I[L][kLeaf], NoMask> w;
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const int64_t cb = (int64_t)(gl * L + l) * kLeaf;
+    load_regs<T, R, ALIGNED>(dC + it.lr * ldc, cb, n, a[l]);
+    if constexpr (MASKED)
+      load_cols<I, kLeaf, ALIGNED>(mask.arg + it.lr * mask.ld, cb, n, I(-1), w[l]);
+  }
   // Column indices come LG at a time (one coalesced load per group, then ds_bpermute), so the
   // B-row loads of a batch never wait behind a dependent index load; lane t keeps the result of
   // the batch's t-th nonzero and the group stores LG results with one coalesced store.
-  for (int64_t jb = j0; jb < j1; jb += LG) {
-    const int cnt = (int)((j1 - jb) < LG ? (j1 - jb) : LG);
+  for (int64_t jb = it.j0; jb < it.j1; jb += LG) {
+    const int cnt = (int)((it.j1 - jb) < LG ? (it.j1 - jb) : LG);
     const I myc = gl < cnt ? col[jb + gl] : I(0);
     A res = A(0);
     for (int k = 0; k < cnt; k += U) {
-      A bv[U][L][kLeaf];
+      R bv[U][L][kLeaf];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t cu = (int64_t)__shfl((int64_t)myc, gbase + ((k + u) & (LG - 1)), 64);
         if (k + u < cnt) {
-          // a column outside [0, k): the forward gathered a zero row (zero_row_leaves)
-          const T* brow = B + cu * ldb;
+          // a column outside [0, k): the forward gathered a zero row (zero_row_leaves); every
+          // leaf reads as out of range and the row's address is never used
           const bool in = (uint64_t)cu < (uint64_t)kb;
 #pragma unroll
-          for (int l = 0; l < L; ++l) load_leaf<T, ALIGNED>(brow, in ? (int64_t)(gl * L + l) * kLeaf : n, n, bv[u][l]);
+          for (int l = 0; l < L; ++l)
+            load_regs<T, R, ALIGNED>(B + cu * ldb, in ? (int64_t)(gl * L + l) * kLeaf : n, n,
+                                     bv[u][l]);
         }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (k + u < cnt) {
+          // Written out here, not a call of sddmm_dot: through the helper the f32 kernels zero
+          // their B leaves before every load and lose the packed multiplies (the masked N = 128
+          // launch of the products graph measured 0.4-1 % slower), and with the butterfly inside
+          // the helper a lane's B leaves are copied whole per nonzero (f32, LG = 16: 70 -> 106
+          // VGPRs).  The wide kernel, one wave per item, takes the helper.
+          const I j = (I)(jb + k + u);
           A leaf[L];
 #pragma unroll
           for (int l = 0; l < L; ++l) {
             A s = A(0);
 #pragma unroll
-            for (int e = 0; e < kLeaf; ++e) s = s + a[l][e] * bv[u][l][e];
+            for (int e = 0; e < kLeaf; ++e) {
+              if constexpr (MASKED)
+                s = s + (w[l][e] == j ? as_acc<T>(a[l][e]) * as_acc<T>(bv[u][l][e]) : A(0));
+              else
+                s = s + as_acc<T>(a[l][e]) * as_acc<T>(bv[u][l][e]);
+            }
             leaf[l] = s;
           }
 #pragma unroll
-          for (int w = 1; w < L; w <<= 1)
+          for (int x = 1; x < L; x <<= 1)
 #pragma unroll
-            for (int l = 0; l < L; l += 2 * w) leaf[l] = leaf[l] + leaf[l + w];
+            for (int l = 0; l < L; l += 2 * x) leaf[l] = leaf[l] + leaf[l + x];
           A t = leaf[0];
 #pragma unroll
-          for (int w = 1; w < LG; w <<= 1) t = t + __shfl_xor(t, w, 64);
+          for (int x = 1; x < LG; x <<= 1) t = t + __shfl_xor(t, x, 64);
           if (gl == k + u) res = t;
         }
       }
@@ -332,15 +341,15 @@ __global__ void __launch_bounds__(kBlock)
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
   constexpr int L = kWideLeaves / 64, U = 2;
-  if (sddmm_plan_invalid(counters, block_base, err, rp, row_begin, nrows, out)) return;
+  if (poison_nonzeros(counters, block_base, err, rp, row_begin, nrows, out)) return;
   const int lane = threadIdx.x & 63;
   const int64_t g = (block_base + (int64_t)blockIdx.x) * (kBlock / 64) +
                     __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int64_t lr, j0, j1;
-  if (!sddmm_item<I>(rp, g, row_begin, nrows, chunk, counters, items, order, &lr, &j0, &j1)) return;
-  const T* arow = dC + lr * ldc;
-  for (int64_t jb = j0; jb < j1; jb += 64) {
-    const int cnt = (int)((j1 - jb) < 64 ? (j1 - jb) : 64);
+  Item it;
+  if (!work_item<I>(rp, g, row_begin, nrows, chunk, counters, items, order, &it)) return;
+  const T* arow = dC + it.lr * ldc;
+  for (int64_t jb = it.j0; jb < it.j1; jb += 64) {
+    const int cnt = (int)((it.j1 - jb) < 64 ? (it.j1 - jb) : 64);
     const I myc = lane < cnt ? col[jb + lane] : I(0);
     A stk[kMaxTilesLog + 1];
 #pragma unroll
@@ -349,7 +358,7 @@ __global__ void __launch_bounds__(kBlock)
       const int64_t leaf0 = (int64_t)t * kWideLeaves + (int64_t)lane * L;
       A a[L][kLeaf];
 #pragma unroll
-      for (int l = 0; l < L; ++l) load_leaf<T, ALIGNED>(arow, (leaf0 + l) * kLeaf, n, a[l]);
+      for (int l = 0; l < L; ++l) load_regs<T, A, ALIGNED>(arow, (leaf0 + l) * kLeaf, n, a[l]);
       A tv = A(0);
       for (int k = 0; k < cnt; k += U) {
         A bv[U][L][kLeaf];
@@ -357,30 +366,16 @@ __global__ void __launch_bounds__(kBlock)
         for (int u = 0; u < U; ++u) {
           const int64_t cu = (int64_t)__shfl((int64_t)myc, (k + u) & 63, 64);
           if (k + u < cnt) {
-            const T* brow = B + cu * ldb;
             const bool in = (uint64_t)cu < (uint64_t)kb;  // else a zero row
 #pragma unroll
-            for (int l = 0; l < L; ++l) load_leaf<T, ALIGNED>(brow, in ? (leaf0 + l) * kLeaf : n, n, bv[u][l]);
+            for (int l = 0; l < L; ++l)
+              load_regs<T, A, ALIGNED>(B + cu * ldb, in ? (leaf0 + l) * kLeaf : n, n, bv[u][l]);
           }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           if (k + u < cnt) {
-            A leaf[L];
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-              A sl = A(0);
-#pragma unroll
-              for (int e = 0; e < kLeaf; ++e) sl = sl + a[l][e] * bv[u][l][e];
-              leaf[l] = sl;
-            }
-#pragma unroll
-            for (int w = 1; w < L; w <<= 1)
-#pragma unroll
-              for (int l = 0; l < L; l += 2 * w) leaf[l] = leaf[l] + leaf[l + w];
-            A x = leaf[0];
-#pragma unroll
-            for (int w = 1; w < 64; w <<= 1) x = x + __shfl_xor(x, w, 64);
+            const A x = sddmm_dot<T, 64, L>(a, bv[u]);
             if (lane == k + u) tv = x;
           }
         }
@@ -409,10 +404,11 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 struct SddmmArgs {
+  const char* fn;
   hipStream_t s;
-  const void *rp, *col, *dC, *B;
+  const void *rp, *col, *arg, *dC, *B;  // arg: the masked SDDMM's, else NULL
   void* out;
-  int64_t ldc, ldb, row_begin, nrows, n, nnz, k;
+  int64_t ldarg, ldc, ldb, row_begin, nrows, n, nnz, k;
   void* ws;
   size_t ws_bytes;
   bool planned;  // ws already holds this launch's plan (ofx_sddmm_csr_plan): no planner launch
@@ -425,12 +421,19 @@ struct SddmmArgs {
 // (1M power-law, N=32: 1.67 ms, slower than N=64).  Items of at most kSddmmChunk nonzeros keep the
 // chains short; the wide kernel (n > 2048, one wave per item) keeps the forward's cut.
 constexpr int64_t kSddmmChunk = 256;
-constexpr int64_t kMaxNarrowN = 256 * kLeaf;  // sddmm_aligned's narrow configurations
+constexpr int64_t kMaxNarrowN = 256 * kLeaf;  // the narrow configurations: 64 lanes x 4 leaves
 
 Schedule sddmm_schedule(int64_t n) {
   Schedule s = resolve_schedule(n, nullptr);
   if (n <= kMaxNarrowN) s.split = s.chunk = kSddmmChunk;
   return s;
+}
+
+// The work list of either SDDMM: no partials, no options.
+template <typename I>
+int sddmm_plan(const SddmmArgs& a, Planned* p) {
+  return prepare_plan<I>(a.fn, a.s, static_cast<const I*>(a.rp), a.row_begin, a.nrows, a.nnz, a.nnz,
+                         0, 0, sddmm_schedule(a.n), a.planned, a.ws, a.ws_bytes, p);
 }
 
 #ifndef OFX_SD_U
@@ -442,102 +445,78 @@ Schedule sddmm_schedule(int64_t n) {
 #ifndef OFX_SD_LG16
 #define OFX_SD_LG16 16
 #endif
-template <typename T, typename I, int LG, int L, bool ALIGNED>
+template <typename T, typename I, int LG, int L, bool ALIGNED, bool MASKED>
 int sddmm_cfg(const SddmmArgs& a) {
-  constexpr int U = OFX_SD_U > 0 ? OFX_SD_U : (L >= 4 ? 2 : 4);
-  constexpr int64_t GPB = (kBlock / 64) * (64 / LG);
-  const Schedule sched = sddmm_schedule(a.n);
-  const plan::WsLayout w = plan::ws_layout(a.nrows, a.nnz, 0, 0, sched);
-  plan::WorkList wl{};
-  if (w.total > 0) {
-    OFX_REQUIRE(a.ws && a.ws_bytes >= w.total, OFX_EWORKSPACE,
-                "sddmm_csr: workspace of %zu bytes < %zu required", a.ws_bytes, w.total);
-    if (a.planned) {
-      plan::worklist_of(w, static_cast<char*>(a.ws), &wl);
-    } else {
-      const int rc = plan::launch_plan<I>(a.s, static_cast<const I*>(a.rp), a.row_begin, a.nrows,
-                                          a.nnz, sched, w, static_cast<char*>(a.ws), &wl);
-      if (rc) return rc;
-    }
-  }
-  const int64_t work = a.nrows + (w.total > 0 ? w.max_chunks : 0);
-  const int64_t grid = (work + GPB - 1) / GPB;
-  for (int64_t b0 = 0; b0 < grid; b0 += kLaunchBlocks) {  // < 2^31 threads per launch
-    hipLaunchKernelGGL((sddmm_kernel<T, I, LG, L, U, ALIGNED>),
-                       dim3((unsigned)std::min(kLaunchBlocks, grid - b0)), dim3(kBlock), 0, a.s,
+  constexpr int U = !MASKED && OFX_SD_U > 0 ? OFX_SD_U : (L >= 4 ? 2 : 4);
+  using M = std::conditional_t<MASKED, ArgMask<I>, NoMask>;
+  M mask{};
+  if constexpr (MASKED) mask = M{static_cast<const I*>(a.arg), a.ldarg};
+  Planned p;
+  if (const int rc = sddmm_plan<I>(a, &p)) return rc;
+  return launch_cut_grid(p.work, (kBlock / 64) * (64 / LG), [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL((sddmm_kernel<T, I, LG, L, U, ALIGNED, M>), grid, dim3(kBlock), 0, a.s,
                        static_cast<const I*>(a.rp), static_cast<const I*>(a.col),
                        static_cast<const T*>(a.dC), a.ldc, static_cast<const T*>(a.B), a.ldb, a.k,
-                       static_cast<T*>(a.out), a.row_begin, a.nrows, a.n,
-                       w.total > 0 ? sched.chunk : INT64_MAX, wl.counters, wl.items, wl.order, b0,
-                       w.total > 0 ? device_error_words() : nullptr);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
-  return OFX_OK;
+                       static_cast<T*>(a.out), a.row_begin, a.nrows, a.n, p.chunk, p.wl.counters,
+                       p.wl.items, p.wl.order, b0, p.err, mask);
+  });
 }
 
+// The plain SDDMM's widths.
 template <typename T, typename I, bool ALIGNED>
-int sddmm_aligned(const SddmmArgs& a) {
+int sddmm_width(const SddmmArgs& a) {
   const int64_t leaves = (a.n + kLeaf - 1) / kLeaf;
-  if (leaves <= 1) return sddmm_cfg<T, I, 1, 1, ALIGNED>(a);
-  if (leaves <= 2) return sddmm_cfg<T, I, 2, 1, ALIGNED>(a);
-  if (leaves <= 4) return sddmm_cfg<T, I, 4, 1, ALIGNED>(a);
-  if (leaves <= 8) return sddmm_cfg<T, I, OFX_SD_LG8, 8 / OFX_SD_LG8, ALIGNED>(a);
-  if (leaves <= 16) return sddmm_cfg<T, I, OFX_SD_LG16, 16 / OFX_SD_LG16, ALIGNED>(a);
-  if (leaves <= 32) return sddmm_cfg<T, I, 32, 1, ALIGNED>(a);
-  if (leaves <= 64) return sddmm_cfg<T, I, 64, 1, ALIGNED>(a);
-  if (leaves <= 128) return sddmm_cfg<T, I, 64, 2, ALIGNED>(a);
-  if (leaves <= 256) return sddmm_cfg<T, I, 64, 4, ALIGNED>(a);
+  if (leaves <= 1) return sddmm_cfg<T, I, 1, 1, ALIGNED, false>(a);
+  if (leaves <= 2) return sddmm_cfg<T, I, 2, 1, ALIGNED, false>(a);
+  if (leaves <= 4) return sddmm_cfg<T, I, 4, 1, ALIGNED, false>(a);
+  if (leaves <= 8) return sddmm_cfg<T, I, OFX_SD_LG8, 8 / OFX_SD_LG8, ALIGNED, false>(a);
+  if (leaves <= 16) return sddmm_cfg<T, I, OFX_SD_LG16, 16 / OFX_SD_LG16, ALIGNED, false>(a);
+  if (leaves <= 32) return sddmm_cfg<T, I, 32, 1, ALIGNED, false>(a);
+  if (leaves <= 64) return sddmm_cfg<T, I, 64, 1, ALIGNED, false>(a);
+  if (leaves <= 128) return sddmm_cfg<T, I, 64, 2, ALIGNED, false>(a);
+  if (leaves <= 256) return sddmm_cfg<T, I, 64, 4, ALIGNED, false>(a);
   int64_t tiles = 1;
   while (tiles * kWideLeaves < leaves) tiles *= 2;
   OFX_REQUIRE(tiles <= (1 << kMaxTilesLog), OFX_EUNSUPPORTED,
               "sddmm_csr: n=%lld > %d is not supported", (long long)a.n,
               kWideLeaves * kLeaf << kMaxTilesLog);
-  const Schedule sched = sddmm_schedule(a.n);
-  const plan::WsLayout w = plan::ws_layout(a.nrows, a.nnz, 0, 0, sched);
-  plan::WorkList wl{};
-  if (w.total > 0) {
-    OFX_REQUIRE(a.ws && a.ws_bytes >= w.total, OFX_EWORKSPACE,
-                "sddmm_csr: workspace of %zu bytes < %zu required", a.ws_bytes, w.total);
-    if (a.planned) {
-      plan::worklist_of(w, static_cast<char*>(a.ws), &wl);
-    } else {
-      const int rc = plan::launch_plan<I>(a.s, static_cast<const I*>(a.rp), a.row_begin, a.nrows,
-                                          a.nnz, sched, w, static_cast<char*>(a.ws), &wl);
-      if (rc) return rc;
-    }
-  }
-  const int64_t work = a.nrows + (w.total > 0 ? w.max_chunks : 0);
-  const int64_t grid = (work + kBlock / 64 - 1) / (kBlock / 64);
-  for (int64_t b0 = 0; b0 < grid; b0 += kLaunchBlocks) {  // < 2^31 threads per launch
-    hipLaunchKernelGGL((sddmm_wide_kernel<T, I, ALIGNED>),
-                       dim3((unsigned)std::min(kLaunchBlocks, grid - b0)), dim3(kBlock), 0, a.s,
+  Planned p;
+  if (const int rc = sddmm_plan<I>(a, &p)) return rc;
+  return launch_cut_grid(p.work, kBlock / 64, [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL((sddmm_wide_kernel<T, I, ALIGNED>), grid, dim3(kBlock), 0, a.s,
                        static_cast<const I*>(a.rp), static_cast<const I*>(a.col),
                        static_cast<const T*>(a.dC), a.ldc, static_cast<const T*>(a.B), a.ldb, a.k,
-                       static_cast<T*>(a.out), a.row_begin, a.nrows, a.n,
-                       w.total > 0 ? sched.chunk : INT64_MAX, (int)tiles, wl.counters, wl.items,
-                       wl.order, b0, w.total > 0 ? device_error_words() : nullptr);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
-  return OFX_OK;
+                       static_cast<T*>(a.out), a.row_begin, a.nrows, a.n, p.chunk, (int)tiles,
+                       p.wl.counters, p.wl.items, p.wl.order, b0, p.err);
+  });
 }
 
-template <typename T, typename I>
-int sddmm_typed(const SddmmArgs& a) {
-  const bool aligned = a.n % kLeaf == 0 && a.ldc % kLeaf == 0 && a.ldb % kLeaf == 0 &&
-                       ((uintptr_t)a.dC % 16) == 0 && ((uintptr_t)a.B % 16) == 0 &&
-                       ((size_t)a.ldc * sizeof(T)) % 16 == 0 && ((size_t)a.ldb * sizeof(T)) % 16 == 0;
-  return aligned ? sddmm_aligned<T, I, true>(a) : sddmm_aligned<T, I, false>(a);
+// The masked SDDMM's widths (the entry refuses n > kMaxNarrowN).
+template <typename T, typename I, bool ALIGNED>
+int sddmm_select_width(const SddmmArgs& a) {
+  const int64_t leaves = (a.n + kLeaf - 1) / kLeaf;
+  if (leaves <= 1) return sddmm_cfg<T, I, 1, 1, ALIGNED, true>(a);
+  if (leaves <= 4) return sddmm_cfg<T, I, 4, 1, ALIGNED, true>(a);
+  if (leaves <= 16) return sddmm_cfg<T, I, 16, 1, ALIGNED, true>(a);
+  if (leaves <= 64) return sddmm_cfg<T, I, 64, 1, ALIGNED, true>(a);
+  return sddmm_cfg<T, I, 64, 4, ALIGNED, true>(a);
 }
 
-template <typename I>
-int sddmm_idx(int val_dtype, const SddmmArgs& a) {
-  switch (val_dtype) {
-    case OFX_DT_FLOAT: return sddmm_typed<float, I>(a);
-    case OFX_DT_DOUBLE: return sddmm_typed<double, I>(a);
-    case OFX_DT_BFLOAT16: return sddmm_typed<bf16, I>(a);
-    case OFX_DT_FLOAT16: return sddmm_typed<f16, I>(a);
-    default: return fail(OFX_EUNSUPPORTED, "sddmm_csr: unsupported value dtype %d", val_dtype);
-  }
+template <bool MASKED>
+int sddmm_launch(int idx_dtype, int val_dtype, const SddmmArgs& a) {
+  return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+    using T = std::remove_pointer_t<decltype(tp)>;
+    using I = std::remove_pointer_t<decltype(ip)>;
+    // the plain SDDMM also wants whole leaves per row (its rule from before the masked one)
+    const bool aligned = a.n % kLeaf == 0 && rows_aligned(a.dC, a.ldc, sizeof(T), kLeaf) &&
+                         rows_aligned(a.B, a.ldb, sizeof(T), kLeaf) &&
+                         rows_aligned(a.arg, a.ldarg, sizeof(I), kLeaf) &&
+                         (MASKED || (a.ldc % kLeaf == 0 && a.ldb % kLeaf == 0));
+    if constexpr (MASKED)
+      return aligned ? sddmm_select_width<T, I, true>(a) : sddmm_select_width<T, I, false>(a);
+    else
+      return aligned ? sddmm_width<T, I, true>(a) : sddmm_width<T, I, false>(a);
+  });
 }
 
 }  // namespace
@@ -550,10 +529,12 @@ extern "C" int ofx_csr_transpose_workspace_size(int idx_dtype, int64_t m, int64_
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_REQUIRE(bytes && m >= 0 && k >= 0 && nnz >= 0, OFX_EINVAL, "csr_transpose: bad arguments");
     OFX_REQUIRE(nnz <= INT32_MAX, OFX_EINVAL, "csr_transpose: nnz > 2^31-1 is not supported");
+    OFX_REQUIRE(is_index_dtype(idx_dtype), OFX_EUNSUPPORTED,
+                "csr_transpose: index dtype %d is not int32/int64", idx_dtype);
     size_t cub = 0;
-    if (idx_dtype == OFX_DT_INT32) return transpose_ws<int32_t>(nnz, k, bytes, &cub);
-    if (idx_dtype == OFX_DT_INT64) return transpose_ws<int64_t>(nnz, k, bytes, &cub);
-    return fail(OFX_EUNSUPPORTED, "csr_transpose: index dtype %d is not int32/int64", idx_dtype);
+    return by_index(idx_dtype, [&](auto* ip) -> int {
+      return transpose_ws<std::remove_pointer_t<decltype(ip)>>(nnz, k, bytes, &cub);
+    });
   });
 }
 
@@ -566,16 +547,14 @@ extern "C" int ofx_csr_transpose(void* stream, int idx_dtype, int64_t m, int64_t
                     (nnz == 0 || (col_idx && out_col_idx && out_perm)),
                 OFX_EINVAL, "csr_transpose: bad arguments");
     OFX_REQUIRE(nnz <= INT32_MAX, OFX_EINVAL, "csr_transpose: nnz > 2^31-1 is not supported");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (idx_dtype == OFX_DT_INT32)
-      return transpose<int32_t>(s, m, k, nnz, (const int32_t*)row_ptr, (const int32_t*)col_idx,
-                                (int32_t*)out_row_ptr, (int32_t*)out_col_idx, (int32_t*)out_perm,
-                                workspace, workspace_bytes);
-    if (idx_dtype == OFX_DT_INT64)
-      return transpose<int64_t>(s, m, k, nnz, (const int64_t*)row_ptr, (const int64_t*)col_idx,
-                                (int64_t*)out_row_ptr, (int64_t*)out_col_idx, (int64_t*)out_perm,
-                                workspace, workspace_bytes);
-    return fail(OFX_EUNSUPPORTED, "csr_transpose: index dtype %d is not int32/int64", idx_dtype);
+    OFX_REQUIRE(is_index_dtype(idx_dtype), OFX_EUNSUPPORTED,
+                "csr_transpose: index dtype %d is not int32/int64", idx_dtype);
+    return by_index(idx_dtype, [&](auto* ip) -> int {
+      using I = std::remove_pointer_t<decltype(ip)>;
+      return transpose<I>(static_cast<hipStream_t>(stream), m, k, nnz, (const I*)row_ptr,
+                          (const I*)col_idx, (I*)out_row_ptr, (I*)out_col_idx, (I*)out_perm,
+                          workspace, workspace_bytes);
+    });
   });
 }
 
@@ -584,33 +563,28 @@ extern "C" int ofx_gather_values(void* stream, int idx_dtype, int val_dtype, int
   return ::ofx::guarded(__func__, [&]() -> int {
     if (nnz == 0) return OFX_OK;
     OFX_REQUIRE(perm && src && dst, OFX_EINVAL, "gather_values: NULL pointer");
+    OFX_REQUIRE(is_value_dtype(val_dtype) || is_index_dtype(val_dtype), OFX_EUNSUPPORTED,
+                "gather_values: bad value dtype %d", val_dtype);
+    OFX_REQUIRE(is_index_dtype(idx_dtype), OFX_EUNSUPPORTED, "gather_values: bad index dtype %d",
+                idx_dtype);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned g = (unsigned)std::min<int64_t>((nnz + kBlock - 1) / kBlock, 65536);
-    auto go = [&](auto* ip) -> int {
-      using I = std::remove_const_t<std::remove_pointer_t<decltype(ip)>>;
-      switch (dtype_size(val_dtype)) {
-        case 2:
-          hipLaunchKernelGGL((gather_values_kernel<uint16_t, I>), dim3(g), dim3(kBlock), 0, s,
-                             (const I*)perm, (const uint16_t*)src, nnz, (uint16_t*)dst);
-          break;
-        case 4:
-          hipLaunchKernelGGL((gather_values_kernel<uint32_t, I>), dim3(g), dim3(kBlock), 0, s,
-                             (const I*)perm, (const uint32_t*)src, nnz, (uint32_t*)dst);
-          break;
-        case 8:
-          hipLaunchKernelGGL((gather_values_kernel<uint64_t, I>), dim3(g), dim3(kBlock), 0, s,
-                             (const I*)perm, (const uint64_t*)src, nnz, (uint64_t*)dst);
-          break;
-        default: return fail(OFX_EUNSUPPORTED, "gather_values: bad value dtype %d", val_dtype);
-      }
+    // values move as bits of their size: index dtypes are values here too
+    auto go = [&](auto* ip, auto* vp) -> int {
+      using I = std::remove_pointer_t<decltype(ip)>;
+      using V = std::remove_pointer_t<decltype(vp)>;
+      hipLaunchKernelGGL((gather_values_kernel<V, I>), dim3(g), dim3(kBlock), 0, s, (const I*)perm,
+                         (const V*)src, nnz, (V*)dst);
       OFX_HIP_CHECK(hipGetLastError());
       return OFX_OK;
     };
-    OFX_REQUIRE(is_value_dtype(val_dtype) || is_index_dtype(val_dtype), OFX_EUNSUPPORTED,
-                "gather_values: bad value dtype %d", val_dtype);
-    if (idx_dtype == OFX_DT_INT32) return go((const int32_t*)nullptr);
-    if (idx_dtype == OFX_DT_INT64) return go((const int64_t*)nullptr);
-    return fail(OFX_EUNSUPPORTED, "gather_values: bad index dtype %d", idx_dtype);
+    return by_index(idx_dtype, [&](auto* ip) -> int {
+      switch (dtype_size(val_dtype)) {
+        case 2: return go(ip, (uint16_t*)nullptr);
+        case 4: return go(ip, (uint32_t*)nullptr);
+        default: return go(ip, (uint64_t*)nullptr);
+      }
+    });
   });
 }
 
@@ -655,11 +629,37 @@ extern "C" int ofx_sddmm_csr_ex(void* stream, int idx_dtype, int val_dtype, int6
     OFX_REQUIRE(row_ptr && col_idx && out && (n == 0 || (a && b)), OFX_EINVAL,
                 "sddmm_csr: NULL pointer");
     if (n == 0) return fail(OFX_EINVAL, "sddmm_csr: n == 0 (use a zero fill)");
-    SddmmArgs args{static_cast<hipStream_t>(stream), row_ptr, col_idx, a, b, out, lda, ldb,
-                   row_begin, row_end - row_begin, n, nnz, k, workspace, workspace_bytes,
-                   opts->planned != 0};
-    if (idx_dtype == OFX_DT_INT32) return sddmm_idx<int32_t>(val_dtype, args);
-    return sddmm_idx<int64_t>(val_dtype, args);
+    const SddmmArgs args{"sddmm_csr", static_cast<hipStream_t>(stream), row_ptr, col_idx, nullptr,
+                         a, b, out, 0, lda, ldb, row_begin, row_end - row_begin, n, nnz, k,
+                         workspace, workspace_bytes, opts->planned != 0};
+    return sddmm_launch<false>(idx_dtype, val_dtype, args);
+  });
+}
+
+// The masked SDDMM: d(values) of the max / min reductions (op "spmm_csr_reduce").  It plans with
+// the plain SDDMM's work layout, so ofx_sddmm_csr_workspace_size serves it too.
+extern "C" int ofx_sddmm_csr_select(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                    int64_t n, int64_t nnz, const void* row_ptr,
+                                    const void* col_idx, const void* arg, int64_t ldarg,
+                                    const void* a, int64_t lda, const void* b, int64_t ldb,
+                                    void* out, int64_t row_begin, int64_t row_end, void* workspace,
+                                    size_t workspace_bytes) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_TAKE_DEVICE_ERROR("sddmm_csr_select");  // an earlier launch's loud failure (spmm_plan.h)
+    int rc = check_sddmm_select_args("sddmm_csr_select", idx_dtype, val_dtype, m, k, n, nnz, ldarg,
+                                     lda, ldb, row_begin, row_end);
+    if (rc) return rc;
+    if (row_end == row_begin || nnz == 0) return OFX_OK;
+    OFX_REQUIRE(n <= kMaxNarrowN, OFX_EUNSUPPORTED,
+                "sddmm_csr_select: n=%lld > %lld is not supported", (long long)n,
+                (long long)kMaxNarrowN);
+    OFX_REQUIRE(arg != nullptr, OFX_EINVAL,
+                "sddmm_csr_select: arg is NULL (the gradient of max / min needs it)");
+    OFX_REQUIRE(row_ptr && col_idx && out && a && b, OFX_EINVAL, "sddmm_csr_select: NULL pointer");
+    const SddmmArgs args{"sddmm_csr_select", static_cast<hipStream_t>(stream), row_ptr, col_idx,
+                         arg, a, b, out, ldarg, lda, ldb, row_begin, row_end - row_begin, n, nnz,
+                         k, workspace, workspace_bytes, false};
+    return sddmm_launch<true>(idx_dtype, val_dtype, args);
   });
 }
 
@@ -676,18 +676,14 @@ extern "C" int ofx_sddmm_csr_plan(void* stream, int idx_dtype, int val_dtype, in
                     row_end <= m, OFX_EINVAL, "sddmm_csr_plan: bad sizes or row range");
     const int64_t nrows = row_end - row_begin;
     if (nrows == 0 || nnz == 0 || n == 0) return OFX_OK;  // the launch plans nothing either
-    const Schedule sched = sddmm_schedule(n);
-    const plan::WsLayout w = plan::ws_layout(nrows, nnz, 0, 0, sched);
-    if (w.total == 0) return OFX_OK;
+    if (plan::ws_layout(nrows, nnz, 0, 0, sddmm_schedule(n)).total == 0) return OFX_OK;
     OFX_REQUIRE(row_ptr != nullptr, OFX_EINVAL, "sddmm_csr_plan: NULL row_ptr");
-    OFX_REQUIRE(workspace != nullptr && workspace_bytes >= w.total, OFX_EWORKSPACE,
-                "sddmm_csr_plan: workspace of %zu bytes < %zu required", workspace_bytes, w.total);
-    plan::WorkList wl{};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (idx_dtype == OFX_DT_INT32)
-      return plan::launch_plan<int32_t>(s, static_cast<const int32_t*>(row_ptr), row_begin, nrows,
-                                        nnz, sched, w, static_cast<char*>(workspace), &wl);
-    return plan::launch_plan<int64_t>(s, static_cast<const int64_t*>(row_ptr), row_begin, nrows,
-                                      nnz, sched, w, static_cast<char*>(workspace), &wl);
+    return by_index(idx_dtype, [&](auto* ip) -> int {
+      using I = std::remove_pointer_t<decltype(ip)>;
+      Planned p;
+      return prepare_plan<I>("sddmm_csr_plan", static_cast<hipStream_t>(stream),
+                             static_cast<const I*>(row_ptr), row_begin, nrows, nnz, nnz, 0, 0,
+                             sddmm_schedule(n), false, workspace, workspace_bytes, &p);
+    });
   });
 }

@@ -1,5 +1,6 @@
 // spmm_common.h — numeric contract shared by the HIP kernels (spmm_csr.hip) and the CPU kernel
-// (spmm_cpu.cpp): storage types, conversions, schedule (split) resolution, counter-based RNG.
+// (spmm_cpu.cpp): storage types, conversions, dtype dispatch, schedule (split) resolution,
+// counter-based RNG.
 //
 // The accumulation contract restates the reference composition gather -> multiply ->
 // unsorted_segment_sum (oneflow/user/kernels/gather_kernel_util.cpp:72-92,
@@ -144,6 +145,26 @@ OFX_HD bool is_index_dtype(int dt) { return dt == OFX_DT_INT32 || dt == OFX_DT_I
 OFX_HD bool is_value_dtype(int dt) {
   return dt == OFX_DT_FLOAT || dt == OFX_DT_DOUBLE || dt == OFX_DT_FLOAT16 ||
          dt == OFX_DT_BFLOAT16;
+}
+
+// Dtype dispatch of the C-ABI entries (host code): by_index calls f(I*), by_types f(T*, I*), with
+// null pointers of the index / value types the dtype codes name.  An unknown code falls through
+// to int64 / f16, so an entry checks is_index_dtype / is_value_dtype before it dispatches.
+template <typename F>
+int by_index(int idx_dtype, F&& f) {
+  if (idx_dtype == OFX_DT_INT32) return f((int32_t*)nullptr);
+  return f((int64_t*)nullptr);
+}
+template <typename F>
+int by_types(int idx_dtype, int val_dtype, F&& f) {
+  return by_index(idx_dtype, [&](auto* ip) -> int {
+    switch (val_dtype) {
+      case OFX_DT_FLOAT: return f((float*)nullptr, ip);
+      case OFX_DT_DOUBLE: return f((double*)nullptr, ip);
+      case OFX_DT_BFLOAT16: return f((bf16*)nullptr, ip);
+      default: return f((f16*)nullptr, ip);
+    }
+  });
 }
 
 // ---- schedule ---------------------------------------------------------------------------

@@ -15,6 +15,7 @@
 
 #include "ofx_internal.h"
 #include "spmm_common.h"
+#include "spmm_extremum.h"
 
 namespace ofx {
 namespace {
@@ -228,9 +229,13 @@ void cpu_transpose(int64_t m, int64_t k, int64_t nnz, const I* rp, const I* col,
     }
 }
 
-template <typename T, typename I>
-void cpu_sddmm(int nthreads, int64_t k, int64_t n, const I* rp, const I* col, const T* a,
-               int64_t lda, const T* b, int64_t ldb, T* out, int64_t row_begin, int64_t row_end) {
+// The SDDMM in its order contract (csrc/spmm_backward.hip).  MASKED: d(values) of max / min, the
+// terms of the columns nonzero j did not win (arg[r, c] != j) replaced by +0.  A column outside
+// [0, k) reads the gathered zero row as the factor A(0).
+template <typename T, typename I, bool MASKED>
+void cpu_sddmm(int nthreads, int64_t k, int64_t n, const I* rp, const I* col, const I* arg,
+               int64_t ldarg, const T* a, int64_t lda, const T* b, int64_t ldb, T* out,
+               int64_t row_begin, int64_t row_end) {
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
   const int64_t leaves = (n + 7) / 8;
@@ -239,17 +244,20 @@ void cpu_sddmm(int nthreads, int64_t k, int64_t n, const I* rp, const I* col, co
 #pragma omp parallel num_threads(nthreads)
   {
     std::vector<A> leaf(padded);
-    const std::vector<T> zero(n, Num<T>::store(A(0)));  // the zero-filled row of a column outside [0, k)
 #pragma omp for schedule(dynamic, 64)
     for (int64_t r = row_begin; r < row_end; ++r) {
       const T* arow = a + (r - row_begin) * lda;
+      const I* grow = MASKED ? arg + (r - row_begin) * ldarg : nullptr;
       for (int64_t j = (int64_t)rp[r]; j < (int64_t)rp[r + 1]; ++j) {
         const int64_t cj = (int64_t)col[j];
-        const T* brow = (uint64_t)cj < (uint64_t)k ? b + cj * ldb : zero.data();
+        const T* brow = (uint64_t)cj < (uint64_t)k ? b + cj * ldb : nullptr;
         for (int64_t l = 0; l < padded; ++l) {
           A s = A(0);
-          for (int64_t e = 8 * l; e < 8 * l + 8 && e < n; ++e)
-            s = s + Num<T>::load(arow[e]) * Num<T>::load(brow[e]);
+          for (int64_t e = 8 * l; e < 8 * l + 8 && e < n; ++e) {
+            A term = Num<T>::load(arow[e]) * (brow ? Num<T>::load(brow[e]) : A(0));
+            if constexpr (MASKED) term = (int64_t)grow[e] == j ? term : A(0);
+            s = s + term;
+          }
           leaf[l] = s;
         }
         for (int64_t w = 1; w < padded; w *= 2)
@@ -308,6 +316,26 @@ int64_t row_ptr_at(int idx_dtype, const void* row_ptr, int64_t r) {
   return idx_dtype == OFX_DT_INT32 ? (int64_t) static_cast<const int32_t*>(row_ptr)[r]
                                    : (int64_t) static_cast<const int64_t*>(row_ptr)[r];
 }
+
+// Either SDDMM over rows [row_begin, row_end), its arguments checked by the entry.
+template <bool MASKED>
+int run_sddmm(const char* fn, int num_threads, int idx_dtype, int val_dtype, int64_t k, int64_t n,
+              const void* row_ptr, const void* col_idx, const void* arg, int64_t ldarg,
+              const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t row_begin,
+              int64_t row_end) {
+  OFX_REQUIRE(!negative_column(idx_dtype, col_idx, row_ptr_at(idx_dtype, row_ptr, row_begin),
+                               row_ptr_at(idx_dtype, row_ptr, row_end)),
+              OFX_EINVAL, "%s: negative column index (gather_kernel_util.cpp:80 CHECK_GE(idx, 0))",
+              fn);
+  const int nt = num_threads > 0 ? num_threads : omp_get_max_threads();
+  return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+    using T = std::remove_pointer_t<decltype(tp)>;
+    using I = std::remove_pointer_t<decltype(ip)>;
+    cpu_sddmm<T, I, MASKED>(nt, k, n, (const I*)row_ptr, (const I*)col_idx, (const I*)arg, ldarg,
+                            (const T*)a, lda, (const T*)b, ldb, (T*)out, row_begin, row_end);
+    return OFX_OK;
+  });
+}
 }  // namespace
 }  // namespace ofx
 
@@ -322,15 +350,12 @@ extern "C" int ofx_csr_transpose_cpu(int idx_dtype, int64_t m, int64_t k, int64_
                 idx_dtype);
     OFX_REQUIRE(nnz == 0 || !negative_column(idx_dtype, col_idx, 0, nnz), OFX_EINVAL,
                 "csr_transpose_cpu: negative column index (gather_kernel_util.cpp:80 CHECK_GE(idx, 0))");
-    if (idx_dtype == OFX_DT_INT32)
-      cpu_transpose<int32_t>(m, k, nnz, (const int32_t*)row_ptr, (const int32_t*)col_idx,
-                             (int32_t*)out_row_ptr, (int32_t*)out_col_idx, (int32_t*)out_perm);
-    else if (idx_dtype == OFX_DT_INT64)
-      cpu_transpose<int64_t>(m, k, nnz, (const int64_t*)row_ptr, (const int64_t*)col_idx,
-                             (int64_t*)out_row_ptr, (int64_t*)out_col_idx, (int64_t*)out_perm);
-    else
-      return fail(OFX_EUNSUPPORTED, "csr_transpose_cpu: bad index dtype %d", idx_dtype);
-    return OFX_OK;
+    return by_index(idx_dtype, [&](auto* ip) -> int {
+      using I = std::remove_pointer_t<decltype(ip)>;
+      cpu_transpose<I>(m, k, nnz, (const I*)row_ptr, (const I*)col_idx, (I*)out_row_ptr,
+                       (I*)out_col_idx, (I*)out_perm);
+      return OFX_OK;
+    });
   });
 }
 
@@ -345,33 +370,29 @@ extern "C" int ofx_sddmm_csr_cpu(int num_threads, int idx_dtype, int val_dtype, 
                     row_begin <= row_end && row_end <= m,
                 OFX_EINVAL, "sddmm_csr_cpu: bad sizes");
     if (row_end == row_begin || nnz == 0) return OFX_OK;
-    OFX_REQUIRE(!negative_column(idx_dtype, col_idx, row_ptr_at(idx_dtype, row_ptr, row_begin),
-                                 row_ptr_at(idx_dtype, row_ptr, row_end)),
-                OFX_EINVAL,
-                "sddmm_csr_cpu: negative column index (gather_kernel_util.cpp:80 CHECK_GE(idx, 0))");
-    const int nt = num_threads > 0 ? num_threads : omp_get_max_threads();
-    auto run = [&](auto* ip) {
-      using I = std::remove_const_t<std::remove_pointer_t<decltype(ip)>>;
-      const I* rp = (const I*)row_ptr;
-      const I* ci = (const I*)col_idx;
-      switch (val_dtype) {
-        case OFX_DT_FLOAT:
-          cpu_sddmm<float, I>(nt, k, n, rp, ci, (const float*)a, lda, (const float*)b, ldb, (float*)out, row_begin, row_end);
-          break;
-        case OFX_DT_DOUBLE:
-          cpu_sddmm<double, I>(nt, k, n, rp, ci, (const double*)a, lda, (const double*)b, ldb, (double*)out, row_begin, row_end);
-          break;
-        case OFX_DT_BFLOAT16:
-          cpu_sddmm<bf16, I>(nt, k, n, rp, ci, (const bf16*)a, lda, (const bf16*)b, ldb, (bf16*)out, row_begin, row_end);
-          break;
-        default:
-          cpu_sddmm<f16, I>(nt, k, n, rp, ci, (const f16*)a, lda, (const f16*)b, ldb, (f16*)out, row_begin, row_end);
-          break;
-      }
-    };
-    if (idx_dtype == OFX_DT_INT32) run((const int32_t*)nullptr);
-    else run((const int64_t*)nullptr);
-    return OFX_OK;
+    return run_sddmm<false>("sddmm_csr_cpu", num_threads, idx_dtype, val_dtype, k, n, row_ptr,
+                            col_idx, nullptr, 0, a, lda, b, ldb, out, row_begin, row_end);
+  });
+}
+
+// d(values) of the max / min reductions: the masked SDDMM (csrc/spmm_extremum_cpu.cpp has the
+// other kCPU kernels of op "spmm_csr_reduce").
+extern "C" int ofx_sddmm_csr_select_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                        int64_t k, int64_t n, int64_t nnz, const void* row_ptr,
+                                        const void* col_idx, const void* arg, int64_t ldarg,
+                                        const void* a, int64_t lda, const void* b, int64_t ldb,
+                                        void* out, int64_t row_begin, int64_t row_end) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    int rc = check_sddmm_select_args("sddmm_csr_select_cpu", idx_dtype, val_dtype, m, k, n, nnz,
+                                     ldarg, lda, ldb, row_begin, row_end);
+    if (rc) return rc;
+    if (row_end == row_begin || nnz == 0) return OFX_OK;
+    OFX_REQUIRE(arg != nullptr, OFX_EINVAL,
+                "sddmm_csr_select_cpu: arg is NULL (the gradient of max / min needs it)");
+    OFX_REQUIRE(row_ptr && col_idx && out && a && b, OFX_EINVAL,
+                "sddmm_csr_select_cpu: NULL pointer");
+    return run_sddmm<true>("sddmm_csr_select_cpu", num_threads, idx_dtype, val_dtype, k, n, row_ptr,
+                           col_idx, arg, ldarg, a, lda, b, ldb, out, row_begin, row_end);
   });
 }
 

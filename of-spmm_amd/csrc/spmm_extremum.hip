@@ -18,35 +18,13 @@
 
 #include <hip/hip_runtime.h>
 
-#include <climits>
-
-#include "spmm_extremum_dev.h"
+#include "spmm_extremum.h"
+#include "spmm_items_dev.h"
 
 namespace ofx {
 namespace {
 
-using namespace xt;
-
-// No valid plan: the whole output is the canonical NaN and arg -1 (the loud-failure contract of
-// the work list's consumers, spmm_plan.h); the host reports the error word at its next entry.
-template <typename T, typename I>
-__device__ __forceinline__ bool extremum_plan_invalid(
-    const unsigned long long* __restrict__ counters, int64_t block_base, unsigned* err,
-    T* __restrict__ out, int64_t ldc, I* __restrict__ arg, int64_t ldarg, int64_t nrows,
-    int64_t n) {
-  if (counters == nullptr || plan::plan_valid(counters)) return false;
-  if (block_base + blockIdx.x == 0 && threadIdx.x == 0)
-    plan::raise_device_error(err, plan::kErrPlanInvalid);
-  const T p = poison_value<T>();
-  const int64_t total = nrows * n;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t r = i / n, c = i - r * n;
-    out[r * ldc + c] = p;
-    if (arg != nullptr) arg[r * ldarg + c] = I(-1);
-  }
-  return true;
-}
+using namespace item;
 
 template <typename T, typename I, int VEC, int LPR, int U, bool ALIGNED>
 __global__ void __launch_bounds__(kBlock)
@@ -61,7 +39,7 @@ __global__ void __launch_bounds__(kBlock)
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
   constexpr int GPW = 64 / LPR;
-  if (extremum_plan_invalid(counters, block_base, err, out, ldc, arg, ldarg, nrows, n)) return;
+  if (poison_rows(counters, block_base, err, out, ldc, arg, ldarg, nrows, n)) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int gl = lane & (LPR - 1);
@@ -204,19 +182,15 @@ int extremum_cfg(const ExtArgs& a) {
   // partials: the int64 args first (8-byte aligned at the region's start), then the winners
   int64_t* part_arg = static_cast<int64_t*>(p.wl.part);
   A* part_best = p.has_plan ? reinterpret_cast<A*>(part_arg + p.w.max_chunks * a.n) : nullptr;
-  const int64_t work = a.nrows + (p.has_plan ? p.w.max_chunks : 0);
-  const int64_t grid = (work + GPB - 1) / GPB;
-  unsigned* err = p.has_plan ? device_error_words() : nullptr;
-  for (int64_t b0 = 0; b0 < grid; b0 += kLaunchBlocks) {  // < 2^31 threads per launch
-    hipLaunchKernelGGL((extremum_kernel<T, I, VEC, LPR, U, ALIGNED>),
-                       dim3((unsigned)std::min(kLaunchBlocks, grid - b0)), dim3(kBlock), 0, a.s,
+  rc = launch_cut_grid(p.work, GPB, [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL((extremum_kernel<T, I, VEC, LPR, U, ALIGNED>), grid, dim3(kBlock), 0, a.s,
                        static_cast<const I*>(a.rp), static_cast<const I*>(a.col),
                        static_cast<const T*>(a.val), static_cast<const T*>(a.b), a.ldb, a.k,
                        static_cast<T*>(a.c), a.ldc, static_cast<I*>(a.arg), a.ldarg, a.row_begin,
-                       a.nrows, a.n, p.has_plan ? p.sched.chunk : INT64_MAX, a.is_max ? 1 : 0,
-                       p.wl.counters, p.wl.items, p.wl.order, part_best, part_arg, b0, err);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
+                       a.nrows, a.n, p.chunk, a.is_max ? 1 : 0, p.wl.counters, p.wl.items,
+                       p.wl.order, part_best, part_arg, b0, p.err);
+  });
+  if (rc) return rc;
   if (p.has_plan && p.w.max_hubs > 0) {
     const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
     hipLaunchKernelGGL((extremum_hub_kernel<T, I>), dim3(hgrid), dim3(kBlock), 0, a.s,
@@ -265,8 +239,8 @@ extern "C" int ofx_spmm_csr_reduce_workspace_size(int idx_dtype, int val_dtype, 
     OFX_READ_OPTIONS(opts, "spmm_csr_reduce_workspace_size");
     rc = check_types_sizes("spmm_csr_reduce_workspace_size", idx_dtype, val_dtype, m, k, n, nnz);
     if (rc) return rc;
-    *bytes = xt::workspace_bytes(m, nnz, n, (val_dtype == OFX_DT_DOUBLE ? 8 : 4) + sizeof(int64_t),
-                             opts);
+    *bytes = item::workspace_bytes(m, nnz, n,
+                                   (val_dtype == OFX_DT_DOUBLE ? 8 : 4) + sizeof(int64_t), opts);
     return OFX_OK;
   });
 }
@@ -301,7 +275,7 @@ extern "C" int ofx_spmm_csr_reduce(void* stream, int idx_dtype, int val_dtype, i
     const ExtArgs a{static_cast<hipStream_t>(stream), row_ptr, col_idx, values, b, c, arg, ldb,
                     ldc, ldarg, m, row_begin, nrows, n, nnz, k, reduce == OFX_REDUCE_MAX,
                     workspace, workspace_bytes, opts};
-    return xt::by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
       return extremum_typed<std::remove_pointer_t<decltype(tp)>,
                             std::remove_pointer_t<decltype(ip)>>(a);
     });
@@ -321,11 +295,11 @@ extern "C" int ofx_row_scale_by_degree(void* stream, int idx_dtype, int val_dtyp
     OFX_REQUIRE(row_ptr && src && dst, OFX_EINVAL, "row_scale_by_degree: NULL pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t total = nrows * n;
-    const unsigned grid = (unsigned)std::min<int64_t>((total + xt::kBlock - 1) / xt::kBlock, 1 << 20);
-    return xt::by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+    const unsigned grid = (unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, 1 << 20);
+    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
       using T = std::remove_pointer_t<decltype(tp)>;
       using I = std::remove_pointer_t<decltype(ip)>;
-      hipLaunchKernelGGL((row_scale_kernel<T, I>), dim3(grid), dim3(xt::kBlock), 0, s,
+      hipLaunchKernelGGL((row_scale_kernel<T, I>), dim3(grid), dim3(kBlock), 0, s,
                          static_cast<const I*>(row_ptr), static_cast<const T*>(src), ldsrc,
                          static_cast<T*>(dst), lddst, row_begin, nrows, n);
       OFX_HIP_CHECK(hipGetLastError());

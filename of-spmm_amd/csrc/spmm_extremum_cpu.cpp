@@ -1,7 +1,8 @@
 // spmm_extremum_cpu.cpp — the DeviceType::kCPU kernels of the max / min / mean reductions of
 // op "spmm_csr_reduce" and of their gradients (contracts in include/ofx_spmm.h, shared helpers in
 // spmm_extremum.h).  Row-parallel over OpenMP like spmm_cpu.cpp; the same bits as the HIP kernels
-// (spmm_extremum.hip, spmm_extremum_grad.hip, spmm_extremum_sddmm.hip).
+// (spmm_extremum.hip, spmm_extremum_grad.hip).  d(values), the masked SDDMM, is beside the plain
+// SDDMM in spmm_cpu.cpp.
 #pragma clang fp contract(off)
 
 #include <omp.h>
@@ -116,45 +117,6 @@ void cpu_select(int nthreads, int64_t m, int64_t nnz, int64_t n, const I* rp_t, 
   }
 }
 
-// d(values) of max / min: ofx_sddmm_csr's order with the terms of the columns the nonzero did not
-// win replaced by +0.
-template <typename T, typename I>
-void cpu_sddmm_select(int nthreads, int64_t k, int64_t n, const I* rp, const I* col, const I* arg,
-                      int64_t ldarg, const T* a, int64_t lda, const T* b, int64_t ldb, T* out,
-                      int64_t row_begin, int64_t row_end) {
-#pragma clang fp contract(off)
-  using A = typename Num<T>::acc;
-  const int64_t leaves = (n + 7) / 8;
-  int64_t padded = 1;
-  while (padded < leaves) padded *= 2;
-#pragma omp parallel num_threads(nthreads)
-  {
-    std::vector<A> leaf(padded);
-#pragma omp for schedule(dynamic, 64)
-    for (int64_t r = row_begin; r < row_end; ++r) {
-      const T* arow = a + (r - row_begin) * lda;
-      const I* grow = arg + (r - row_begin) * ldarg;
-      for (int64_t j = (int64_t)rp[r]; j < (int64_t)rp[r + 1]; ++j) {
-        const int64_t cj = (int64_t)col[j];
-        const T* brow = (uint64_t)cj < (uint64_t)k ? b + cj * ldb : nullptr;
-        for (int64_t l = 0; l < padded; ++l) {
-          A s = A(0);
-          for (int64_t e = 8 * l; e < 8 * l + 8 && e < n; ++e) {
-            const A term = (int64_t)grow[e] == j
-                               ? Num<T>::load(arow[e]) * (brow ? Num<T>::load(brow[e]) : A(0))
-                               : A(0);
-            s = s + term;
-          }
-          leaf[l] = s;
-        }
-        for (int64_t w = 1; w < padded; w *= 2)
-          for (int64_t l = 0; l < padded; l += 2 * w) leaf[l] = leaf[l] + leaf[l + w];
-        out[j] = Num<T>::store(leaf[0]);
-      }
-    }
-  }
-}
-
 template <typename T, typename I>
 void cpu_row_scale(int nthreads, int64_t n, const I* rp, const T* src, int64_t ldsrc, T* dst,
                    int64_t lddst, int64_t row_begin, int64_t row_end) {
@@ -166,21 +128,6 @@ void cpu_row_scale(int nthreads, int64_t n, const I* rp, const T* src, int64_t l
     T* d = dst + (r - row_begin) * lddst;
     for (int64_t c = 0; c < n; ++c) d[c] = scale_by_degree<T>(s[c], deg);
   }
-}
-
-// Calls f(T*, I*) with null pointers of the value / index types the dtype codes name.
-template <typename F>
-int by_types(int idx_dtype, int val_dtype, F&& f) {
-  auto with_i = [&](auto* ip) -> int {
-    switch (val_dtype) {
-      case OFX_DT_FLOAT: return f((float*)nullptr, ip);
-      case OFX_DT_DOUBLE: return f((double*)nullptr, ip);
-      case OFX_DT_BFLOAT16: return f((bf16*)nullptr, ip);
-      default: return f((f16*)nullptr, ip);
-    }
-  };
-  if (idx_dtype == OFX_DT_INT32) return with_i((int32_t*)nullptr);
-  return with_i((int64_t*)nullptr);
 }
 
 int threads_of(int num_threads) { return num_threads > 0 ? num_threads : omp_get_max_threads(); }
@@ -247,37 +194,6 @@ extern "C" int ofx_spmm_csr_select_cpu(int num_threads, int idx_dtype, int val_d
       cpu_select<T, I>(threads_of(num_threads), m, nnz, n, (const I*)row_ptr_t,
                        (const I*)col_idx_t, (const I*)perm, (const T*)values, (const I*)arg, ldarg,
                        (const T*)g, ldg, (T*)db, lddb, row_begin, row_end, s);
-      return OFX_OK;
-    });
-  });
-}
-
-extern "C" int ofx_sddmm_csr_select_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
-                                        int64_t k, int64_t n, int64_t nnz, const void* row_ptr,
-                                        const void* col_idx, const void* arg, int64_t ldarg,
-                                        const void* a, int64_t lda, const void* b, int64_t ldb,
-                                        void* out, int64_t row_begin, int64_t row_end) {
-  return ::ofx::guarded(__func__, [&]() -> int {
-    int rc = check_sddmm_select_args("sddmm_csr_select_cpu", idx_dtype, val_dtype, m, k, n, nnz,
-                                     ldarg, lda, ldb, row_begin, row_end);
-    if (rc) return rc;
-    if (row_end == row_begin || nnz == 0) return OFX_OK;
-    OFX_REQUIRE(arg != nullptr, OFX_EINVAL,
-                "sddmm_csr_select_cpu: arg is NULL (the gradient of max / min needs it)");
-    OFX_REQUIRE(row_ptr && col_idx && out && a && b, OFX_EINVAL,
-                "sddmm_csr_select_cpu: NULL pointer");
-    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
-      using T = std::remove_pointer_t<decltype(tp)>;
-      using I = std::remove_pointer_t<decltype(ip)>;
-      const I* rp = (const I*)row_ptr;
-      const I* ci = (const I*)col_idx;
-      bool neg = false;
-      for (int64_t j = (int64_t)rp[row_begin]; j < (int64_t)rp[row_end]; ++j) neg |= ci[j] < 0;
-      OFX_REQUIRE(!neg, OFX_EINVAL,
-                  "sddmm_csr_select_cpu: negative column index (gather_kernel_util.cpp:80 "
-                  "CHECK_GE(idx, 0))");
-      cpu_sddmm_select<T, I>(threads_of(num_threads), k, n, rp, ci, (const I*)arg, ldarg,
-                             (const T*)a, lda, (const T*)b, ldb, (T*)out, row_begin, row_end);
       return OFX_OK;
     });
   });

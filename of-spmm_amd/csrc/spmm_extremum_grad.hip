@@ -18,32 +18,13 @@
 
 #include <hip/hip_runtime.h>
 
-#include <climits>
-
-#include "spmm_extremum_dev.h"
+#include "spmm_extremum.h"
+#include "spmm_items_dev.h"
 
 namespace ofx {
 namespace {
 
-using namespace xt;
-
-template <typename T, typename I>
-__device__ __forceinline__ bool select_plan_invalid(const unsigned long long* __restrict__ counters,
-                                                    int64_t block_base, unsigned* err,
-                                                    T* __restrict__ db, int64_t lddb, int64_t nrows,
-                                                    int64_t n) {
-  if (counters == nullptr || plan::plan_valid(counters)) return false;
-  if (block_base + blockIdx.x == 0 && threadIdx.x == 0)
-    plan::raise_device_error(err, plan::kErrPlanInvalid);
-  const T p = poison_value<T>();
-  const int64_t total = nrows * n;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t r = i / n;
-    db[r * lddb + (i - r * n)] = p;
-  }
-  return true;
-}
+using namespace item;
 
 template <typename T, typename I, int VEC, int LPR, int U, bool ALIGNED>
 __global__ void __launch_bounds__(kBlock)
@@ -58,7 +39,7 @@ __global__ void __launch_bounds__(kBlock)
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
   constexpr int GPW = 64 / LPR;
-  if (select_plan_invalid<T, I>(counters, block_base, err, db, lddb, nrows, n)) return;
+  if (poison_rows(counters, block_base, err, db, lddb, (I*)nullptr, 0, nrows, n)) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int gl = lane & (LPR - 1);
@@ -167,20 +148,15 @@ int select_cfg(const SelArgs& a) {
                            a.nrows, a.nnz, a.n, sizeof(A), a.opts, a.ws, a.ws_bytes, &p);
   if (rc) return rc;
   A* part = static_cast<A*>(p.wl.part);
-  const int64_t work = a.nrows + (p.has_plan ? p.w.max_chunks : 0);
-  const int64_t grid = (work + GPB - 1) / GPB;
-  unsigned* err = p.has_plan ? device_error_words() : nullptr;
-  for (int64_t b0 = 0; b0 < grid; b0 += kLaunchBlocks) {  // < 2^31 threads per launch
-    hipLaunchKernelGGL((select_kernel<T, I, VEC, LPR, U, ALIGNED>),
-                       dim3((unsigned)std::min(kLaunchBlocks, grid - b0)), dim3(kBlock), 0, a.s,
+  rc = launch_cut_grid(p.work, GPB, [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL((select_kernel<T, I, VEC, LPR, U, ALIGNED>), grid, dim3(kBlock), 0, a.s,
                        static_cast<const I*>(a.rp_t), static_cast<const I*>(a.col_t),
                        static_cast<const I*>(a.perm), static_cast<const T*>(a.val),
                        static_cast<const I*>(a.arg), a.ldarg, static_cast<const T*>(a.g), a.ldg,
                        a.m, a.nnz, static_cast<T*>(a.db), a.lddb, a.row_begin, a.nrows, a.n,
-                       p.has_plan ? p.sched.chunk : INT64_MAX, p.wl.counters, p.wl.items,
-                       p.wl.order, part, b0, err);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
+                       p.chunk, p.wl.counters, p.wl.items, p.wl.order, part, b0, p.err);
+  });
+  if (rc) return rc;
   if (p.has_plan && p.w.max_hubs > 0) {
     const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
     hipLaunchKernelGGL((select_hub_kernel<T>), dim3(hgrid), dim3(kBlock), 0, a.s, p.wl.counters,
@@ -222,7 +198,7 @@ extern "C" int ofx_spmm_csr_select_workspace_size(int idx_dtype, int val_dtype, 
     OFX_READ_OPTIONS(opts, "spmm_csr_select_workspace_size");
     int rc = check_types_sizes("spmm_csr_select_workspace_size", idx_dtype, val_dtype, m, k, n, nnz);
     if (rc) return rc;
-    *bytes = xt::workspace_bytes(k, nnz, n, val_dtype == OFX_DT_DOUBLE ? 8 : 4, opts);
+    *bytes = item::workspace_bytes(k, nnz, n, val_dtype == OFX_DT_DOUBLE ? 8 : 4, opts);
     return OFX_OK;
   });
 }
@@ -250,7 +226,7 @@ extern "C" int ofx_spmm_csr_select(void* stream, int idx_dtype, int val_dtype, i
     const SelArgs a{static_cast<hipStream_t>(stream), row_ptr_t, col_idx_t, perm, values, arg, g,
                     db, ldarg, ldg, lddb, m, k, row_begin, nrows, n, nnz, workspace,
                     workspace_bytes, opts};
-    return xt::by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
       return select_typed<std::remove_pointer_t<decltype(tp)>,
                           std::remove_pointer_t<decltype(ip)>>(a);
     });
