@@ -402,6 +402,74 @@ int ofx_row_scale_by_degree_cpu(int num_threads, int idx_dtype, int val_dtype, i
                                 const void* row_ptr, const void* src, int64_t ldsrc, void* dst,
                                 int64_t lddst, int64_t row_begin, int64_t row_end);
 
+/* ---- edge softmax over CSR rows (op "edge_softmax_csr") -----------------------
+ * y = edge_softmax(row_ptr, e): the scores e T[nnz] (one per nonzero, e.g. ofx_sddmm_csr's output)
+ * normalised over each row of the CSR, DGL's edge_softmax / PyG's softmax(src, ptr=row_ptr): the
+ * step between sddmm and spmm of a dot-product attention layer.  One launch, no atomics, no
+ * row-id vector.  Numeric contract, identical in the kCPU kernels and the HIP kernels (every
+ * operation rounded separately, nothing contracted to FMA, a = the accumulation type: f32 for
+ * f32 / f16 / bf16, f64 for f64; each output element rounded to T once).  For row r with the
+ * nonzeros j in [row_ptr[r], row_ptr[r+1]):
+ *
+ *   m_r = max_j load(e_j), found with the max rule of ofx_spmm_csr_reduce walking j upwards from
+ *     the row's first element: a NaN score wins and propagates.  (Which of a tied +0 and -0 wins
+ *     cannot change a bit of y, so a kernel may combine partial maxima in any order.)
+ *   t_j = load(e_j) - m_r, one subtraction in a (never positive).
+ *   x_j = exp_acc(t_j) (csrc/edge_softmax.h): exp from IEEE-exact steps only, no library or
+ *     hardware transcendental, so host and device agree bit for bit.
+ *       f32: k = rint(t * log2e) (ties to even); r = (t - k*C1) - k*C2 with C1 = 0.693359375,
+ *         C2 = -2.12194440e-4; p = the Cephes expf degree-5 polynomial in r, Horner;
+ *         x = (((p * (r*r)) + r) + 1) * 2^k, 2^k assembled from exponent bits.  t < -87 (-inf
+ *         included) gives +0, so no result is subnormal.  Maximum error 0.98 ulp (exhaustive).
+ *       f64: the same reduction (C1 = 0.693145751953125, C2 = 1.42860682030941723212e-6) and the
+ *         Cephes exp rational form x = (1 + 2 * (r P(r^2) / (Q(r^2) - r P(r^2)))) * 2^k, one IEEE
+ *         division; t < -708 gives +0.  Maximum error 1.7 ulp measured on 10^7 points.
+ *       exp_acc(+-0) == 1 exactly; NaN gives the canonical quiet NaN.
+ *   s_r = sum_j x_j in the SDDMM's order applied along the row: leaf i is the sequential sum from
+ *     +0 of the row's positions [8i, 8i+8) (positions past the row's end are absent); the leaves,
+ *     zero-padded to a power of two, are added pairwise level by level.  A pure function of the
+ *     row: lane grouping, tiling, row range and the schedule options have NO numeric effect.
+ *     s_r >= 1 (the maximum's own term is exactly 1).
+ *   y_j = store(x_j / s_r), one IEEE division in a.  A NaN is stored as the canonical quiet NaN.
+ *
+ *   Special cases: a row that holds a NaN, or whose maximum is +inf, or whose scores are all -inf
+ *   (-inf - -inf is NaN), is the canonical NaN in every element; a -inf score in an otherwise
+ *   finite row gives +0; an empty row writes nothing.
+ *
+ * Gradient for upstream g = d(y) (ofx_edge_softmax_csr_grad), from the STORED y (nothing is
+ * recomputed):
+ *   q_j = load(y_j) * load(g_j), rounded to a;  d_r = sum_j q_j in the same leaf / tree order;
+ *   de_j = store(load(y_j) * (load(g_j) - d_r)): one subtraction and one multiply in a, then the
+ *   rounding to T as a separate step.  A NaN is stored as the canonical quiet NaN.
+ *
+ * Row range: [row_begin, row_end) writes exactly out[row_ptr[row_begin] .. row_ptr[row_end]),
+ * global positions, as ofx_sddmm_csr does.  opts: validated; no option has an effect (the kernels
+ * read no work plan, so `planned` is ignored and no workspace is needed).                       */
+/* Bytes of device workspace ofx_edge_softmax_csr / _grad need (0 today; query it all the same). */
+int ofx_edge_softmax_csr_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t nnz,
+                                        const ofx_spmm_options* opts, size_t* bytes);
+/* y[j] for the nonzeros of rows [row_begin, row_end) of the m-row CSR; e and y T[nnz], distinct
+ * buffers.  Device pointers; asynchronous on `stream`; no allocation, no host synchronisation,
+ * capturable in a graph.  OFX_EINVAL: a bad size or row range, int32 indices that cannot address
+ * the problem, a NULL pointer; OFX_EUNSUPPORTED: a dtype; OFX_EWORKSPACE: a workspace too small. */
+int ofx_edge_softmax_csr(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t nnz,
+                         const void* row_ptr, const void* e, void* y, int64_t row_begin,
+                         int64_t row_end, void* workspace, size_t workspace_bytes,
+                         const ofx_spmm_options* opts);
+/* kCPU version: host pointers, synchronous, the same bits.                                      */
+int ofx_edge_softmax_csr_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t nnz,
+                             const void* row_ptr, const void* e, void* y, int64_t row_begin,
+                             int64_t row_end, const ofx_spmm_options* opts);
+/* de[j] from the forward's y and the upstream g (contract above); three distinct buffers.        */
+int ofx_edge_softmax_csr_grad(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t nnz,
+                              const void* row_ptr, const void* y, const void* g, void* de,
+                              int64_t row_begin, int64_t row_end, void* workspace,
+                              size_t workspace_bytes, const ofx_spmm_options* opts);
+int ofx_edge_softmax_csr_grad_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                  int64_t nnz, const void* row_ptr, const void* y, const void* g,
+                                  void* de, int64_t row_begin, int64_t row_end,
+                                  const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -781,6 +849,19 @@ int ofx_functional_spmm_csr_reduce_grad_values(void* stream, const ofx_tensor_de
                                                const ofx_tensor_desc* b, int64_t a_num_rows,
                                                int64_t a_num_cols, ofx_tensor_desc* out, void* tmp,
                                                size_t tmp_bytes, size_t* tmp_size_out);
+/* functional::EdgeSoftmaxCsr / EdgeSoftmaxCsrGrad: ops "edge_softmax_csr" (row_ptr [M+1],
+ * col_idx [nnz] for its shape only, e [nnz] -> out [nnz] in e's dtype) and
+ * "edge_softmax_csr_grad" (y, dy [nnz] -> dx [nnz]) of oneflow/user/ops/edge_softmax_op.cpp through
+ * the op-registry dispatch; the contract of ofx_edge_softmax_csr(_grad).  tmp_size_out != NULL:
+ * only the tmp size is computed.                                                                */
+int ofx_functional_edge_softmax_csr(void* stream, const ofx_tensor_desc* row_ptr,
+                                    const ofx_tensor_desc* col_idx, const ofx_tensor_desc* e,
+                                    ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+                                    size_t* tmp_size_out);
+int ofx_functional_edge_softmax_csr_grad(void* stream, const ofx_tensor_desc* row_ptr,
+                                         const ofx_tensor_desc* col_idx, const ofx_tensor_desc* y,
+                                         const ofx_tensor_desc* dy, ofx_tensor_desc* dx, void* tmp,
+                                         size_t tmp_bytes, size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

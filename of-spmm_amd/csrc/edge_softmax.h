@@ -1,0 +1,98 @@
+// edge_softmax.h — what the kCPU kernels (edge_softmax_cpu.cpp) and the HIP kernels
+// (edge_softmax.hip) of op "edge_softmax_csr" and of its gradient share: the exponential, the
+// constants of the sum's order and the argument checks of their C-ABI entries (contract in
+// include/ofx_spmm.h).
+#ifndef OFX_EDGE_SOFTMAX_H_
+#define OFX_EDGE_SOFTMAX_H_
+
+#include "ofx_internal.h"
+#include "spmm_common.h"
+#include "spmm_extremum.h"
+
+namespace ofx {
+namespace esm {
+
+// The sum's order (the SDDMM's, along the row): leaves of kLeaf consecutive positions, summed
+// sequentially from +0; the leaves, zero-padded to a power of two, added pairwise level by level.
+constexpr int kLeaf = 8;
+// The HIP kernels cut a row longer than kTile into tiles of kTileLeaves leaves (one leaf per lane
+// of a wave) and add the tile values pairwise in tile order: the same tree.  Rows of at most
+// kTile elements are held in registers (the widest lane group is the wave).
+constexpr int kTileLeaves = 64;
+constexpr int kTile = kTileLeaves * kLeaf;
+
+// exp(t) for t <= 0 in the accumulation type, from IEEE-exact steps only (multiply, add,
+// subtract, divide in f64, rint to nearest even, a power of two assembled from exponent bits),
+// each rounded separately, so that the host and the device return the same bits.  No library or
+// hardware transcendental.
+//   t below the cut-off (f32 -87, f64 -708), -inf included: +0; no result is subnormal
+//   t == +-0: exactly 1;  NaN: the canonical quiet NaN
+// A positive t is never passed (t = e - max(e)).  exp_acc<A> is the entry; exp_acc_of are its two
+// forms.
+// f32: Cody-Waite reduction t = k ln2 + r with ln2 = C1 + C2 (k C1 is exact), the Cephes expf
+// degree-5 polynomial, p = (poly(r) * (r * r) + r) + 1, times 2^k.  -87 <= t gives k >= -126 and
+// a result above 1.6e-38, the smallest normal being 1.18e-38.
+OFX_HD float exp_acc_of(float t) {
+#pragma clang fp contract(off)
+  if (t != t) return __builtin_nanf("");
+  if (t < -87.0f) return 0.0f;
+  const float k = __builtin_rintf(t * 1.44269504088896341f);
+  float r = t - k * 0.693359375f;
+  r = r - k * -2.12194440e-4f;
+  float p = 1.9875691500e-4f;
+  p = p * r + 1.3981999507e-3f;
+  p = p * r + 8.3334519073e-3f;
+  p = p * r + 4.1665795894e-2f;
+  p = p * r + 1.6666665459e-1f;
+  p = p * r + 5.0000001201e-1f;
+  const float z = r * r;
+  p = p * z;
+  p = p + r;
+  p = p + 1.0f;
+  const float scale = bits_to_f32((uint32_t)((int)k + 127) << 23);
+  return p * scale;
+}
+
+// f64: the Cephes exp rational form, e^r = 1 + 2 r P(r^2) / (Q(r^2) - r P(r^2)), with the same
+// reduction (C1 = 0.693145751953125).  -708 <= t gives k >= -1021 and a result above 3.3e-308,
+// the smallest normal being 2.2e-308.
+OFX_HD double exp_acc_of(double t) {
+#pragma clang fp contract(off)
+  if (t != t) return __builtin_nan("");
+  if (t < -708.0) return 0.0;
+  const double k = __builtin_rint(t * 1.4426950408889634073599);
+  double r = t - k * 6.93145751953125e-1;
+  r = r - k * 1.42860682030941723212e-6;
+  const double z = r * r;
+  double pp = 1.26177193074810590878e-4;
+  pp = pp * z + 3.02994407707441961300e-2;
+  pp = pp * z + 9.99999999999999999910e-1;
+  pp = pp * r;
+  double qq = 3.00198505138664455042e-6;
+  qq = qq * z + 2.52448340349684104192e-3;
+  qq = qq * z + 2.27265548208155028766e-1;
+  qq = qq * z + 2.00000000000000000009e0;
+  double p = pp / (qq - pp);
+  p = p * 2.0;
+  p = p + 1.0;
+  const double scale =
+      __builtin_bit_cast(double, (uint64_t)((int64_t)k + 1023) << 52);
+  return p * scale;
+}
+
+template <typename A>
+OFX_HD A exp_acc(A t) {
+  return exp_acc_of(t);
+}
+
+// ---- argument checks shared by the device and host entries ----------------------------------
+static inline int check_edge_softmax_args(const char* fn, int idx_dtype, int val_dtype, int64_t m,
+                                          int64_t nnz, int64_t row_begin, int64_t row_end) {
+  if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, 0, 0, nnz)) return rc;
+  return check_row_range(fn, row_begin, row_end, m);
+}
+
+}  // namespace esm
+}  // namespace ofx
+
+#endif  // OFX_EDGE_SOFTMAX_H_

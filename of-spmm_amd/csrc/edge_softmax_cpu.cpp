@@ -1,0 +1,146 @@
+// edge_softmax_cpu.cpp — the DeviceType::kCPU kernels of op "edge_softmax_csr" and of its gradient
+// (contract in include/ofx_spmm.h, shared helpers in edge_softmax.h).  Row-parallel over OpenMP
+// like spmm_extremum_cpu.cpp; the same bits as the HIP kernels (edge_softmax.hip).
+#pragma clang fp contract(off)
+
+#include <omp.h>
+
+#include <type_traits>
+#include <vector>
+
+#include "edge_softmax.h"
+#include "ofx_internal.h"
+#include "spmm_common.h"
+#include "spmm_extremum.h"
+
+namespace ofx {
+namespace {
+
+using namespace esm;
+
+// The contract's sum of x[0 .. len): leaves of kLeaf positions from +0, zero-padded to a power of
+// two, pairwise level by level.  `leaf` is scratch.
+template <typename A>
+A tree_sum(const A* x, int64_t len, std::vector<A>& leaf) {
+#pragma clang fp contract(off)
+  const int64_t leaves = (len + kLeaf - 1) / kLeaf;
+  int64_t padded = 1;
+  while (padded < leaves) padded *= 2;
+  leaf.assign((size_t)padded, A(0));
+  for (int64_t i = 0; i < leaves; ++i) {
+    A s = A(0);
+    const int64_t end = (i + 1) * kLeaf < len ? (i + 1) * kLeaf : len;
+    for (int64_t p = i * kLeaf; p < end; ++p) s = s + x[p];
+    leaf[(size_t)i] = s;
+  }
+  for (int64_t w = 1; w < padded; w *= 2)
+    for (int64_t i = 0; i < padded; i += 2 * w) leaf[(size_t)i] = leaf[(size_t)i] + leaf[(size_t)(i + w)];
+  return leaf[0];
+}
+
+template <typename T, typename I>
+void cpu_forward(int nthreads, const I* rp, const T* e, T* y, int64_t row_begin, int64_t row_end) {
+#pragma clang fp contract(off)
+  using A = typename Num<T>::acc;
+#pragma omp parallel num_threads(nthreads)
+  {
+    std::vector<A> x, leaf;
+#pragma omp for schedule(dynamic, 64)
+    for (int64_t r = row_begin; r < row_end; ++r) {
+      const int64_t j0 = (int64_t)rp[r], len = (int64_t)rp[r + 1] - j0;
+      if (len <= 0) continue;
+      A best = Num<T>::load(e[j0]);
+      for (int64_t p = 1; p < len; ++p) {
+        const A c = Num<T>::load(e[j0 + p]);
+        best = better(c, best, true) ? c : best;
+      }
+      x.resize((size_t)len);
+      for (int64_t p = 0; p < len; ++p) {
+        const A t = Num<T>::load(e[j0 + p]) - best;
+        x[(size_t)p] = exp_acc<A>(t);
+      }
+      const A s = tree_sum(x.data(), len, leaf);
+      for (int64_t p = 0; p < len; ++p) {
+        const A q = x[(size_t)p] / s;
+        y[j0 + p] = Num<T>::store(canonical_nan(q));
+      }
+    }
+  }
+}
+
+template <typename T, typename I>
+void cpu_backward(int nthreads, const I* rp, const T* y, const T* g, T* de, int64_t row_begin,
+                  int64_t row_end) {
+#pragma clang fp contract(off)
+  using A = typename Num<T>::acc;
+#pragma omp parallel num_threads(nthreads)
+  {
+    std::vector<A> q, leaf;
+#pragma omp for schedule(dynamic, 64)
+    for (int64_t r = row_begin; r < row_end; ++r) {
+      const int64_t j0 = (int64_t)rp[r], len = (int64_t)rp[r + 1] - j0;
+      if (len <= 0) continue;
+      q.resize((size_t)len);
+      for (int64_t p = 0; p < len; ++p) {
+        const A prod = Num<T>::load(y[j0 + p]) * Num<T>::load(g[j0 + p]);
+        q[(size_t)p] = prod;
+      }
+      const A d = tree_sum(q.data(), len, leaf);
+      for (int64_t p = 0; p < len; ++p) {
+        const A diff = Num<T>::load(g[j0 + p]) - d;
+        const A prod = Num<T>::load(y[j0 + p]) * diff;
+        de[j0 + p] = Num<T>::store(canonical_nan(prod));
+      }
+    }
+  }
+}
+
+int threads_of(int num_threads) { return num_threads > 0 ? num_threads : omp_get_max_threads(); }
+
+}  // namespace
+}  // namespace ofx
+
+using namespace ofx;
+
+extern "C" int ofx_edge_softmax_csr_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                        int64_t nnz, const void* row_ptr, const void* e, void* y,
+                                        int64_t row_begin, int64_t row_end,
+                                        const ofx_spmm_options* opts) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_READ_OPTIONS(opts, "edge_softmax_csr_cpu");  // validated; no option has an effect
+    int rc = esm::check_edge_softmax_args("edge_softmax_csr_cpu", idx_dtype, val_dtype, m, nnz,
+                                          row_begin, row_end);
+    if (rc) return rc;
+    if (row_end == row_begin || nnz == 0) return OFX_OK;
+    OFX_REQUIRE(row_ptr && e && y, OFX_EINVAL, "edge_softmax_csr_cpu: NULL pointer");
+    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+      using T = std::remove_pointer_t<decltype(tp)>;
+      using I = std::remove_pointer_t<decltype(ip)>;
+      cpu_forward<T, I>(threads_of(num_threads), (const I*)row_ptr, (const T*)e, (T*)y, row_begin,
+                        row_end);
+      return OFX_OK;
+    });
+  });
+}
+
+extern "C" int ofx_edge_softmax_csr_grad_cpu(int num_threads, int idx_dtype, int val_dtype,
+                                             int64_t m, int64_t nnz, const void* row_ptr,
+                                             const void* y, const void* g, void* de,
+                                             int64_t row_begin, int64_t row_end,
+                                             const ofx_spmm_options* opts) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_READ_OPTIONS(opts, "edge_softmax_csr_grad_cpu");
+    int rc = esm::check_edge_softmax_args("edge_softmax_csr_grad_cpu", idx_dtype, val_dtype, m, nnz,
+                                          row_begin, row_end);
+    if (rc) return rc;
+    if (row_end == row_begin || nnz == 0) return OFX_OK;
+    OFX_REQUIRE(row_ptr && y && g && de, OFX_EINVAL, "edge_softmax_csr_grad_cpu: NULL pointer");
+    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+      using T = std::remove_pointer_t<decltype(tp)>;
+      using I = std::remove_pointer_t<decltype(ip)>;
+      cpu_backward<T, I>(threads_of(num_threads), (const I*)row_ptr, (const T*)y, (const T*)g,
+                         (T*)de, row_begin, row_end);
+      return OFX_OK;
+    });
+  });
+}

@@ -127,6 +127,29 @@ REGISTER_USER_OP("spmm_csr_reduce_grad_values")
     .SetGetSbpFn(SpmmCsrReduceGradValuesOp::GetSbp)
     .SetDataTypeInferFn(SpmmCsrReduceGradValuesOp::InferDataType);
 
+REGISTER_USER_OP("edge_softmax_csr")
+    .Input("a_csr_row_ptr")
+    .Input("a_csr_col_idx")
+    .Input("e")
+    .Output("out")
+    .SetLogicalTensorDescInferFn(EdgeSoftmaxCsrOp::InferLogicalTensorDesc)
+    .SetPhysicalTensorDescInferFn(EdgeSoftmaxCsrOp::InferPhysicalTensorDesc)
+    .SetGetSbpFn(EdgeSoftmaxCsrOp::GetSbp)
+    .SetDataTypeInferFn(EdgeSoftmaxCsrOp::InferDataType)
+    .SetInputArgModifyFn(EdgeSoftmaxCsrOp::ModifyInputArg);
+
+REGISTER_USER_OP("edge_softmax_csr_grad")
+    .Input("a_csr_row_ptr")
+    .Input("a_csr_col_idx")
+    .Input("y")
+    .Input("dy")
+    .Output("dx")
+    .SetLogicalTensorDescInferFn(EdgeSoftmaxCsrGradOp::InferLogicalTensorDesc)
+    .SetPhysicalTensorDescInferFn(EdgeSoftmaxCsrGradOp::InferPhysicalTensorDesc)
+    .SetGetSbpFn(EdgeSoftmaxCsrGradOp::GetSbp)
+    .SetDataTypeInferFn(EdgeSoftmaxCsrGradOp::InferDataType)
+    .SetInputArgModifyFn(EdgeSoftmaxCsrGradOp::ModifyInputArg);
+
 REGISTER_USER_OP("eager_ccl_all_gather")
     .Input("in")
     .Output("out")

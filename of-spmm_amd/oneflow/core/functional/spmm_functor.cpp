@@ -797,3 +797,51 @@ extern "C" int ofx_functional_spmm_csr_reduce_grad_values(
                               tmp, tmp_bytes, tmp_size_out));
   });
 }
+
+// ---- functional::EdgeSoftmaxCsr and its gradient functor ----------------------------------------
+// Ops "edge_softmax_csr" and "edge_softmax_csr_grad" (oneflow/user/ops/edge_softmax_op.cpp)
+// through the same op-registry dispatch.
+namespace oneflow {
+
+int EdgeSoftmaxCsr(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+                   const ofx_tensor_desc* in, const ofx_tensor_desc* grad, ofx_tensor_desc* out,
+                   void* tmp, size_t tmp_bytes, size_t* tmp_size_out, int num_threads) {
+  // an earlier launch's loud failure comes back here as OFX_EPLAN (as for spmm_csr)
+  if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("edge_softmax_csr");
+  if (grad == nullptr)
+    return ToStatus(RunUserOp("edge_softmax_csr",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"e", in}},
+                              {{"out", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                              num_threads));
+  return ToStatus(RunUserOp("edge_softmax_csr_grad",
+                            {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"y", in},
+                             {"dy", grad}},
+                            {{"dx", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                            num_threads));
+}
+
+}  // namespace oneflow
+
+extern "C" int ofx_functional_edge_softmax_csr(void* stream, const ofx_tensor_desc* row_ptr,
+                                               const ofx_tensor_desc* col_idx,
+                                               const ofx_tensor_desc* e, ofx_tensor_desc* out,
+                                               void* tmp, size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(e != nullptr, OFX_EINVAL, "edge_softmax_csr: NULL input e");
+    return EdgeSoftmaxCsr(stream, row_ptr, col_idx, e, nullptr, out, tmp, tmp_bytes, tmp_size_out,
+                          0);
+  });
+}
+
+extern "C" int ofx_functional_edge_softmax_csr_grad(void* stream, const ofx_tensor_desc* row_ptr,
+                                                    const ofx_tensor_desc* col_idx,
+                                                    const ofx_tensor_desc* y,
+                                                    const ofx_tensor_desc* dy, ofx_tensor_desc* dx,
+                                                    void* tmp, size_t tmp_bytes,
+                                                    size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(y != nullptr && dy != nullptr, OFX_EINVAL,
+                "edge_softmax_csr_grad: NULL input y or dy");
+    return EdgeSoftmaxCsr(stream, row_ptr, col_idx, y, dy, dx, tmp, tmp_bytes, tmp_size_out, 0);
+  });
+}

@@ -29,6 +29,13 @@ int SpmmCsrGlobalWithState(void* stream, const ofx_tensor_desc* row_ptr,
 bool SpmmCsrPlanStateStats(user_op::OpKernelState* state, int64_t* entries, int64_t* plans,
                            int64_t* hits, bool release);
 
+// functional::EdgeSoftmaxCsr / EdgeSoftmaxCsrGrad: ops "edge_softmax_csr" (in = e, grad == NULL)
+// and "edge_softmax_csr_grad" (in = y, grad = dy) through the op-registry dispatch.  With
+// tmp_size_out != NULL only the tmp-buffer size is computed.  num_threads: CPU kernel only.
+int EdgeSoftmaxCsr(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+                   const ofx_tensor_desc* in, const ofx_tensor_desc* grad, ofx_tensor_desc* out,
+                   void* tmp, size_t tmp_bytes, size_t* tmp_size_out, int num_threads);
+
 }  // namespace oneflow
 
 #endif  // OFX_ONEFLOW_CORE_FUNCTIONAL_SPMM_FUNCTOR_H_

@@ -382,6 +382,53 @@ def spmm_csr_reduce_grad_values(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torc
     return out
 
 
+def _edge_softmax_inputs(op, rp, ci, named):
+    """The shape and dtype checks the two edge-softmax ops share, ahead of the op layer's own (its
+    messages name the C-ABI); `named`: the per-nonzero value tensors."""
+    for name, t in named:
+        if t.dim() != 1:
+            raise RuntimeError(f"{op}: {name} should be 1-D, got shape {tuple(t.shape)}")
+        if t.numel() != ci.numel():
+            raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} elements (as "
+                               f"a_csr_col_idx), got {t.numel()}")
+    if rp.dtype != ci.dtype:
+        raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
+                        f"({ci.dtype} vs {rp.dtype})")
+    dtype_code(rp.dtype)
+    first = named[0][1]
+    if first.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {first.dtype}")
+    for name, t in named[1:]:
+        if t.dtype != first.dtype:
+            raise TypeError(f"{op}: {name} datatype should be equal to {named[0][0]}")
+
+
+def edge_softmax_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, e: torch.Tensor, *,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "edge_softmax_csr": out[j] = softmax of the scores e over the nonzeros of j's row (DGL's
+    edge_softmax, PyG's softmax(src, ptr=row_ptr)); contract in include/ofx_spmm.h.  One HIP
+    launch on GPU tensors, the kCPU kernel on CPU tensors: the same bits."""
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    e = _prep(e, "e")
+    _edge_softmax_inputs("edge_softmax_csr", rp, ci, [("e", e)])
+    if out is None:
+        out = torch.empty_like(e)
+    _run_grad_op(LIB.ofx_functional_edge_softmax_csr, e, [rp, ci, e], [out], [])
+    return out
+
+
+def edge_softmax_csr_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                          y: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """Op "edge_softmax_csr_grad": dx[j] = y[j] * (dy[j] - sum over j's row of y * dy), from the
+    forward's stored y."""
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    y, dy = _prep(y, "y"), _prep(dy, "dy")
+    _edge_softmax_inputs("edge_softmax_csr_grad", rp, ci, [("y", y), ("dy", dy)])
+    dx = torch.empty_like(y)
+    _run_grad_op(LIB.ofx_functional_edge_softmax_csr_grad, y, [rp, ci, y, dy], [dx], [])
+    return dx
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

@@ -6,6 +6,7 @@
 `spmm` is differentiable in the values and in b (autograd.py: SDDMM and A^T @ dC).
     out = flow_spmm.spmm(..., reduce="max")            # "sum" (default), "mean", "max", "min"
     out, arg = flow_spmm.spmm_reduce(..., reduce="max")  # arg: the winning nonzero per element
+    y = flow_spmm.edge_softmax(row_ptr, col_idx, e)    # softmax of per-edge scores over each row
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 
@@ -14,9 +15,9 @@ Re-exports mirror python/oneflow/__init__.py:158-160 (`from oneflow._C import ..
 from . import _C, _lib, autograd, build, ops, synth  # noqa: F401
 from ._C import spmm_csr, spmm_csr_reduce
 from ._lib import OfxError
-from .autograd import csr_transpose, fused_spmm, sddmm, spmm, spmm_reduce
+from .autograd import csr_transpose, edge_softmax, fused_spmm, sddmm, spmm, spmm_reduce
 from .build import coo_to_csr
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_reduce", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "_C"]
+__all__ = ["spmm", "spmm_reduce", "edge_softmax", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "_C"]

@@ -158,6 +158,18 @@ def _load():
         "ofx_row_scale_by_degree": ([p, i32, i32, i64, i64, p, p, i64, p, i64, i64, i64], i32),
         "ofx_row_scale_by_degree_cpu": ([i32, i32, i32, i64, i64, p, p, i64, p, i64, i64, i64],
                                         i32),
+        "ofx_edge_softmax_csr_workspace_size": ([i32, i32, i64, i64, popt, ctypes.POINTER(sz)],
+                                                i32),
+        "ofx_edge_softmax_csr": ([p, i32, i32, i64, i64, p, p, p, i64, i64, p, sz, popt], i32),
+        "ofx_edge_softmax_csr_cpu": ([i32, i32, i32, i64, i64, p, p, p, i64, i64, popt], i32),
+        "ofx_edge_softmax_csr_grad": ([p, i32, i32, i64, i64, p, p, p, p, i64, i64, p, sz, popt],
+                                      i32),
+        "ofx_edge_softmax_csr_grad_cpu": ([i32, i32, i32, i64, i64, p, p, p, p, i64, i64, popt],
+                                          i32),
+        "ofx_functional_edge_softmax_csr": ([p, pdesc, pdesc, pdesc, pdesc, p, sz,
+                                             ctypes.POINTER(sz)], i32),
+        "ofx_functional_edge_softmax_csr_grad": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, p, sz,
+                                                  ctypes.POINTER(sz)], i32),
         "ofx_coo_to_csr_workspace_size": ([i32, i64, i64, i64, ctypes.POINTER(sz)], i32),
         "ofx_coo_to_csr": ([p, i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, p, p, p, sz], i32),
         "ofx_coo_to_csr_cpu": ([i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, ctypes.POINTER(i64)], i32),

@@ -46,7 +46,11 @@ def gather_values(perm: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
 def sddmm(row_ptr: torch.Tensor, col_idx: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
           static_csr: int = 0) -> torch.Tensor:
     """out[j] = <a[row(j), :], b[col_idx[j], :]>: op "sddmm_csr" through the op layer
-    (`static_csr`: the forward's promise that the CSR is unchanged; its SDDMM plan is kept)."""
+    (`static_csr`: the forward's promise that the CSR is unchanged; its SDDMM plan is kept).
+    Differentiable in a and b when one of them requires a gradient (the scores of a dot-product
+    attention layer: SddmmCsrFunction)."""
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        return SddmmCsrFunction.apply(row_ptr, col_idx, a, b, int(static_csr))
     return _C.sddmm_csr(row_ptr, col_idx, a, b, row_ptr.numel() - 1, b.shape[0],
                         static_csr=static_csr)
 
@@ -145,6 +149,61 @@ class SpmmCsrFunction(torch.autograd.Function):
         if ctx.needs_input_grad[5]:
             d_b = TRANSPOSE_CACHE.grad_b(row_ptr, col_idx, values.detach(), ctx.m, ctx.k, d_out)
         return None, None, d_values, None, None, d_b, None
+
+
+class SddmmCsrFunction(torch.autograd.Function):
+    """out[j] = <a[row(j), :], b[col(j), :]>, differentiable in a and b.  With g = d(out) as the
+    values of A's pattern: d(a) = A(g) @ b and d(b) = A(g)^T @ a, both the SpMM kernels (the latter
+    on the cached transpose)."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, a, b, static_csr=0):
+        ctx.save_for_backward(row_ptr, col_idx, a, b)
+        ctx.static_csr = static_csr
+        return _C.sddmm_csr(row_ptr, col_idx, a, b, row_ptr.numel() - 1, b.shape[0],
+                            static_csr=static_csr)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        row_ptr, col_idx, a, b = ctx.saved_tensors
+        g = d_out.contiguous()
+        m, k = row_ptr.numel() - 1, b.shape[0]
+        d_a = d_b = None
+        if ctx.needs_input_grad[2]:
+            d_a = spmm_csr(row_ptr, col_idx, g, m, k, b.detach())
+        if ctx.needs_input_grad[3]:
+            d_b = TRANSPOSE_CACHE.grad_b(row_ptr, col_idx, g, m, k, a.detach())
+        return None, None, d_a, d_b, None
+
+
+class EdgeSoftmaxFunction(torch.autograd.Function):
+    """y = edge_softmax(row_ptr, e), differentiable in e.  The output is saved and the backward is
+    op "edge_softmax_csr_grad" on it (nothing is recomputed)."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, e):
+        y = _C.edge_softmax_csr(row_ptr, col_idx, e)
+        ctx.save_for_backward(row_ptr, col_idx, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        row_ptr, col_idx, y = ctx.saved_tensors
+        return None, None, _C.edge_softmax_csr_grad(row_ptr, col_idx, y, d_y.contiguous())
+
+
+def edge_softmax(a_csr_row_ptr, a_csr_col_idx, e, *, out=None):
+    """The scores e [nnz] of a CSR's nonzeros normalised over each row:
+    y[j] = exp(e[j] - max_row) / sum over j's row of exp(e - max_row) (DGL's edge_softmax, PyG's
+    softmax(src, ptr=row_ptr)), the step between `sddmm` and `spmm` of dot-product graph
+    attention.  One launch, deterministic, the same bits on CPU and GPU tensors; differentiable
+    in e.  `a_csr_col_idx` is taken for its shape only.  `out=` only when no gradient is being
+    recorded."""
+    if torch.is_grad_enabled() and e.requires_grad:
+        if out is not None:
+            raise RuntimeError("edge_softmax: out= is not supported when gradients are required")
+        return EdgeSoftmaxFunction.apply(a_csr_row_ptr, a_csr_col_idx, e)
+    return _C.edge_softmax_csr(a_csr_row_ptr, a_csr_col_idx, e, out=out)
 
 
 class SpmmCsrReduceFunction(torch.autograd.Function):
@@ -272,4 +331,5 @@ def fused_spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_col
 
 
 __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm", "TRANSPOSE_CACHE", "ops",
-           "FusedSpmmCsrFunction", "fused_spmm", "SpmmCsrReduceFunction", "spmm_reduce"]
+           "FusedSpmmCsrFunction", "fused_spmm", "SpmmCsrReduceFunction", "spmm_reduce",
+           "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax"]
