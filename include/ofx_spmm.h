@@ -470,6 +470,51 @@ int ofx_edge_softmax_csr_grad_cpu(int num_threads, int idx_dtype, int val_dtype,
                                   void* de, int64_t row_begin, int64_t row_end,
                                   const ofx_spmm_options* opts);
 
+/* ---- multi-head SpMM / SDDMM (ops "spmm_csr_heads", "sddmm_csr_heads") ---------
+ * The hot path of multi-head graph attention (GAT, graph transformers): H = heads of width D = d,
+ * N = H*D.  b, c and a are [rows, H*D] with head h in columns [h*D, (h+1)*D); values and the
+ * SDDMM's out are [nnz, H], row-major and contiguous.  One launch gathers each B row once for all
+ * heads; the two ops are each other's gradients.
+ *
+ * Rule: every head's slice has exactly the bits of the single-head op on that slice.
+ *   ofx_spmm_csr_heads: c[r - row_begin, h*D + x] = sum_j values[j, h] * b[col[j], h*D + x] with
+ *     ofx_spmm_csr's accumulation contract on (values[:, h], b[:, h*D:(h+1)*D]) under the same
+ *     options; the default split = chunk = ofx_spmm_default_split(D) is a function of D, not of
+ *     H*D.  Columns outside [0, k) add val * 0; an empty row writes +0.  heavy_threshold and
+ *     range_nnz have no numeric effect; planned != 0 or variant != 0 is refused (OFX_EINVAL).
+ *   ofx_sddmm_csr_heads: out[j, h] = <a[r - row_begin, h*D:(h+1)*D], b[col[j], h*D:(h+1)*D]> in
+ *     ofx_sddmm_csr's order within the head (8-column leaves of the head summed from +0, the
+ *     head's leaves zero-padded to a power of two and added pairwise); a row range writes
+ *     out[row_ptr[row_begin]*H .. row_ptr[row_end]*H).  d <= 2048 (OFX_EUNSUPPORTED beyond).
+ * heads == 1 gives the bits of ofx_spmm_csr / ofx_sddmm_csr.  HIP kernel, kCPU kernel and the
+ * per-head composition give the same bits.  Device versions: asynchronous on `stream`, no
+ * atomics, no allocation, no host synchronisation, capturable in a graph; a workspace smaller than
+ * the query's returns OFX_EWORKSPACE before anything is launched.                                */
+int ofx_spmm_csr_heads_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                      int64_t heads, int64_t d, int64_t nnz,
+                                      const ofx_spmm_options* opts, size_t* bytes);
+int ofx_spmm_csr_heads(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                       int64_t heads, int64_t d, int64_t nnz, const void* row_ptr,
+                       const void* col_idx, const void* values /* [nnz, heads] */, const void* b,
+                       int64_t ldb, void* c, int64_t ldc, int64_t row_begin, int64_t row_end,
+                       void* workspace, size_t workspace_bytes, const ofx_spmm_options* opts);
+int ofx_spmm_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                           int64_t heads, int64_t d, int64_t nnz, const void* row_ptr,
+                           const void* col_idx, const void* values, const void* b, int64_t ldb,
+                           void* c, int64_t ldc, int64_t row_begin, int64_t row_end,
+                           const ofx_spmm_options* opts);
+int ofx_sddmm_csr_heads_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t heads,
+                                       int64_t d, int64_t nnz, size_t* bytes);
+int ofx_sddmm_csr_heads(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                        int64_t heads, int64_t d, int64_t nnz, const void* row_ptr,
+                        const void* col_idx, const void* a, int64_t lda, const void* b, int64_t ldb,
+                        void* out /* [nnz, heads] */, int64_t row_begin, int64_t row_end,
+                        void* workspace, size_t workspace_bytes);
+int ofx_sddmm_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                            int64_t heads, int64_t d, int64_t nnz, const void* row_ptr,
+                            const void* col_idx, const void* a, int64_t lda, const void* b,
+                            int64_t ldb, void* out, int64_t row_begin, int64_t row_end);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -862,6 +907,21 @@ int ofx_functional_edge_softmax_csr_grad(void* stream, const ofx_tensor_desc* ro
                                          const ofx_tensor_desc* col_idx, const ofx_tensor_desc* y,
                                          const ofx_tensor_desc* dy, ofx_tensor_desc* dx, void* tmp,
                                          size_t tmp_bytes, size_t* tmp_size_out);
+/* functional::SpmmCsrHeads / SddmmCsrHeads: ops "spmm_csr_heads" (values [nnz, H], b [K, N] ->
+ * out [M, N]; H = values' columns, N % H == 0) and "sddmm_csr_heads" (a [M, N], b [K, N],
+ * attribute num_heads -> out [nnz, H]) of oneflow/user/ops/spmm_heads_op.cpp through the
+ * op-registry dispatch; the contract of ofx_spmm_csr_heads / ofx_sddmm_csr_heads.
+ * tmp_size_out != NULL: only the tmp size is computed.                                          */
+int ofx_functional_spmm_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                  const ofx_tensor_desc* col_idx, const ofx_tensor_desc* values,
+                                  const ofx_tensor_desc* b, int64_t a_num_rows, int64_t a_num_cols,
+                                  ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+                                  size_t* tmp_size_out);
+int ofx_functional_sddmm_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                   const ofx_tensor_desc* col_idx, const ofx_tensor_desc* a,
+                                   const ofx_tensor_desc* b, int64_t num_heads,
+                                   ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+                                   size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

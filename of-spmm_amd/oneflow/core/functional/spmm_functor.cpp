@@ -845,3 +845,42 @@ extern "C" int ofx_functional_edge_softmax_csr_grad(void* stream, const ofx_tens
     return EdgeSoftmaxCsr(stream, row_ptr, col_idx, y, dy, dx, tmp, tmp_bytes, tmp_size_out, 0);
   });
 }
+
+// ---- functional::SpmmCsrHeads / SddmmCsrHeads ---------------------------------------------------
+// Ops "spmm_csr_heads" and "sddmm_csr_heads" (oneflow/user/ops/spmm_heads_op.cpp) through the same
+// op-registry dispatch.
+extern "C" int ofx_functional_spmm_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                             const ofx_tensor_desc* col_idx,
+                                             const ofx_tensor_desc* values,
+                                             const ofx_tensor_desc* b, int64_t a_num_rows,
+                                             int64_t a_num_cols, ofx_tensor_desc* out, void* tmp,
+                                             size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(values != nullptr && b != nullptr, OFX_EINVAL,
+                "spmm_csr_heads: NULL input a_csr_values or b");
+    // an earlier launch's loud failure comes back here as OFX_EPLAN (as for spmm_csr)
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_heads");
+    return ToStatus(RunUserOp("spmm_csr_heads",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                               {"a_csr_values", values}, {"b", b}},
+                              {{"out", out}},
+                              {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols}}, stream,
+                              tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
+extern "C" int ofx_functional_sddmm_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                              const ofx_tensor_desc* col_idx,
+                                              const ofx_tensor_desc* a, const ofx_tensor_desc* b,
+                                              int64_t num_heads, ofx_tensor_desc* out, void* tmp,
+                                              size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(a != nullptr && b != nullptr, OFX_EINVAL, "sddmm_csr_heads: NULL input a or b");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("sddmm_csr_heads");
+    return ToStatus(RunUserOp("sddmm_csr_heads",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"a", a},
+                               {"b", b}},
+                              {{"out", out}}, {{"num_heads", num_heads}}, stream, tmp, tmp_bytes,
+                              tmp_size_out));
+  });
+}

@@ -429,6 +429,92 @@ def edge_softmax_csr_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tens
     return dx
 
 
+def _heads_inputs(op, rp, ci, named):
+    """The index checks the two multi-head ops share, ahead of the op layer's own, and the dtype
+    equality of their value tensors (`named`: [(name, tensor)], "b" last)."""
+    if rp.dtype != ci.dtype:
+        raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
+                        f"({ci.dtype} vs {rp.dtype})")
+    dtype_code(rp.dtype)
+    b = named[-1][1]
+    if b.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {b.dtype}")
+    for name, t in named[:-1]:
+        if t.dtype != b.dtype:
+            raise TypeError(f"{op}: {name} datatype should be equal to b ({t.dtype} vs {b.dtype})")
+        if t.dim() != 2:
+            raise RuntimeError(f"{op}: {name} should be 2-D, got shape {tuple(t.shape)}")
+    if b.dim() != 2:
+        raise RuntimeError(f"{op}: b should be 2-D [K, heads * D], got shape {tuple(b.shape)}")
+
+
+def _check_out(op, out, shape, like, contiguous=False):
+    if contiguous and not out.is_contiguous():
+        raise RuntimeError(f"{op}: out must be contiguous")
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device:
+        raise RuntimeError(f"{op}: out must be a {tuple(shape)} tensor of dtype {like.dtype} on "
+                           f"{like.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+
+
+def spmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                   a_csr_values: torch.Tensor, a_num_rows: int, a_num_cols: int, b: torch.Tensor,
+                   *, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "spmm_csr_heads": out[M, H*D] with out[r, h*D + c] = sum over the row's nonzeros j of
+    a_csr_values[j, h] * b[a_csr_col_idx[j], h*D + c]; a_csr_values is [nnz, H], b is [K, H*D] with
+    head h in columns [h*D, (h+1)*D).  One launch for all heads; every head's slice has the bits
+    of spmm_csr on that slice (contract in include/ofx_spmm.h)."""
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    vals = _prep(a_csr_values, "a_csr_values")
+    bb = _prep(b, "b", matrix=True)
+    _heads_inputs("spmm_csr_heads", rp, ci, [("a_csr_values", vals), ("b", bb)])
+    if vals.shape[0] != ci.numel():
+        raise RuntimeError(f"spmm_csr_heads: a_csr_values should have nnz = {ci.numel()} rows (as "
+                           f"a_csr_col_idx), got {vals.shape[0]}")
+    if vals.shape[1] < 1 or bb.shape[1] % vals.shape[1] != 0:
+        raise RuntimeError(f"spmm_csr_heads: b's columns ({bb.shape[1]}) should be a multiple of "
+                           f"the number of heads ({vals.shape[1]})")
+    shape = (int(a_num_rows), bb.shape[1])
+    if out is None:
+        out = torch.empty(shape, dtype=bb.dtype, device=bb.device)
+    else:
+        _check_out("spmm_csr_heads", out, shape, bb)
+    if out.numel() == 0:
+        return out
+    _run_grad_op(LIB.ofx_functional_spmm_csr_heads, bb, [rp, ci, vals, bb], [out],
+                 [int(a_num_rows), int(a_num_cols)])
+    return out
+
+
+def sddmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a: torch.Tensor,
+                    b: torch.Tensor, num_heads: int, *,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "sddmm_csr_heads": out[nnz, H] with out[j, h] = <a[row(j), h*D:(h+1)*D],
+    b[col(j), h*D:(h+1)*D]> for a [M, H*D], b [K, H*D], H = num_heads: the scores of multi-head
+    graph attention and the values-gradient of spmm_csr_heads; every head has the bits of
+    sddmm_csr on its slice."""
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    a, bb = _prep(a, "a", matrix=True), _prep(b, "b", matrix=True)
+    _heads_inputs("sddmm_csr_heads", rp, ci, [("a", a), ("b", bb)])
+    heads = int(num_heads)
+    if heads < 1 or bb.shape[1] % heads != 0:
+        raise RuntimeError(f"sddmm_csr_heads: b's columns ({bb.shape[1]}) should be a multiple of "
+                           f"num_heads ({heads})")
+    if a.shape[1] != bb.shape[1]:
+        raise RuntimeError("sddmm_csr_heads: a and b should have the same number of columns "
+                           f"({a.shape[1]} vs {bb.shape[1]})")
+    shape = (ci.numel(), heads)
+    if out is None:
+        out = torch.empty(shape, dtype=bb.dtype, device=bb.device)
+    else:
+        _check_out("sddmm_csr_heads", out, shape, bb, contiguous=True)
+    if out.numel() == 0:
+        return out
+    if bb.shape[1] == 0:  # empty inner dimension: every dot product is +0
+        return out.zero_()
+    _run_grad_op(LIB.ofx_functional_sddmm_csr_heads, bb, [rp, ci, a, bb], [out], [heads])
+    return out
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

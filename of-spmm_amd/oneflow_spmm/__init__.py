@@ -7,6 +7,10 @@
     out = flow_spmm.spmm(..., reduce="max")            # "sum" (default), "mean", "max", "min"
     out, arg = flow_spmm.spmm_reduce(..., reduce="max")  # arg: the winning nonzero per element
     y = flow_spmm.edge_softmax(row_ptr, col_idx, e)    # softmax of per-edge scores over each row
+Multi-head graph attention (q, k, v as [rows, H, D]; scores and weights as [nnz, H]):
+    e = flow_spmm.sddmm(row_ptr, col_idx, q, k)        # [nnz, H], one launch for all heads
+    w = flow_spmm.edge_softmax(row_ptr, col_idx, e)    # per-head composition (H launches)
+    out = flow_spmm.spmm(row_ptr, col_idx, w, M, K, v) # [M, H, D], one launch for all heads
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 

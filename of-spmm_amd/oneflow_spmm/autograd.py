@@ -43,12 +43,31 @@ def gather_values(perm: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _heads_2d(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A [rows, H, D] tensor made contiguous and viewed as [rows, H*D]."""
+    if t.dim() != 3:
+        raise RuntimeError(f"{name} should be 3-D [rows, heads, D], got shape {tuple(t.shape)}")
+    return t.contiguous().view(t.shape[0], t.shape[1] * t.shape[2])
+
+
 def sddmm(row_ptr: torch.Tensor, col_idx: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
           static_csr: int = 0) -> torch.Tensor:
     """out[j] = <a[row(j), :], b[col_idx[j], :]>: op "sddmm_csr" through the op layer
     (`static_csr`: the forward's promise that the CSR is unchanged; its SDDMM plan is kept).
     Differentiable in a and b when one of them requires a gradient (the scores of a dot-product
-    attention layer: SddmmCsrFunction)."""
+    attention layer: SddmmCsrFunction).
+
+    Multi-head: a [M, H, D] and b [K, H, D] give out [nnz, H] with out[j, h] = <a[row(j), h, :],
+    b[col_idx[j], h, :]> in one launch (op "sddmm_csr_heads"), every head with the bits of the
+    2-D call on its slice; `static_csr` is accepted and has no effect there."""
+    if a.dim() == 3:
+        if b.dim() != 3 or a.shape[1:] != b.shape[1:]:
+            raise RuntimeError("sddmm: a [M, H, D] needs b [K, H, D] with the same heads and D, "
+                               f"got {tuple(a.shape)} and {tuple(b.shape)}")
+        heads = a.shape[1]
+        if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+            return SddmmCsrHeadsFunction.apply(row_ptr, col_idx, a, b)
+        return _C.sddmm_csr_heads(row_ptr, col_idx, _heads_2d(a, "a"), _heads_2d(b, "b"), heads)
     if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
         return SddmmCsrFunction.apply(row_ptr, col_idx, a, b, int(static_csr))
     return _C.sddmm_csr(row_ptr, col_idx, a, b, row_ptr.numel() - 1, b.shape[0],
@@ -176,6 +195,120 @@ class SddmmCsrFunction(torch.autograd.Function):
         return None, None, d_a, d_b, None
 
 
+def _heads_grad_b(row_ptr, col_idx, values, m, k, x):
+    """A(values)^T @ x per head: op "spmm_csr_heads" on the cached transpose, with A^T's values =
+    the rows values[perm] of H (ofx_gather_rows on the device, a torch index on the host:
+    plumbing, not hot path)."""
+    rp_t, ci_t, perm = TRANSPOSE_CACHE.get(row_ptr, col_idx, k)
+    values = values.contiguous()
+    # the policy of _TransposeCache.grad_b: values met again unchanged (constant attention
+    # weights) keep their gathered copy; values new every step are gathered every step
+    cache = TRANSPOSE_CACHE
+    key = (row_ptr.data_ptr(), col_idx.data_ptr(), row_ptr._version, col_idx._version, k,
+           values.data_ptr(), values._version, values.dtype, tuple(values.shape),
+           str(values.device))
+    hit = cache.value_entries.get(key)
+    if hit is not None:
+        cache.value_entries.move_to_end(key)
+        return _C.spmm_csr_heads(rp_t, ci_t, hit[1], k, m, x)
+    if values.device.type == "cpu" or values.numel() == 0:
+        vals_t = values.index_select(0, perm.long())
+    else:
+        vals_t = torch.empty_like(values)
+        row_bytes = values.shape[1] * values.element_size()
+        check(LIB.ofx_gather_rows(current_stream_handle(values), dtype_code(perm.dtype),
+                                  values.shape[0], row_bytes, perm.data_ptr(), values.data_ptr(),
+                                  row_bytes, vals_t.data_ptr(), row_bytes), "gather_rows")
+    if values.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        pass  # a copy made inside a graph capture lives in the graph's pool: never cached
+    elif key in cache.seen:
+        cache.value_entries[key] = (values, vals_t)  # holds values: its storage cannot be reused
+        while len(cache.value_entries) > cache.capacity:
+            cache.value_entries.popitem(last=False)
+    else:
+        cache.seen[key] = values
+        while len(cache.seen) > cache.capacity:
+            cache.seen.popitem(last=False)
+    return _C.spmm_csr_heads(rp_t, ci_t, vals_t, k, m, x)
+
+
+class SpmmCsrHeadsFunction(torch.autograd.Function):
+    """out [M, H, D] = per head h, A(values[:, h]) @ b[:, h, :], differentiable in values [nnz, H]
+    and b [K, H, D]: d(values) is the multi-head SDDMM of d(out) and b, d(b) the multi-head SpMM
+    on the cached transpose.  No sum crosses heads, so both have the bits of the per-head
+    gradients."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, values, m, k, b):
+        heads, d = b.shape[1], b.shape[2]
+        b2 = _heads_2d(b, "b")
+        out = _C.spmm_csr_heads(row_ptr, col_idx, values, m, k, b2)
+        ctx.save_for_backward(row_ptr, col_idx, values, b2)
+        ctx.m, ctx.k, ctx.heads, ctx.d = m, k, heads, d
+        return out.view(m, heads, d)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        row_ptr, col_idx, values, b2 = ctx.saved_tensors
+        g = d_out.contiguous().view(ctx.m, ctx.heads * ctx.d)
+        d_values = d_b = None
+        if ctx.needs_input_grad[2]:
+            d_values = _C.sddmm_csr_heads(row_ptr, col_idx, g, b2, ctx.heads)
+        if ctx.needs_input_grad[5]:
+            d_b = _heads_grad_b(row_ptr, col_idx, values.detach().contiguous(), ctx.m, ctx.k, g)
+            d_b = d_b.view(ctx.k, ctx.heads, ctx.d)
+        return None, None, d_values, None, None, d_b
+
+
+class SddmmCsrHeadsFunction(torch.autograd.Function):
+    """out [nnz, H] = per head the SDDMM of a [M, H, D] and b [K, H, D], differentiable in a and b.
+    With g = d(out) as the per-head values of A's pattern: d(a) = spmm_heads(g, b) and d(b) =
+    spmm_heads on A^T with g[perm]."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, a, b):
+        heads, d = b.shape[1], b.shape[2]
+        a2, b2 = _heads_2d(a, "a"), _heads_2d(b, "b")
+        ctx.save_for_backward(row_ptr, col_idx, a2, b2)
+        ctx.heads, ctx.d = heads, d
+        return _C.sddmm_csr_heads(row_ptr, col_idx, a2, b2, heads)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        row_ptr, col_idx, a2, b2 = ctx.saved_tensors
+        g = d_out.contiguous()
+        m, k = row_ptr.numel() - 1, b2.shape[0]
+        d_a = d_b = None
+        if ctx.needs_input_grad[2]:
+            d_a = _C.spmm_csr_heads(row_ptr, col_idx, g, m, k, b2).view(m, ctx.heads, ctx.d)
+        if ctx.needs_input_grad[3]:
+            d_b = _heads_grad_b(row_ptr, col_idx, g, m, k, a2).view(k, ctx.heads, ctx.d)
+        return None, None, d_a, d_b
+
+
+def _spmm_heads(row_ptr, col_idx, values, m, k, b, out, reduce):
+    """`spmm` with b [K, H, D]: values [nnz, H] -> [M, H, D]."""
+    if reduce != "sum":
+        raise ValueError(f"spmm: a multi-head b [K, H, D] supports reduce='sum' only, got {reduce!r}")
+    if values.dim() != 2 or values.shape[1] != b.shape[1]:
+        raise RuntimeError("spmm: a multi-head b [K, H, D] needs a_csr_values [nnz, H], got "
+                           f"{tuple(values.shape)} for b {tuple(b.shape)}")
+    m, k = int(m), int(k)
+    heads, d = b.shape[1], b.shape[2]
+    if torch.is_grad_enabled() and (values.requires_grad or b.requires_grad):
+        if out is not None:
+            raise RuntimeError("spmm: out= is not supported when gradients are required")
+        return SpmmCsrHeadsFunction.apply(row_ptr, col_idx, values, m, k, b)
+    out2 = None
+    if out is not None:
+        if tuple(out.shape) != (m, heads, d) or not out.is_contiguous():
+            raise RuntimeError(f"spmm: out must be a contiguous {(m, heads, d)} tensor, got "
+                               f"{tuple(out.shape)}")
+        out2 = out.view(m, heads * d)
+    res = _C.spmm_csr_heads(row_ptr, col_idx, values, m, k, _heads_2d(b, "b"), out=out2)
+    return out if out is not None else res.view(m, heads, d)
+
+
 class EdgeSoftmaxFunction(torch.autograd.Function):
     """y = edge_softmax(row_ptr, e), differentiable in e.  The output is saved and the backward is
     op "edge_softmax_csr_grad" on it (nothing is recomputed)."""
@@ -198,7 +331,22 @@ def edge_softmax(a_csr_row_ptr, a_csr_col_idx, e, *, out=None):
     softmax(src, ptr=row_ptr)), the step between `sddmm` and `spmm` of dot-product graph
     attention.  One launch, deterministic, the same bits on CPU and GPU tensors; differentiable
     in e.  `a_csr_col_idx` is taken for its shape only.  `out=` only when no gradient is being
-    recorded."""
+    recorded.
+
+    Multi-head scores e [nnz, H] (the output of the 3-D `sddmm`) give y [nnz, H], each head
+    normalised on its own.  This is a COMPOSITION, not a kernel: one contiguous column per head
+    goes through the single-head op and the results are stacked back, so it costs H launches and
+    H column copies each way; a native multi-head kernel is a follow-up.  Every head has the bits
+    of the 1-D call on its column."""
+    if e.dim() == 2:
+        if out is not None and torch.is_grad_enabled() and e.requires_grad:
+            raise RuntimeError("edge_softmax: out= is not supported when gradients are required")
+        y = torch.stack([edge_softmax(a_csr_row_ptr, a_csr_col_idx, e[:, h].contiguous())
+                         for h in range(e.shape[1])], dim=1) if e.shape[1] else torch.empty_like(e)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
     if torch.is_grad_enabled() and e.requires_grad:
         if out is not None:
             raise RuntimeError("edge_softmax: out= is not supported when gradients are required")
@@ -272,7 +420,15 @@ def spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b, 
     the forward plans its work list once (_C.spmm_csr).
     `reduce`: "sum" (the default: the op as it always was), "mean", "max" or "min" (PyG's
     reduce=, DGL's u_mul_e_max / _min / copy-mean); `spmm_reduce` also returns max / min's arg.
-    static_csr applies to "sum" only."""
+    static_csr applies to "sum" only.
+
+    Multi-head: b [K, H, D] with a_csr_values [nnz, H] gives out [M, H, D], out[r, h, :] =
+    sum_j values[j, h] * b[col[j], h, :], in one launch (op "spmm_csr_heads"; reduce must be
+    "sum", static_csr is accepted and has no effect), every head with the bits of the 2-D call on
+    its slice."""
+    if isinstance(b, torch.Tensor) and b.dim() == 3:
+        return _spmm_heads(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b,
+                           out, reduce)
     if reduce != "sum":
         return spmm_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b,
                            reduce, out=out)[0]
@@ -332,4 +488,5 @@ def fused_spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_col
 
 __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm", "TRANSPOSE_CACHE", "ops",
            "FusedSpmmCsrFunction", "fused_spmm", "SpmmCsrReduceFunction", "spmm_reduce",
-           "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax"]
+           "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax", "SpmmCsrHeadsFunction",
+           "SddmmCsrHeadsFunction"]

@@ -209,6 +209,65 @@ def spmm_csr_cpu(row_ptr, col_idx, values, b, m, k, *, out=None, row_begin=0, ro
     return out
 
 
+def _nz(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def spmm_csr_heads(row_ptr, col_idx, values, b, m, k, heads, *, out=None, row_begin=0,
+                   row_end=None, options: Options | None = None, num_threads: int = 0,
+                   workspace_bytes: int | None = None):
+    """The multi-head SpMM at the C-ABI (ofx_spmm_csr_heads on device tensors, the kCPU kernel
+    ofx_spmm_csr_heads_cpu on host tensors): values [nnz, heads] contiguous, b [K, heads * D] with
+    unit column stride -> out [row_end - row_begin, heads * D].  workspace_bytes: the device
+    workspace to pass instead of the query's size (tests)."""
+    row_end = m if row_end is None else row_end
+    n, nnz = b.shape[1], col_idx.numel()
+    d = n // heads if heads else 0
+    if out is None:
+        out = torch.empty((row_end - row_begin, n), dtype=b.dtype, device=b.device)
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(b.dtype)
+    popt = ctypes.byref(options) if options else None
+    body = (idt, vdt, m, k, heads, d, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(values), _nz(b),
+            b.stride(0), out.data_ptr(), out.stride(0), row_begin, row_end)
+    if b.device.type == "cpu":
+        check(LIB.ofx_spmm_csr_heads_cpu(int(num_threads), *body, popt), "spmm_csr_heads_cpu")
+        return out
+    size = ctypes.c_size_t(0)
+    check(LIB.ofx_spmm_csr_heads_workspace_size(idt, vdt, m, k, heads, d, nnz, popt,
+                                                ctypes.byref(size)), "spmm_csr_heads")
+    ws = size.value if workspace_bytes is None else int(workspace_bytes)
+    wbuf = torch.empty(max(ws, 1), dtype=torch.uint8, device=b.device)
+    check(LIB.ofx_spmm_csr_heads(current_stream_handle(b), *body, wbuf.data_ptr(), ws, popt),
+          "spmm_csr_heads")
+    return out
+
+
+def sddmm_csr_heads(row_ptr, col_idx, a, b, m, k, heads, *, out=None, row_begin=0, row_end=None,
+                    num_threads: int = 0, workspace_bytes: int | None = None):
+    """The multi-head SDDMM at the C-ABI (ofx_sddmm_csr_heads / ofx_sddmm_csr_heads_cpu by device):
+    a holds rows [row_begin, row_end) of the left operand, out is [nnz, heads] and a row range
+    writes its own nonzeros' rows of it."""
+    row_end = m if row_end is None else row_end
+    n, nnz = b.shape[1], col_idx.numel()
+    d = n // heads if heads else 0
+    if out is None:
+        out = torch.empty((nnz, heads), dtype=b.dtype, device=b.device)
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(b.dtype)
+    body = (idt, vdt, m, k, heads, d, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(a), a.stride(0),
+            _nz(b), b.stride(0), _nz(out), row_begin, row_end)
+    if b.device.type == "cpu":
+        check(LIB.ofx_sddmm_csr_heads_cpu(int(num_threads), *body), "sddmm_csr_heads_cpu")
+        return out
+    size = ctypes.c_size_t(0)
+    check(LIB.ofx_sddmm_csr_heads_workspace_size(idt, vdt, m, heads, d, nnz, ctypes.byref(size)),
+          "sddmm_csr_heads")
+    ws = size.value if workspace_bytes is None else int(workspace_bytes)
+    wbuf = torch.empty(max(ws, 1), dtype=torch.uint8, device=b.device)
+    check(LIB.ofx_sddmm_csr_heads(current_stream_handle(b), *body, wbuf.data_ptr(), ws),
+          "sddmm_csr_heads")
+    return out
+
+
 def validate_csr(row_ptr, col_idx, m, k) -> int:
     """Device-side CSR check; returns 0 ok, 1 bad row_ptr, 2 column out of range (syncs)."""
     flag = torch.zeros(1, dtype=torch.int32, device=row_ptr.device)
@@ -236,5 +295,5 @@ def csr_row_slice(row_ptr, row_begin: int, row_end: int):
 
 __all__ = ["make_options", "default_split", "workspace_size", "SpmmCsrKernel", "spmm_csr_device",
            "describe",
-           "spmm_csr_gathered",
+           "spmm_csr_gathered", "spmm_csr_heads", "sddmm_csr_heads",
            "spmm_csr_cpu", "validate_csr", "csr_row_slice", "INT64_MAX", "_lib"]
