@@ -515,6 +515,52 @@ int ofx_sddmm_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64
                             const void* col_idx, const void* a, int64_t lda, const void* b,
                             int64_t ldb, void* out, int64_t row_begin, int64_t row_end);
 
+/* ---- multi-head edge softmax (ops "edge_softmax_csr_heads" / "_grad") -----------
+ * The step between ofx_sddmm_csr_heads and ofx_spmm_csr_heads: e, y, g, de are T[nnz, heads],
+ * row-major and contiguous, and every head is normalised over each row on its own, all heads in
+ * one launch.
+ *
+ * Rule: for every head h, y[:, h] has exactly the bits of ofx_edge_softmax_csr on e[:, h], and
+ * de[:, h] those of ofx_edge_softmax_csr_grad on (y[:, h], g[:, h]).  The whole contract above
+ * carries over per head: the row maximum with the max rule, one subtraction, exp_acc, leaves of 8
+ * consecutive POSITIONS OF THE ROW summed from +0, zero-padded to a power of two and added
+ * pairwise, one division, the canonical NaN, a separate rounding to T.  Heads never mix: a NaN,
+ * +inf or all -inf row in one head leaves the other heads of that row untouched.  heads == 1
+ * gives the bits of the single-head entries; heads == 0 or nnz == 0 writes nothing and returns
+ * OFX_OK.  The HIP kernels, the kCPU kernels and the per-column composition agree bit for bit.
+ *
+ * Row range: [row_begin, row_end) writes exactly out[row_ptr[row_begin]*heads ..
+ * row_ptr[row_end]*heads).  Offsets are formed in 64 bits: int32 indices are valid whenever they
+ * address the CSR itself (nnz, m <= INT32_MAX), whatever nnz * heads is.  opts: validated; no
+ * option has a numeric effect and `planned` is ignored.  Device versions: asynchronous on
+ * `stream`, no atomics, no allocation, no host synchronisation, capturable in a graph.  Workspace:
+ * 0 bytes (query it all the same); a NULL workspace with a non-zero size returns OFX_EWORKSPACE.
+ * OFX_EINVAL: a negative heads or size, a bad row range, int32 indices that cannot address the
+ * CSR, a NULL pointer; OFX_EUNSUPPORTED: a dtype.  Nothing is launched on an error.              */
+int ofx_edge_softmax_csr_heads_workspace_size(int idx_dtype, int val_dtype, int64_t m,
+                                              int64_t heads, int64_t nnz,
+                                              const ofx_spmm_options* opts, size_t* bytes);
+int ofx_edge_softmax_csr_heads(void* stream, int idx_dtype, int val_dtype, int64_t m,
+                               int64_t heads, int64_t nnz, const void* row_ptr,
+                               const void* e /* [nnz, heads] */, void* y, int64_t row_begin,
+                               int64_t row_end, void* workspace, size_t workspace_bytes,
+                               const ofx_spmm_options* opts);
+/* kCPU version: host pointers, synchronous, the same bits, independent of num_threads.          */
+int ofx_edge_softmax_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                   int64_t heads, int64_t nnz, const void* row_ptr, const void* e,
+                                   void* y, int64_t row_begin, int64_t row_end,
+                                   const ofx_spmm_options* opts);
+/* de[nnz, heads] from the forward's y and the upstream g; three distinct buffers.                */
+int ofx_edge_softmax_csr_heads_grad(void* stream, int idx_dtype, int val_dtype, int64_t m,
+                                    int64_t heads, int64_t nnz, const void* row_ptr, const void* y,
+                                    const void* g, void* de, int64_t row_begin, int64_t row_end,
+                                    void* workspace, size_t workspace_bytes,
+                                    const ofx_spmm_options* opts);
+int ofx_edge_softmax_csr_heads_grad_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                        int64_t heads, int64_t nnz, const void* row_ptr,
+                                        const void* y, const void* g, void* de, int64_t row_begin,
+                                        int64_t row_end, const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -922,6 +968,20 @@ int ofx_functional_sddmm_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
                                    const ofx_tensor_desc* b, int64_t num_heads,
                                    ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
                                    size_t* tmp_size_out);
+/* functional::EdgeSoftmaxCsrHeads / EdgeSoftmaxCsrHeadsGrad: ops "edge_softmax_csr_heads"
+ * (row_ptr [M+1], col_idx [nnz] for its shape only, e [nnz, H] -> out [nnz, H]) and
+ * "edge_softmax_csr_heads_grad" (y, dy [nnz, H] -> dx [nnz, H]) of
+ * oneflow/user/ops/edge_softmax_heads_op.cpp through the op-registry dispatch; the contract of
+ * ofx_edge_softmax_csr_heads(_grad).  tmp_size_out != NULL: only the tmp size is computed.       */
+int ofx_functional_edge_softmax_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                          const ofx_tensor_desc* col_idx, const ofx_tensor_desc* e,
+                                          ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+                                          size_t* tmp_size_out);
+int ofx_functional_edge_softmax_csr_heads_grad(void* stream, const ofx_tensor_desc* row_ptr,
+                                               const ofx_tensor_desc* col_idx,
+                                               const ofx_tensor_desc* y, const ofx_tensor_desc* dy,
+                                               ofx_tensor_desc* dx, void* tmp, size_t tmp_bytes,
+                                               size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

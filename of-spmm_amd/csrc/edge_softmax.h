@@ -1,7 +1,8 @@
 // edge_softmax.h — what the kCPU kernels (edge_softmax_cpu.cpp) and the HIP kernels
-// (edge_softmax.hip) of op "edge_softmax_csr" and of its gradient share: the exponential, the
-// constants of the sum's order and the argument checks of their C-ABI entries (contract in
-// include/ofx_spmm.h).
+// (edge_softmax.hip, edge_softmax_heads.hip) of ops "edge_softmax_csr", "edge_softmax_csr_heads"
+// and of their gradients share: the exponential, the constants of the sum's order, the argument
+// checks of their C-ABI entries and, for the HIP units, the device steps of a leaf, the lane-group
+// butterflies and the tile stack (contract in include/ofx_spmm.h).
 #ifndef OFX_EDGE_SOFTMAX_H_
 #define OFX_EDGE_SOFTMAX_H_
 
@@ -92,7 +93,141 @@ static inline int check_edge_softmax_args(const char* fn, int idx_dtype, int val
   return check_row_range(fn, row_begin, row_end, m);
 }
 
+// The multi-head entries (ops "edge_softmax_csr_heads" / "_grad"): e, y, g, de are T[nnz, heads].
+// int32 indices need only address the CSR itself; offsets into e are formed in 64 bits.
+static inline int check_edge_softmax_heads_args(const char* fn, int idx_dtype, int val_dtype,
+                                                int64_t m, int64_t heads, int64_t nnz,
+                                                int64_t row_begin, int64_t row_end) {
+  OFX_REQUIRE(heads >= 0 && (heads == 0 || nnz <= INT64_MAX / heads), OFX_EINVAL,
+              "%s: bad heads=%lld for nnz=%lld", fn, (long long)heads, (long long)nnz);
+  return check_edge_softmax_args(fn, idx_dtype, val_dtype, m, nnz, row_begin, row_end);
+}
+
 }  // namespace esm
 }  // namespace ofx
+
+#if defined(__HIP__)
+// ---- what the HIP units (edge_softmax.hip, edge_softmax_heads.hip) share on the device ----------
+// The steps of one row's leaf (kLeaf positions in a lane's registers), the lane-group butterflies
+// and the binary-counter stack of a long row's tiles.  Both units take every arithmetic step from
+// here, so a head's column has the single-head op's bits by construction.
+#include <hip/hip_runtime.h>
+
+namespace ofx {
+namespace esm {
+
+// The rounding to T of a quotient or product, as a step of its own: the value passes through a
+// register between the arithmetic and the conversion, so no mixed-precision multiply-convert
+// (spmm_extremum.h signed_product) can fuse the two roundings.  NaN: the canonical quiet NaN.
+template <typename T>
+__device__ __forceinline__ T store_rounded(typename Num<T>::acc v) {
+  v = canonical_nan(v);
+  if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(v));
+  return Num<T>::store(v);
+}
+
+template <typename A, int LG>
+__device__ __forceinline__ A group_max(A best) {
+#pragma unroll
+  for (int x = 1; x < LG; x <<= 1) {
+    const A o = __shfl_xor(best, x, 64);
+    best = better(o, best, true) ? o : best;
+  }
+  return best;
+}
+
+template <typename A, int LG>
+__device__ __forceinline__ A group_sum(A t) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int x = 1; x < LG; x <<= 1) t = t + __shfl_xor(t, x, 64);
+  return t;
+}
+
+template <typename A>
+__device__ __forceinline__ A leaf_max(const A (&x)[kLeaf], A best) {
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) best = better(x[i], best, true) ? x[i] : best;
+  return best;
+}
+
+// x <- exp_acc(x - m) at the leaf's positions inside the row, +0 at the others; the leaf's sum.
+template <typename A>
+__device__ __forceinline__ A leaf_exp_sum(A (&x)[kLeaf], A m, int64_t pos, int64_t len) {
+#pragma clang fp contract(off)
+  A s = A(0);
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) {
+    const A t = x[i] - m;
+    const A v = exp_acc<A>(t);
+    x[i] = pos + i < len ? v : A(0);
+    s = s + x[i];
+  }
+  return s;
+}
+
+// The backward's leaf sum of q = y * g (absent positions hold +0 in both).
+template <typename A>
+__device__ __forceinline__ A leaf_dot(const A (&y)[kLeaf], const A (&g)[kLeaf]) {
+#pragma clang fp contract(off)
+  A s = A(0);
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) {
+    const A q = y[i] * g[i];
+    s = s + q;
+  }
+  return s;
+}
+
+template <typename T>
+__device__ __forceinline__ void leaf_divide(const typename Num<T>::acc (&x)[kLeaf],
+                                            typename Num<T>::acc s, T (&y)[kLeaf]) {
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) y[i] = store_rounded<T>(x[i] / s);
+}
+
+template <typename T>
+__device__ __forceinline__ void leaf_grad(const typename Num<T>::acc (&y)[kLeaf],
+                                          const typename Num<T>::acc (&g)[kLeaf],
+                                          typename Num<T>::acc d, T (&de)[kLeaf]) {
+#pragma clang fp contract(off)
+  using A = typename Num<T>::acc;
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) {
+    const A diff = g[i] - d;
+    de[i] = store_rounded<T>(y[i] * diff);
+  }
+}
+
+// The binary-counter stack of tile values, level l in lane l.  Tile t (value v, the same in every
+// lane) merges with the levels of t's trailing one bits, earlier subtrees on the left.
+template <typename A>
+__device__ __forceinline__ void stack_push(A& stk, int64_t t, A v, int lane) {
+#pragma clang fp contract(off)
+  int l = 0;
+  for (; (t >> l) & 1; ++l) v = __shfl(stk, l, 64) + v;
+  if (lane == l) stk = v;
+}
+
+// The tree's root after `tiles` pushes: the occupied levels, low to high, the higher (earlier)
+// subtree on the left; the zero tiles that pad to a power of two add nothing.
+template <typename A>
+__device__ __forceinline__ A stack_fold(A stk, int64_t tiles) {
+#pragma clang fp contract(off)
+  A s = A(0);
+  bool have = false;
+  for (int l = 0; (tiles >> l) != 0; ++l) {
+    if ((tiles >> l) & 1) {
+      const A v = __shfl(stk, l, 64);
+      s = have ? v + s : v;
+      have = true;
+    }
+  }
+  return s;
+}
+
+}  // namespace esm
+}  // namespace ofx
+#endif  // __HIP__
 
 #endif  // OFX_EDGE_SOFTMAX_H_

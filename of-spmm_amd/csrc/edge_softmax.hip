@@ -88,16 +88,6 @@ __device__ __forceinline__ void load_leaf(const T* __restrict__ p, int64_t pos, 
   }
 }
 
-// The rounding to T of a quotient or product, as a step of its own: the value passes through a
-// register between the arithmetic and the conversion, so no mixed-precision multiply-convert
-// (spmm_extremum.h signed_product) can fuse the two roundings.  NaN: the canonical quiet NaN.
-template <typename T>
-__device__ __forceinline__ T store_rounded(typename Num<T>::acc v) {
-  v = canonical_nan(v);
-  if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(v));
-  return Num<T>::store(v);
-}
-
 template <typename T>
 __device__ __forceinline__ void store_leaf(T* __restrict__ p, int64_t pos, int64_t len,
                                            const T (&y)[kLeaf]) {
@@ -119,78 +109,8 @@ __device__ __forceinline__ void store_leaf(T* __restrict__ p, int64_t pos, int64
   }
 }
 
-template <typename A, int LG>
-__device__ __forceinline__ A group_max(A best) {
-#pragma unroll
-  for (int x = 1; x < LG; x <<= 1) {
-    const A o = __shfl_xor(best, x, 64);
-    best = better(o, best, true) ? o : best;
-  }
-  return best;
-}
-
-template <typename A, int LG>
-__device__ __forceinline__ A group_sum(A t) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int x = 1; x < LG; x <<= 1) t = t + __shfl_xor(t, x, 64);
-  return t;
-}
-
-template <typename A>
-__device__ __forceinline__ A leaf_max(const A (&x)[kLeaf], A best) {
-#pragma unroll
-  for (int i = 0; i < kLeaf; ++i) best = better(x[i], best, true) ? x[i] : best;
-  return best;
-}
-
-// x <- exp_acc(x - m) at the leaf's positions inside the row, +0 at the others; the leaf's sum.
-template <typename A>
-__device__ __forceinline__ A leaf_exp_sum(A (&x)[kLeaf], A m, int64_t pos, int64_t len) {
-#pragma clang fp contract(off)
-  A s = A(0);
-#pragma unroll
-  for (int i = 0; i < kLeaf; ++i) {
-    const A t = x[i] - m;
-    const A v = exp_acc<A>(t);
-    x[i] = pos + i < len ? v : A(0);
-    s = s + x[i];
-  }
-  return s;
-}
-
-// The backward's leaf sum of q = y * g (absent positions hold +0 in both).
-template <typename A>
-__device__ __forceinline__ A leaf_dot(const A (&y)[kLeaf], const A (&g)[kLeaf]) {
-#pragma clang fp contract(off)
-  A s = A(0);
-#pragma unroll
-  for (int i = 0; i < kLeaf; ++i) {
-    const A q = y[i] * g[i];
-    s = s + q;
-  }
-  return s;
-}
-
-template <typename T>
-__device__ __forceinline__ void leaf_divide(const typename Num<T>::acc (&x)[kLeaf],
-                                            typename Num<T>::acc s, T (&y)[kLeaf]) {
-#pragma unroll
-  for (int i = 0; i < kLeaf; ++i) y[i] = store_rounded<T>(x[i] / s);
-}
-
-template <typename T>
-__device__ __forceinline__ void leaf_grad(const typename Num<T>::acc (&y)[kLeaf],
-                                          const typename Num<T>::acc (&g)[kLeaf],
-                                          typename Num<T>::acc d, T (&de)[kLeaf]) {
-#pragma clang fp contract(off)
-  using A = typename Num<T>::acc;
-#pragma unroll
-  for (int i = 0; i < kLeaf; ++i) {
-    const A diff = g[i] - d;
-    de[i] = store_rounded<T>(y[i] * diff);
-  }
-}
+// The leaf steps, the butterflies and the tile stack are in edge_softmax.h (shared with
+// edge_softmax_heads.hip).
 
 // A row of at most 8 LG elements over a group of LG lanes, lane gl holding leaf gl.  len == 0:
 // nothing is loaded or stored (a group with no row, or whose row the wave takes over).
@@ -216,33 +136,6 @@ __device__ __forceinline__ void row_in_registers(const T* __restrict__ a, const 
     leaf_grad<T>(x, gg, d, res);
   }
   store_leaf<T>(out + j0, pos, len, res);
-}
-
-// The binary-counter stack of tile values, level l in lane l.  Tile t (value v, the same in every
-// lane) merges with the levels of t's trailing one bits, earlier subtrees on the left.
-template <typename A>
-__device__ __forceinline__ void stack_push(A& stk, int64_t t, A v, int lane) {
-#pragma clang fp contract(off)
-  int l = 0;
-  for (; (t >> l) & 1; ++l) v = __shfl(stk, l, 64) + v;
-  if (lane == l) stk = v;
-}
-
-// The tree's root after `tiles` pushes: the occupied levels, low to high, the higher (earlier)
-// subtree on the left; the zero tiles that pad to a power of two add nothing.
-template <typename A>
-__device__ __forceinline__ A stack_fold(A stk, int64_t tiles) {
-#pragma clang fp contract(off)
-  A s = A(0);
-  bool have = false;
-  for (int l = 0; (tiles >> l) != 0; ++l) {
-    if ((tiles >> l) & 1) {
-      const A v = __shfl(stk, l, 64);
-      s = have ? v + s : v;
-      have = true;
-    }
-  }
-  return s;
 }
 
 // A row of more than kTile elements, by the whole wave.

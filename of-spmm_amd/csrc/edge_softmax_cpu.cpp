@@ -1,6 +1,9 @@
-// edge_softmax_cpu.cpp — the DeviceType::kCPU kernels of op "edge_softmax_csr" and of its gradient
-// (contract in include/ofx_spmm.h, shared helpers in edge_softmax.h).  Row-parallel over OpenMP
-// like spmm_extremum_cpu.cpp; the same bits as the HIP kernels (edge_softmax.hip).
+// edge_softmax_cpu.cpp — the DeviceType::kCPU kernels of ops "edge_softmax_csr" and
+// "edge_softmax_csr_heads" and of their gradients (contract in include/ofx_spmm.h, shared helpers
+// in edge_softmax.h).  Row-parallel over OpenMP like spmm_extremum_cpu.cpp; the same bits as the
+// HIP kernels (edge_softmax.hip, edge_softmax_heads.hip).  The multi-head entries run the
+// single-head code on every column of e[nnz, heads] (element stride `heads`; 1 is the single-head
+// op), so a head has the single-head bits by construction.
 #pragma clang fp contract(off)
 
 #include <omp.h>
@@ -39,7 +42,8 @@ A tree_sum(const A* x, int64_t len, std::vector<A>& leaf) {
 }
 
 template <typename T, typename I>
-void cpu_forward(int nthreads, const I* rp, const T* e, T* y, int64_t row_begin, int64_t row_end) {
+void cpu_forward(int nthreads, const I* rp, const T* e, T* y, int64_t heads, int64_t row_begin,
+                 int64_t row_end) {
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
 #pragma omp parallel num_threads(nthreads)
@@ -49,28 +53,32 @@ void cpu_forward(int nthreads, const I* rp, const T* e, T* y, int64_t row_begin,
     for (int64_t r = row_begin; r < row_end; ++r) {
       const int64_t j0 = (int64_t)rp[r], len = (int64_t)rp[r + 1] - j0;
       if (len <= 0) continue;
-      A best = Num<T>::load(e[j0]);
-      for (int64_t p = 1; p < len; ++p) {
-        const A c = Num<T>::load(e[j0 + p]);
-        best = better(c, best, true) ? c : best;
-      }
       x.resize((size_t)len);
-      for (int64_t p = 0; p < len; ++p) {
-        const A t = Num<T>::load(e[j0 + p]) - best;
-        x[(size_t)p] = exp_acc<A>(t);
-      }
-      const A s = tree_sum(x.data(), len, leaf);
-      for (int64_t p = 0; p < len; ++p) {
-        const A q = x[(size_t)p] / s;
-        y[j0 + p] = Num<T>::store(canonical_nan(q));
+      for (int64_t h = 0; h < heads; ++h) {
+        const T* eh = e + j0 * heads + h;
+        T* yh = y + j0 * heads + h;
+        A best = Num<T>::load(eh[0]);
+        for (int64_t p = 1; p < len; ++p) {
+          const A c = Num<T>::load(eh[p * heads]);
+          best = better(c, best, true) ? c : best;
+        }
+        for (int64_t p = 0; p < len; ++p) {
+          const A t = Num<T>::load(eh[p * heads]) - best;
+          x[(size_t)p] = exp_acc<A>(t);
+        }
+        const A s = tree_sum(x.data(), len, leaf);
+        for (int64_t p = 0; p < len; ++p) {
+          const A q = x[(size_t)p] / s;
+          yh[p * heads] = Num<T>::store(canonical_nan(q));
+        }
       }
     }
   }
 }
 
 template <typename T, typename I>
-void cpu_backward(int nthreads, const I* rp, const T* y, const T* g, T* de, int64_t row_begin,
-                  int64_t row_end) {
+void cpu_backward(int nthreads, const I* rp, const T* y, const T* g, T* de, int64_t heads,
+                  int64_t row_begin, int64_t row_end) {
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
 #pragma omp parallel num_threads(nthreads)
@@ -81,15 +89,20 @@ void cpu_backward(int nthreads, const I* rp, const T* y, const T* g, T* de, int6
       const int64_t j0 = (int64_t)rp[r], len = (int64_t)rp[r + 1] - j0;
       if (len <= 0) continue;
       q.resize((size_t)len);
-      for (int64_t p = 0; p < len; ++p) {
-        const A prod = Num<T>::load(y[j0 + p]) * Num<T>::load(g[j0 + p]);
-        q[(size_t)p] = prod;
-      }
-      const A d = tree_sum(q.data(), len, leaf);
-      for (int64_t p = 0; p < len; ++p) {
-        const A diff = Num<T>::load(g[j0 + p]) - d;
-        const A prod = Num<T>::load(y[j0 + p]) * diff;
-        de[j0 + p] = Num<T>::store(canonical_nan(prod));
+      for (int64_t h = 0; h < heads; ++h) {
+        const T* yh = y + j0 * heads + h;
+        const T* gh = g + j0 * heads + h;
+        T* dh = de + j0 * heads + h;
+        for (int64_t p = 0; p < len; ++p) {
+          const A prod = Num<T>::load(yh[p * heads]) * Num<T>::load(gh[p * heads]);
+          q[(size_t)p] = prod;
+        }
+        const A d = tree_sum(q.data(), len, leaf);
+        for (int64_t p = 0; p < len; ++p) {
+          const A diff = Num<T>::load(gh[p * heads]) - d;
+          const A prod = Num<T>::load(yh[p * heads]) * diff;
+          dh[p * heads] = Num<T>::store(canonical_nan(prod));
+        }
       }
     }
   }
@@ -116,8 +129,8 @@ extern "C" int ofx_edge_softmax_csr_cpu(int num_threads, int idx_dtype, int val_
     return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
       using T = std::remove_pointer_t<decltype(tp)>;
       using I = std::remove_pointer_t<decltype(ip)>;
-      cpu_forward<T, I>(threads_of(num_threads), (const I*)row_ptr, (const T*)e, (T*)y, row_begin,
-                        row_end);
+      cpu_forward<T, I>(threads_of(num_threads), (const I*)row_ptr, (const T*)e, (T*)y, 1,
+                        row_begin, row_end);
       return OFX_OK;
     });
   });
@@ -139,7 +152,52 @@ extern "C" int ofx_edge_softmax_csr_grad_cpu(int num_threads, int idx_dtype, int
       using T = std::remove_pointer_t<decltype(tp)>;
       using I = std::remove_pointer_t<decltype(ip)>;
       cpu_backward<T, I>(threads_of(num_threads), (const I*)row_ptr, (const T*)y, (const T*)g,
-                         (T*)de, row_begin, row_end);
+                         (T*)de, 1, row_begin, row_end);
+      return OFX_OK;
+    });
+  });
+}
+
+extern "C" int ofx_edge_softmax_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype,
+                                              int64_t m, int64_t heads, int64_t nnz,
+                                              const void* row_ptr, const void* e, void* y,
+                                              int64_t row_begin, int64_t row_end,
+                                              const ofx_spmm_options* opts) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads_cpu");  // validated; no option has an effect
+    int rc = esm::check_edge_softmax_heads_args("edge_softmax_csr_heads_cpu", idx_dtype, val_dtype,
+                                                m, heads, nnz, row_begin, row_end);
+    if (rc) return rc;
+    if (row_end == row_begin || nnz == 0 || heads == 0) return OFX_OK;
+    OFX_REQUIRE(row_ptr && e && y, OFX_EINVAL, "edge_softmax_csr_heads_cpu: NULL pointer");
+    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+      using T = std::remove_pointer_t<decltype(tp)>;
+      using I = std::remove_pointer_t<decltype(ip)>;
+      cpu_forward<T, I>(threads_of(num_threads), (const I*)row_ptr, (const T*)e, (T*)y, heads,
+                        row_begin, row_end);
+      return OFX_OK;
+    });
+  });
+}
+
+extern "C" int ofx_edge_softmax_csr_heads_grad_cpu(int num_threads, int idx_dtype, int val_dtype,
+                                                   int64_t m, int64_t heads, int64_t nnz,
+                                                   const void* row_ptr, const void* y,
+                                                   const void* g, void* de, int64_t row_begin,
+                                                   int64_t row_end, const ofx_spmm_options* opts) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads_grad_cpu");
+    int rc = esm::check_edge_softmax_heads_args("edge_softmax_csr_heads_grad_cpu", idx_dtype,
+                                                val_dtype, m, heads, nnz, row_begin, row_end);
+    if (rc) return rc;
+    if (row_end == row_begin || nnz == 0 || heads == 0) return OFX_OK;
+    OFX_REQUIRE(row_ptr && y && g && de, OFX_EINVAL,
+                "edge_softmax_csr_heads_grad_cpu: NULL pointer");
+    return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+      using T = std::remove_pointer_t<decltype(tp)>;
+      using I = std::remove_pointer_t<decltype(ip)>;
+      cpu_backward<T, I>(threads_of(num_threads), (const I*)row_ptr, (const T*)y, (const T*)g,
+                         (T*)de, heads, row_begin, row_end);
       return OFX_OK;
     });
   });

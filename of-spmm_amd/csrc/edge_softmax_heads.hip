@@ -1,0 +1,435 @@
+// edge_softmax_heads.hip — ops "edge_softmax_csr_heads" and its gradient on gfx950: the scores
+// e T[nnz, H] of a CSR's nonzeros normalised over each row, every head on its own, in one launch
+// (contract in include/ofx_spmm.h, DESIGN.md §3f "Edge softmax with heads").  Every arithmetic
+// step is edge_softmax.hip's (the leaf steps, butterflies and tile stack of edge_softmax.h), so a
+// head's column has the single-head op's bits by construction.
+//
+// A work item is a (row, head group of V heads); item index = row * G + head group, G = H / V, so
+// the head groups of one row sit in adjacent lane groups of a wave and one load instruction covers
+// whole position records of H elements.  Lane t of the LG-lane group holds leaf t, positions
+// [8t, 8t + 8) of the row, for its V heads: 8 loads of V elements at stride H.  A position past the
+// row's end is clamped to the row's last one and its value replaced, so the 8 loads of a round are
+// unconditional.  Leaf maxima and sums run in the lane per head; the xor butterflies run on the V
+// values.  Stores are V elements wide and plain: a lane's 8 stores are 16-byte (8-byte) pieces of 8
+// different records, which L2 merges into lines; as non-temporal stores they cost the f32 H = 4
+// launch 8.59 ms instead of 6.89 ms forward and 5.87 instead of 3.61 ms backward.
+//   packed path:  H % V == 0 and every base aligned to the vector; V = 4 for f32 (16 bytes), 2 for
+//     f64 (16 bytes), 4 for f16 / bf16 (8 bytes: 8 heads a lane would double the registers)
+//   general path: any other H or base; V = 1, a work item is a (row, head), scalar loads and stores
+// LG is picked from the mean degree as the single-head op does.  A row longer than 8 LG is taken
+// over by the whole wave, one (row, head group) after another: up to kTile = 512 positions in
+// registers, beyond that in tiles of 64 leaves through a binary-counter stack of V values per
+// level.  One tile is in flight on the packed path (its 8 V accumulators per operand are a group
+// row's) and two on the general path: with the single-head kernel's four, whose 32 loads each
+// carry a 64-bit strided address, the general kernels needed 256 VGPRs and AGPR copies (one wave
+// per SIMD); with two on the packed path the f32 kernels take 233-256 VGPRs and measured slower
+// (DESIGN.md §3f).
+//
+// No atomics, no workspace, no allocation, no host synchronisation, no LDS, no scratch.
+#pragma clang fp contract(off)
+
+#include <hip/hip_runtime.h>
+
+#include "edge_softmax.h"
+#include "spmm_items_dev.h"
+
+namespace ofx {
+namespace {
+
+using namespace item;
+using namespace esm;
+
+// V consecutive heads of one position as one load or store.
+template <int BYTES>
+struct RawOf;
+template <>
+struct RawOf<2> {
+  using type = uint16_t;
+};
+template <>
+struct RawOf<4> {
+  using type = uint32_t;
+};
+template <>
+struct RawOf<8> {
+  using type = u32x2;
+};
+template <>
+struct RawOf<16> {
+  using type = u32x4;
+};
+
+template <typename T, int V>
+struct HeadVec {
+  using Raw = typename RawOf<V * sizeof(T)>::type;
+  struct Elems {
+    T v[V];
+  };
+  static_assert(sizeof(Elems) == sizeof(Raw), "a head vector is one load");
+};
+
+// Heads a lane holds on the packed path.
+template <typename T>
+constexpr int packed_heads() {
+  return sizeof(T) == 8 ? 2 : 4;
+}
+
+// x[v][i] = load(p[(pos + i) * H + v]) for the leaf's positions inside [0, len), `fill` for the
+// others; p points at the row's first position and the lane's first head.  len > 0.
+template <typename T, int V>
+__device__ __forceinline__ void load_leaf_heads(const T* __restrict__ p, int64_t H, int64_t pos,
+                                                int64_t len, typename Num<T>::acc fill,
+                                                typename Num<T>::acc (&x)[V][kLeaf]) {
+  using HV = HeadVec<T, V>;
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) {
+    const bool in = pos + i < len;
+    const int64_t q = in ? pos + i : len - 1;
+    const typename HV::Raw raw = *reinterpret_cast<const typename HV::Raw*>(p + q * H);
+    const typename HV::Elems el = __builtin_bit_cast(typename HV::Elems, raw);
+#pragma unroll
+    for (int v = 0; v < V; ++v) x[v][i] = in ? Num<T>::load(el.v[v]) : fill;
+  }
+}
+
+// The same for a group that may have no row (len == 0: nothing is loaded).
+template <typename T, int V>
+__device__ __forceinline__ void load_leaf_heads_or_fill(const T* __restrict__ p, int64_t H,
+                                                        int64_t pos, int64_t len,
+                                                        typename Num<T>::acc fill,
+                                                        typename Num<T>::acc (&x)[V][kLeaf]) {
+  if (len > 0) {
+    load_leaf_heads<T, V>(p, H, pos, len, fill, x);
+  } else {
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+#pragma unroll
+      for (int i = 0; i < kLeaf; ++i) x[v][i] = fill;
+  }
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void store_leaf_heads(T* __restrict__ p, int64_t H, int64_t pos,
+                                                 int64_t len, const T (&y)[V][kLeaf]) {
+  using HV = HeadVec<T, V>;
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) {
+    if (pos + i < len) {
+      typename HV::Elems el;
+#pragma unroll
+      for (int v = 0; v < V; ++v) el.v[v] = y[v][i];
+      *reinterpret_cast<typename HV::Raw*>(p + (pos + i) * H) =
+          __builtin_bit_cast(typename HV::Raw, el);
+    }
+  }
+}
+
+// A row of at most 8 LG positions over a group of LG lanes, lane gl holding leaf gl of V heads.
+// off: the element offset of the row's first position and the lane's first head.  len == 0:
+// nothing is loaded or stored (a group with no item, or whose row the wave takes over).
+// Forward: a = e, out = y.  Backward: a = y, g = the upstream gradient, out = de.
+template <typename T, int V, int LG, bool BWD>
+__device__ __forceinline__ void row_in_registers(const T* __restrict__ a, const T* __restrict__ g,
+                                                 T* __restrict__ out, int64_t H, int64_t off,
+                                                 int64_t len, int gl) {
+  using A = typename Num<T>::acc;
+  const int64_t pos = (int64_t)gl * kLeaf;
+  A x[V][kLeaf];
+  T res[V][kLeaf];
+  if constexpr (!BWD) {
+    load_leaf_heads_or_fill<T, V>(a + off, H, pos, len, -__builtin_huge_val(), x);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const A m = group_max<A, LG>(leaf_max<A>(x[v], x[v][0]));
+      const A s = group_sum<A, LG>(leaf_exp_sum<A>(x[v], m, pos, len));
+      leaf_divide<T>(x[v], s, res[v]);
+    }
+  } else {
+    A gg[V][kLeaf];
+    load_leaf_heads_or_fill<T, V>(a + off, H, pos, len, A(0), x);
+    load_leaf_heads_or_fill<T, V>(g + off, H, pos, len, A(0), gg);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const A d = group_sum<A, LG>(leaf_dot<A>(x[v], gg[v]));
+      leaf_grad<T>(x[v], gg[v], d, res[v]);
+    }
+  }
+  store_leaf_heads<T, V>(out + off, H, pos, len, res);
+}
+
+// A row of more than kTile positions, by the whole wave, for V heads; SW tiles in flight (the
+// number has no numeric effect: tiles are pushed in tile order).
+template <typename T, int V, bool BWD>
+__device__ __forceinline__ void row_in_tiles(const T* __restrict__ a, const T* __restrict__ g,
+                                             T* __restrict__ out, int64_t H, int64_t off,
+                                             int64_t len, int lane) {
+  using A = typename Num<T>::acc;
+  constexpr int SW = V == 1 ? 2 : 1;
+  const T* pa = a + off;
+  const T* pg = BWD ? g + off : nullptr;
+  T* po = out + off;
+  const int64_t tiles = (len + kTile - 1) / kTile;
+  const int64_t lpos = (int64_t)lane * kLeaf;
+  A m[V];
+  if constexpr (!BWD) {
+    A best[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) best[v] = -__builtin_huge_val();
+    for (int64_t t0 = 0; t0 < tiles; t0 += SW) {
+      A x[SW][V][kLeaf];
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) best[v] = leaf_max<A>(x[u][v], best[v]);
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) m[v] = group_max<A, 64>(best[v]);
+  }
+  A stk[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) stk[v] = A(0);
+  for (int64_t t0 = 0; t0 < tiles; t0 += SW) {
+    A x[SW][V][kLeaf], val[SW][V];
+    if constexpr (!BWD) {
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          val[u][v] = leaf_exp_sum<A>(x[u][v], m[v], (t0 + u) * kTile + lpos, len);
+    } else {
+      A gg[SW][V][kLeaf];
+#pragma unroll
+      for (int u = 0; u < SW; ++u) {
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, A(0), x[u]);
+        load_leaf_heads<T, V>(pg, H, (t0 + u) * kTile + lpos, len, A(0), gg[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) val[u][v] = leaf_dot<A>(x[u][v], gg[u][v]);
+    }
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+#pragma unroll
+      for (int v = 0; v < V; ++v) val[u][v] = group_sum<A, 64>(val[u][v]);
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+      if (t0 + u < tiles) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) stack_push<A>(stk[v], t0 + u, val[u][v], lane);
+      }
+  }
+  A s[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) s[v] = stack_fold<A>(stk[v], tiles);
+  for (int64_t t0 = 0; t0 < tiles; t0 += SW) {
+    A x[SW][V][kLeaf];
+    T res[SW][V][kLeaf];
+    if constexpr (!BWD) {
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          (void)leaf_exp_sum<A>(x[u][v], m[v], (t0 + u) * kTile + lpos, len);
+          leaf_divide<T>(x[u][v], s[v], res[u][v]);
+        }
+    } else {
+      A gg[SW][V][kLeaf];
+#pragma unroll
+      for (int u = 0; u < SW; ++u) {
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, A(0), x[u]);
+        load_leaf_heads<T, V>(pg, H, (t0 + u) * kTile + lpos, len, A(0), gg[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) leaf_grad<T>(x[u][v], gg[u][v], s[v], res[u][v]);
+    }
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+      store_leaf_heads<T, V>(po, H, (t0 + u) * kTile + lpos, len, res[u]);
+  }
+}
+
+template <typename T, int V, bool BWD>
+__device__ __forceinline__ void row_by_wave(const T* __restrict__ a, const T* __restrict__ g,
+                                            T* __restrict__ out, int64_t H, int64_t off,
+                                            int64_t len, int lane) {
+  if (len <= kTile)
+    row_in_registers<T, V, 64, BWD>(a, g, out, H, off, len, lane);
+  else
+    row_in_tiles<T, V, BWD>(a, g, out, H, off, len, lane);
+}
+
+// gi = row * G + head group, in 32 bits where both fit.
+__device__ __forceinline__ void split_item(int64_t gi, int64_t G, int64_t* row, int64_t* hg) {
+  if ((((uint64_t)gi | (uint64_t)G) >> 32) == 0) {
+    const uint32_t r = (uint32_t)gi / (uint32_t)G;
+    *row = r;
+    *hg = (uint32_t)gi - r * (uint32_t)G;
+  } else {
+    *row = gi / G;
+    *hg = gi - *row * G;
+  }
+}
+
+template <typename T, typename I, int V, int LG, bool BWD>
+__global__ void __launch_bounds__(kBlock)
+    edge_softmax_heads_kernel(const I* __restrict__ rp, const T* __restrict__ a,
+                              const T* __restrict__ g, T* __restrict__ out, int64_t row_begin,
+                              int64_t H, int64_t G, int64_t items, int64_t block_base) {
+#pragma clang fp contract(off)
+  constexpr int GPW = 64 / LG;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t gi = ((block_base + (int64_t)blockIdx.x) * (kBlock / 64) + wave) * GPW + lane / LG;
+  int64_t off = 0, len = 0;
+  if (gi < items) {
+    int64_t row, hg;
+    split_item(gi, G, &row, &hg);
+    const int64_t j0 = (int64_t)rp[row_begin + row];
+    len = (int64_t)rp[row_begin + row + 1] - j0;
+    off = j0 * H + hg * V;
+  }
+  if constexpr (LG == 64) {
+    row_by_wave<T, V, BWD>(a, g, out, H, off, len, lane);  // uniform over the wave
+  } else {
+    const bool fits = len <= (int64_t)LG * kLeaf;
+    row_in_registers<T, V, LG, BWD>(a, g, out, H, off, fits ? len : 0, lane & (LG - 1));
+    // the items whose row does not fit their group: the whole wave, one after another
+    unsigned long long todo = __ballot(!fits && (lane & (LG - 1)) == 0);
+    while (todo != 0) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int64_t woff = __shfl(off, src, 64), wlen = __shfl(len, src, 64);
+      row_by_wave<T, V, BWD>(a, g, out, H, woff, wlen, lane);
+    }
+  }
+}
+
+struct EsmHeadsArgs {
+  hipStream_t s;
+  const void *rp, *a, *g;
+  void* out;
+  int64_t m, heads, nnz, row_begin, nrows;
+  const ofx_spmm_options* opts;
+};
+
+template <typename T, typename I, int V, int LG, bool BWD>
+int esmh_cfg(const EsmHeadsArgs& x) {
+  const int64_t G = x.heads / V;
+  const int64_t items = x.nrows * G;
+  return launch_cut_grid(items, (kBlock / 64) * (64 / LG), [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL((edge_softmax_heads_kernel<T, I, V, LG, BWD>), grid, dim3(kBlock), 0, x.s,
+                       static_cast<const I*>(x.rp), static_cast<const T*>(x.a),
+                       static_cast<const T*>(x.g), static_cast<T*>(x.out), x.row_begin, x.heads, G,
+                       items, b0);
+  });
+}
+
+// The lane group of a launch, by the single-head op's rule (edge_softmax.hip esm_width): the
+// narrowest whose capacity (8 LG) is at least twice the mean degree of the launch's rows.  Speed
+// only: the bits do not depend on it.
+template <typename T, typename I, int V, bool BWD>
+int esmh_width(const EsmHeadsArgs& x) {
+  const int64_t est = launch_nnz(x.m, x.nrows, x.nnz, x.opts);
+  const int64_t want = 2 * (est / x.nrows);
+  if (want <= 1 * kLeaf) return esmh_cfg<T, I, V, 1, BWD>(x);
+  if (want <= 4 * kLeaf) return esmh_cfg<T, I, V, 4, BWD>(x);
+  if (want <= 16 * kLeaf) return esmh_cfg<T, I, V, 16, BWD>(x);
+  return esmh_cfg<T, I, V, 64, BWD>(x);
+}
+
+template <typename T, typename I, bool BWD>
+int esmh_typed(const EsmHeadsArgs& x) {
+  constexpr int V = packed_heads<T>();
+  constexpr uintptr_t kVecBytes = V * sizeof(T);
+  const bool packed = x.heads % V == 0 && (uintptr_t)x.a % kVecBytes == 0 &&
+                      (uintptr_t)x.out % kVecBytes == 0 && (!BWD || (uintptr_t)x.g % kVecBytes == 0);
+  return packed ? esmh_width<T, I, V, BWD>(x) : esmh_width<T, I, 1, BWD>(x);
+}
+
+template <bool BWD>
+int esmh_entry(const char* fn, void* stream, int idx_dtype, int val_dtype, int64_t m,
+               int64_t heads, int64_t nnz, const void* row_ptr, const void* a, const void* g,
+               void* out, int64_t row_begin, int64_t row_end, const ofx_spmm_options* opts) {
+  int rc =
+      check_edge_softmax_heads_args(fn, idx_dtype, val_dtype, m, heads, nnz, row_begin, row_end);
+  if (rc) return rc;
+  if (row_end == row_begin || nnz == 0 || heads == 0) return OFX_OK;
+  OFX_REQUIRE(row_ptr && a && out && (!BWD || g), OFX_EINVAL, "%s: NULL pointer", fn);
+  OFX_REQUIRE(row_end - row_begin <= INT64_MAX / heads, OFX_EINVAL, "%s: bad heads=%lld", fn,
+              (long long)heads);
+  if (heads == 1) {  // the single-head kernels: the same bits by the contract, contiguous leaves
+    return BWD ? ofx_edge_softmax_csr_grad(stream, idx_dtype, val_dtype, m, nnz, row_ptr, a, g,
+                                           out, row_begin, row_end, nullptr, 0, opts)
+               : ofx_edge_softmax_csr(stream, idx_dtype, val_dtype, m, nnz, row_ptr, a, out,
+                                      row_begin, row_end, nullptr, 0, opts);
+  }
+  const EsmHeadsArgs x{static_cast<hipStream_t>(stream), row_ptr, a, g, out, m, heads, nnz,
+                       row_begin, row_end - row_begin, opts};
+  return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
+    return esmh_typed<std::remove_pointer_t<decltype(tp)>, std::remove_pointer_t<decltype(ip)>,
+                      BWD>(x);
+  });
+}
+
+}  // namespace
+}  // namespace ofx
+
+using namespace ofx;
+
+extern "C" int ofx_edge_softmax_csr_heads_workspace_size(int idx_dtype, int val_dtype, int64_t m,
+                                                         int64_t heads, int64_t nnz,
+                                                         const ofx_spmm_options* opts,
+                                                         size_t* bytes) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads_workspace_size");
+    OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "edge_softmax_csr_heads_workspace_size: NULL bytes");
+    if (const int rc = check_edge_softmax_heads_args("edge_softmax_csr_heads_workspace_size",
+                                                     idx_dtype, val_dtype, m, heads, nnz, 0, m))
+      return rc;
+    *bytes = 0;  // no plan, no partials
+    return OFX_OK;
+  });
+}
+
+extern "C" int ofx_edge_softmax_csr_heads(void* stream, int idx_dtype, int val_dtype, int64_t m,
+                                          int64_t heads, int64_t nnz, const void* row_ptr,
+                                          const void* e, void* y, int64_t row_begin,
+                                          int64_t row_end, void* workspace, size_t workspace_bytes,
+                                          const ofx_spmm_options* opts) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_TAKE_DEVICE_ERROR("edge_softmax_csr_heads");  // an earlier launch's loud failure
+    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads");
+    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
+                "edge_softmax_csr_heads: NULL workspace of %zu bytes", workspace_bytes);
+    return esmh_entry<false>("edge_softmax_csr_heads", stream, idx_dtype, val_dtype, m, heads, nnz,
+                             row_ptr, e, nullptr, y, row_begin, row_end, opts);
+  });
+}
+
+extern "C" int ofx_edge_softmax_csr_heads_grad(void* stream, int idx_dtype, int val_dtype,
+                                               int64_t m, int64_t heads, int64_t nnz,
+                                               const void* row_ptr, const void* y, const void* g,
+                                               void* de, int64_t row_begin, int64_t row_end,
+                                               void* workspace, size_t workspace_bytes,
+                                               const ofx_spmm_options* opts) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_TAKE_DEVICE_ERROR("edge_softmax_csr_heads_grad");
+    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads_grad");
+    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
+                "edge_softmax_csr_heads_grad: NULL workspace of %zu bytes", workspace_bytes);
+    return esmh_entry<true>("edge_softmax_csr_heads_grad", stream, idx_dtype, val_dtype, m, heads,
+                            nnz, row_ptr, y, g, de, row_begin, row_end, opts);
+  });
+}

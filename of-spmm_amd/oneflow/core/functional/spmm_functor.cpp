@@ -884,3 +884,53 @@ extern "C" int ofx_functional_sddmm_csr_heads(void* stream, const ofx_tensor_des
                               tmp_size_out));
   });
 }
+
+// ---- functional::EdgeSoftmaxCsrHeads and its gradient functor -----------------------------------
+// Ops "edge_softmax_csr_heads" and "edge_softmax_csr_heads_grad"
+// (oneflow/user/ops/edge_softmax_heads_op.cpp) through the same op-registry dispatch
+// (INTEGRATION.md §11).
+namespace oneflow {
+
+int EdgeSoftmaxCsrHeads(void* stream, const ofx_tensor_desc* row_ptr,
+                        const ofx_tensor_desc* col_idx, const ofx_tensor_desc* in,
+                        const ofx_tensor_desc* grad, ofx_tensor_desc* out, void* tmp,
+                        size_t tmp_bytes, size_t* tmp_size_out, int num_threads) {
+  // an earlier launch's loud failure comes back here as OFX_EPLAN (as for spmm_csr)
+  if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("edge_softmax_csr_heads");
+  if (grad == nullptr)
+    return ToStatus(RunUserOp("edge_softmax_csr_heads",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"e", in}},
+                              {{"out", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                              num_threads));
+  return ToStatus(RunUserOp("edge_softmax_csr_heads_grad",
+                            {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"y", in},
+                             {"dy", grad}},
+                            {{"dx", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                            num_threads));
+}
+
+}  // namespace oneflow
+
+extern "C" int ofx_functional_edge_softmax_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                                     const ofx_tensor_desc* col_idx,
+                                                     const ofx_tensor_desc* e, ofx_tensor_desc* out,
+                                                     void* tmp, size_t tmp_bytes,
+                                                     size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(e != nullptr, OFX_EINVAL, "edge_softmax_csr_heads: NULL input e");
+    return EdgeSoftmaxCsrHeads(stream, row_ptr, col_idx, e, nullptr, out, tmp, tmp_bytes,
+                               tmp_size_out, 0);
+  });
+}
+
+extern "C" int ofx_functional_edge_softmax_csr_heads_grad(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* y, const ofx_tensor_desc* dy, ofx_tensor_desc* dx, void* tmp,
+    size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(y != nullptr && dy != nullptr, OFX_EINVAL,
+                "edge_softmax_csr_heads_grad: NULL input y or dy");
+    return EdgeSoftmaxCsrHeads(stream, row_ptr, col_idx, y, dy, dx, tmp, tmp_bytes, tmp_size_out,
+                               0);
+  });
+}

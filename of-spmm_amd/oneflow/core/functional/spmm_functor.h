@@ -36,6 +36,13 @@ int EdgeSoftmaxCsr(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tenso
                    const ofx_tensor_desc* in, const ofx_tensor_desc* grad, ofx_tensor_desc* out,
                    void* tmp, size_t tmp_bytes, size_t* tmp_size_out, int num_threads);
 
+// functional::EdgeSoftmaxCsrHeads / EdgeSoftmaxCsrHeadsGrad: the same for ops
+// "edge_softmax_csr_heads" (in = e [nnz, H]) and "edge_softmax_csr_heads_grad" (in = y, grad = dy).
+int EdgeSoftmaxCsrHeads(void* stream, const ofx_tensor_desc* row_ptr,
+                        const ofx_tensor_desc* col_idx, const ofx_tensor_desc* in,
+                        const ofx_tensor_desc* grad, ofx_tensor_desc* out, void* tmp,
+                        size_t tmp_bytes, size_t* tmp_size_out, int num_threads);
+
 }  // namespace oneflow
 
 #endif  // OFX_ONEFLOW_CORE_FUNCTIONAL_SPMM_FUNCTOR_H_

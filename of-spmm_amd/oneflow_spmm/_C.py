@@ -515,6 +515,64 @@ def sddmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a:
     return out
 
 
+def _edge_softmax_heads_inputs(op, rp, ci, named):
+    """The shape and dtype checks the two multi-head edge-softmax ops share, ahead of the op
+    layer's own; `named`: the [nnz, H] value tensors."""
+    first = named[0][1]
+    for name, t in named:
+        if t.dim() != 2:
+            raise RuntimeError(f"{op}: {name} should be 2-D [nnz, heads], got shape "
+                               f"{tuple(t.shape)}")
+        if t.shape[0] != ci.numel():
+            raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} rows (as "
+                               f"a_csr_col_idx), got {t.shape[0]}")
+        if t.shape[1] != first.shape[1]:
+            raise RuntimeError(f"{op}: {name} should have the number of heads of {named[0][0]} "
+                               f"({t.shape[1]} vs {first.shape[1]})")
+    if rp.dtype != ci.dtype:
+        raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
+                        f"({ci.dtype} vs {rp.dtype})")
+    dtype_code(rp.dtype)
+    if first.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {first.dtype}")
+    for name, t in named[1:]:
+        if t.dtype != first.dtype:
+            raise TypeError(f"{op}: {name} datatype should be equal to {named[0][0]}")
+
+
+def edge_softmax_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                           e: torch.Tensor, *, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "edge_softmax_csr_heads": out[j, h] = softmax of the scores e[:, h] over the nonzeros of
+    j's row, for e [nnz, H] (sddmm_csr_heads's output; a non-contiguous e is copied first).  One
+    launch for all heads; every head has the bits of edge_softmax_csr on its column (contract in
+    include/ofx_spmm.h).  `out`: a contiguous [nnz, H] tensor, written directly."""
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    e = _prep(e, "e")
+    _edge_softmax_heads_inputs("edge_softmax_csr_heads", rp, ci, [("e", e)])
+    if out is None:
+        out = torch.empty_like(e)
+    else:
+        _check_out("edge_softmax_csr_heads", out, e.shape, e, contiguous=True)
+    if out.numel() == 0:
+        return out
+    _run_grad_op(LIB.ofx_functional_edge_softmax_csr_heads, e, [rp, ci, e], [out], [])
+    return out
+
+
+def edge_softmax_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                                y: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """Op "edge_softmax_csr_heads_grad": dx[j, h] = y[j, h] * (dy[j, h] - sum over j's row of
+    y[:, h] * dy[:, h]) for y, dy [nnz, H], from the forward's stored y; one launch."""
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    y, dy = _prep(y, "y"), _prep(dy, "dy")
+    _edge_softmax_heads_inputs("edge_softmax_csr_heads_grad", rp, ci, [("y", y), ("dy", dy)])
+    dx = torch.empty_like(y)
+    if dx.numel() == 0:
+        return dx
+    _run_grad_op(LIB.ofx_functional_edge_softmax_csr_heads_grad, y, [rp, ci, y, dy], [dx], [])
+    return dx
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

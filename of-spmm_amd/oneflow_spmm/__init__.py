@@ -9,7 +9,7 @@
     y = flow_spmm.edge_softmax(row_ptr, col_idx, e)    # softmax of per-edge scores over each row
 Multi-head graph attention (q, k, v as [rows, H, D]; scores and weights as [nnz, H]):
     e = flow_spmm.sddmm(row_ptr, col_idx, q, k)        # [nnz, H], one launch for all heads
-    w = flow_spmm.edge_softmax(row_ptr, col_idx, e)    # per-head composition (H launches)
+    w = flow_spmm.edge_softmax(row_ptr, col_idx, e)    # [nnz, H], one launch for all heads
     out = flow_spmm.spmm(row_ptr, col_idx, w, M, K, v) # [M, H, D], one launch for all heads
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.

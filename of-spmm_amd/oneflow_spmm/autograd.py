@@ -325,6 +325,33 @@ class EdgeSoftmaxFunction(torch.autograd.Function):
         return None, None, _C.edge_softmax_csr_grad(row_ptr, col_idx, y, d_y.contiguous())
 
 
+class EdgeSoftmaxHeadsFunction(torch.autograd.Function):
+    """y = edge_softmax(row_ptr, e) for e [nnz, H], differentiable in e.  The output is saved and
+    the backward is one launch of op "edge_softmax_csr_heads_grad" on it."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, e):
+        y = _C.edge_softmax_csr_heads(row_ptr, col_idx, e)
+        ctx.save_for_backward(row_ptr, col_idx, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        row_ptr, col_idx, y = ctx.saved_tensors
+        return None, None, _C.edge_softmax_csr_heads_grad(row_ptr, col_idx, y, d_y.contiguous())
+
+
+def _edge_softmax_heads_composed(a_csr_row_ptr, a_csr_col_idx, e):
+    """The multi-head edge softmax as a per-head composition of the single-head op: one contiguous
+    column per head through `edge_softmax`, the results stacked back (H launches and H column
+    copies each way).  What the 2-D `edge_softmax` was before op "edge_softmax_csr_heads"; kept as
+    the comparison object of the tests and of scripts/edge_softmax_heads_bench.py."""
+    if e.shape[1] == 0:
+        return torch.empty_like(e)
+    return torch.stack([edge_softmax(a_csr_row_ptr, a_csr_col_idx, e[:, h].contiguous())
+                        for h in range(e.shape[1])], dim=1)
+
+
 def edge_softmax(a_csr_row_ptr, a_csr_col_idx, e, *, out=None):
     """The scores e [nnz] of a CSR's nonzeros normalised over each row:
     y[j] = exp(e[j] - max_row) / sum over j's row of exp(e - max_row) (DGL's edge_softmax, PyG's
@@ -334,19 +361,17 @@ def edge_softmax(a_csr_row_ptr, a_csr_col_idx, e, *, out=None):
     recorded.
 
     Multi-head scores e [nnz, H] (the output of the 3-D `sddmm`) give y [nnz, H], each head
-    normalised on its own.  This is a COMPOSITION, not a kernel: one contiguous column per head
-    goes through the single-head op and the results are stacked back, so it costs H launches and
-    H column copies each way; a native multi-head kernel is a follow-up.  Every head has the bits
-    of the 1-D call on its column."""
+    normalised on its own, in one launch forward and one backward (op "edge_softmax_csr_heads");
+    a non-contiguous e or upstream gradient is made contiguous first, `out=` (a contiguous
+    [nnz, H] tensor) is written directly.  Every head has the bits of the 1-D call on its
+    column."""
     if e.dim() == 2:
-        if out is not None and torch.is_grad_enabled() and e.requires_grad:
-            raise RuntimeError("edge_softmax: out= is not supported when gradients are required")
-        y = torch.stack([edge_softmax(a_csr_row_ptr, a_csr_col_idx, e[:, h].contiguous())
-                         for h in range(e.shape[1])], dim=1) if e.shape[1] else torch.empty_like(e)
-        if out is not None:
-            out.copy_(y)
-            return out
-        return y
+        if torch.is_grad_enabled() and e.requires_grad:
+            if out is not None:
+                raise RuntimeError(
+                    "edge_softmax: out= is not supported when gradients are required")
+            return EdgeSoftmaxHeadsFunction.apply(a_csr_row_ptr, a_csr_col_idx, e)
+        return _C.edge_softmax_csr_heads(a_csr_row_ptr, a_csr_col_idx, e, out=out)
     if torch.is_grad_enabled() and e.requires_grad:
         if out is not None:
             raise RuntimeError("edge_softmax: out= is not supported when gradients are required")
@@ -489,4 +514,4 @@ def fused_spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_col
 __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm", "TRANSPOSE_CACHE", "ops",
            "FusedSpmmCsrFunction", "fused_spmm", "SpmmCsrReduceFunction", "spmm_reduce",
            "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax", "SpmmCsrHeadsFunction",
-           "SddmmCsrHeadsFunction"]
+           "SddmmCsrHeadsFunction", "EdgeSoftmaxHeadsFunction"]
