@@ -561,6 +561,65 @@ int ofx_edge_softmax_csr_heads_grad_cpu(int num_threads, int idx_dtype, int val_
                                         const void* y, const void* g, void* de, int64_t row_begin,
                                         int64_t row_end, const ofx_spmm_options* opts);
 
+/* ---- fused multi-head graph attention (op "graph_attention_csr_heads") ----------
+ * Dot-product attention over a CSR as one op: q T[m, H*D] (stride ldq), k and v T[K, H*D]
+ * (strides ldk, ldv), head h in columns [h*D, (h+1)*D); out T[m, H*D] (stride ldo) and
+ * attn T[nnz, H], row-major and contiguous.
+ *
+ * Rule: attn has exactly the bits of ofx_edge_softmax_csr_heads applied to the output of
+ * ofx_sddmm_csr_heads(q, k), and out exactly the bits of ofx_spmm_csr_heads(values = attn, b = v)
+ * under the same opts.  Everything those three contracts say carries over unchanged: the SDDMM's
+ * 8-column leaves and per-head zero-padded pairwise tree, rounded to T; the row maximum with the
+ * max rule, exp_acc, the softmax's 8-position leaves and tree along the row, one IEEE division,
+ * the canonical NaN and the rounding to T; the SpMM's multiply-then-add with no contraction and
+ * its hub schedule, split and chunk resolved from D (not H*D), each hub chunk summed from +0, the
+ * partials added in chunk order, the last chunk taking the remainder.  Columns outside [0, k)
+ * behave as in the two gathers' contracts (a zero row).  There is no scale factor: scale q.
+ * heads == 1 gives the single-head composition's bits.  An empty row writes +0 to out and nothing
+ * to attn.  heads == 0, nnz == 0 or an empty row range returns OFX_OK, and what the composition
+ * would write (zeros in out for the rows of a range with nnz == 0) is still written.
+ *
+ * Row range [row_begin, row_end): q and out hold the rows from row_begin on; attn is written at
+ * the global positions [row_ptr[row_begin]*H, row_ptr[row_end]*H).  Offsets are formed in 64 bits.
+ * attn is always a caller-provided buffer, distinct from every input and from out (NULL or an
+ * overlap is OFX_EINVAL): it is the kernel's hand-off buffer between its phases and a result.
+ * planned != 0 or variant != 0 is OFX_EINVAL, as for ofx_spmm_csr_heads; d <= 2048
+ * (OFX_EUNSUPPORTED beyond), as for the SDDMM.
+ *
+ * Launches and workspace of the device version.  A row of at most `split` nonzeros (the hub
+ * threshold of ofx_spmm_csr_heads under the same opts: 512 at d <= 128) goes through scores,
+ * softmax and aggregation inside ONE kernel.  A longer row (a hub) does not: the shared planner
+ * (as in ofx_spmm_csr_heads) cuts it into the contract's chunks, the main kernel forms the
+ * chunks' scores, and three small launches follow on the same stream (the hubs' softmax, the
+ * chunks' partial sums, their addition in chunk order).  So a call is 1 launch when no row of the
+ * problem can be a hub and the row count is below the planner's binning threshold, else the plan
+ * launch, the main kernel and, where hubs are possible, the three hub launches.  The workspace
+ * holds the planner's work list and the chunks' partials in the accumulation type: query its size
+ * (0 when no plan is needed; it is that of ofx_spmm_csr_heads for the same problem) and pass a
+ * buffer of at least that size.  A smaller one, or a NULL workspace with a non-zero size, returns
+ * OFX_EWORKSPACE before anything is launched.  Asynchronous on `stream`, no atomics on the
+ * outputs, no allocation, no host synchronisation, capturable in a graph.  A work list that is
+ * not valid fills out and attn with the canonical NaN and the next entry returns OFX_EPLAN, as for
+ * the other planned ops.  HIP kernel, kCPU kernel and the composition give the same bits.       */
+int ofx_graph_attention_csr_heads_workspace_size(int idx_dtype, int val_dtype, int64_t m,
+                                                 int64_t k, int64_t heads, int64_t d, int64_t nnz,
+                                                 const ofx_spmm_options* opts, size_t* bytes);
+int ofx_graph_attention_csr_heads(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                  int64_t heads, int64_t d, int64_t nnz, const void* row_ptr,
+                                  const void* col_idx, const void* q, int64_t ldq, const void* kmat,
+                                  int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
+                                  void* attn /* [nnz, heads] */, int64_t row_begin,
+                                  int64_t row_end, void* workspace, size_t workspace_bytes,
+                                  const ofx_spmm_options* opts);
+/* kCPU version: host pointers, synchronous, the same bits (the three kCPU kernels in sequence). */
+int ofx_graph_attention_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                      int64_t k, int64_t heads, int64_t d, int64_t nnz,
+                                      const void* row_ptr, const void* col_idx, const void* q,
+                                      int64_t ldq, const void* kmat, int64_t ldk, const void* v,
+                                      int64_t ldv, void* out, int64_t ldo, void* attn,
+                                      int64_t row_begin, int64_t row_end,
+                                      const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -968,6 +1027,14 @@ int ofx_functional_sddmm_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
                                    const ofx_tensor_desc* b, int64_t num_heads,
                                    ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
                                    size_t* tmp_size_out);
+/* functional::GraphAttentionCsrHeads: op "graph_attention_csr_heads" (row_ptr [M+1], col_idx
+ * [nnz], q [M, H*D], k and v [K, H*D] -> out [M, H*D], attn [nnz, H]).                          */
+int ofx_functional_graph_attention_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                             const ofx_tensor_desc* col_idx,
+                                             const ofx_tensor_desc* q, const ofx_tensor_desc* k,
+                                             const ofx_tensor_desc* v, int64_t num_heads,
+                                             ofx_tensor_desc* out, ofx_tensor_desc* attn,
+                                             void* tmp, size_t tmp_bytes, size_t* tmp_size_out);
 /* functional::EdgeSoftmaxCsrHeads / EdgeSoftmaxCsrHeadsGrad: ops "edge_softmax_csr_heads"
  * (row_ptr [M+1], col_idx [nnz] for its shape only, e [nnz, H] -> out [nnz, H]) and
  * "edge_softmax_csr_heads_grad" (y, dy [nnz, H] -> dx [nnz, H]) of

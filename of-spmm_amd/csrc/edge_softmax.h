@@ -113,6 +113,8 @@ static inline int check_edge_softmax_heads_args(const char* fn, int idx_dtype, i
 // here, so a head's column has the single-head op's bits by construction.
 #include <hip/hip_runtime.h>
 
+#include "spmm_items_dev.h"
+
 namespace ofx {
 namespace esm {
 
@@ -226,7 +228,249 @@ __device__ __forceinline__ A stack_fold(A stk, int64_t tiles) {
   return s;
 }
 
+// ---- the multi-head rows (edge_softmax_heads.hip, phase 2 of graph_attention_heads.hip) ---------
+// Pointers are not restrict-qualified: the fused attention kernel normalises its scores in place
+// (a == out; every position is read and written by the same lane, reads first).
 }  // namespace esm
+
+namespace esmh {  // a namespace of its own: edge_softmax.hip has single-head steps of the same names
+
+using namespace esm;
+using item::u32x2;
+using item::u32x4;
+
+// V consecutive heads of one position as one load or store.
+template <int BYTES>
+struct RawOf;
+template <>
+struct RawOf<2> {
+  using type = uint16_t;
+};
+template <>
+struct RawOf<4> {
+  using type = uint32_t;
+};
+template <>
+struct RawOf<8> {
+  using type = u32x2;
+};
+template <>
+struct RawOf<16> {
+  using type = u32x4;
+};
+
+template <typename T, int V>
+struct HeadVec {
+  using Raw = typename RawOf<V * sizeof(T)>::type;
+  struct Elems {
+    T v[V];
+  };
+  static_assert(sizeof(Elems) == sizeof(Raw), "a head vector is one load");
+};
+
+// Heads a lane holds on the packed path.
+template <typename T>
+constexpr int packed_heads() {
+  return sizeof(T) == 8 ? 2 : 4;
+}
+
+// x[v][i] = load(p[(pos + i) * H + v]) for the leaf's positions inside [0, len), `fill` for the
+// others; p points at the row's first position and the lane's first head.  len > 0.
+template <typename T, int V>
+__device__ __forceinline__ void load_leaf_heads(const T* p, int64_t H, int64_t pos,
+                                                int64_t len, typename Num<T>::acc fill,
+                                                typename Num<T>::acc (&x)[V][kLeaf]) {
+  using HV = HeadVec<T, V>;
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) {
+    const bool in = pos + i < len;
+    const int64_t q = in ? pos + i : len - 1;
+    const typename HV::Raw raw = *reinterpret_cast<const typename HV::Raw*>(p + q * H);
+    const typename HV::Elems el = __builtin_bit_cast(typename HV::Elems, raw);
+#pragma unroll
+    for (int v = 0; v < V; ++v) x[v][i] = in ? Num<T>::load(el.v[v]) : fill;
+  }
+}
+
+// The same for a group that may have no row (len == 0: nothing is loaded).
+template <typename T, int V>
+__device__ __forceinline__ void load_leaf_heads_or_fill(const T* p, int64_t H,
+                                                        int64_t pos, int64_t len,
+                                                        typename Num<T>::acc fill,
+                                                        typename Num<T>::acc (&x)[V][kLeaf]) {
+  if (len > 0) {
+    load_leaf_heads<T, V>(p, H, pos, len, fill, x);
+  } else {
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+#pragma unroll
+      for (int i = 0; i < kLeaf; ++i) x[v][i] = fill;
+  }
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void store_leaf_heads(T* p, int64_t H, int64_t pos,
+                                                 int64_t len, const T (&y)[V][kLeaf]) {
+  using HV = HeadVec<T, V>;
+#pragma unroll
+  for (int i = 0; i < kLeaf; ++i) {
+    if (pos + i < len) {
+      typename HV::Elems el;
+#pragma unroll
+      for (int v = 0; v < V; ++v) el.v[v] = y[v][i];
+      *reinterpret_cast<typename HV::Raw*>(p + (pos + i) * H) =
+          __builtin_bit_cast(typename HV::Raw, el);
+    }
+  }
+}
+
+// A row of at most 8 LG positions over a group of LG lanes, lane gl holding leaf gl of V heads.
+// off: the element offset of the row's first position and the lane's first head.  len == 0:
+// nothing is loaded or stored (a group with no item, or whose row the wave takes over).
+// Forward: a = e, out = y.  Backward: a = y, g = the upstream gradient, out = de.
+template <typename T, int V, int LG, bool BWD>
+__device__ __forceinline__ void row_in_registers(const T* a, const T* g,
+                                                 T* out, int64_t H, int64_t off,
+                                                 int64_t len, int gl) {
+  using A = typename Num<T>::acc;
+  const int64_t pos = (int64_t)gl * kLeaf;
+  A x[V][kLeaf];
+  T res[V][kLeaf];
+  if constexpr (!BWD) {
+    load_leaf_heads_or_fill<T, V>(a + off, H, pos, len, -__builtin_huge_val(), x);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const A m = group_max<A, LG>(leaf_max<A>(x[v], x[v][0]));
+      const A s = group_sum<A, LG>(leaf_exp_sum<A>(x[v], m, pos, len));
+      leaf_divide<T>(x[v], s, res[v]);
+    }
+  } else {
+    A gg[V][kLeaf];
+    load_leaf_heads_or_fill<T, V>(a + off, H, pos, len, A(0), x);
+    load_leaf_heads_or_fill<T, V>(g + off, H, pos, len, A(0), gg);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const A d = group_sum<A, LG>(leaf_dot<A>(x[v], gg[v]));
+      leaf_grad<T>(x[v], gg[v], d, res[v]);
+    }
+  }
+  store_leaf_heads<T, V>(out + off, H, pos, len, res);
+}
+
+// A row of more than kTile positions, by the whole wave, for V heads; SW tiles in flight (the
+// number has no numeric effect: tiles are pushed in tile order).
+template <typename T, int V, bool BWD>
+__device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
+                                             T* out, int64_t H, int64_t off,
+                                             int64_t len, int lane) {
+  using A = typename Num<T>::acc;
+  constexpr int SW = V == 1 ? 2 : 1;
+  const T* pa = a + off;
+  const T* pg = BWD ? g + off : nullptr;
+  T* po = out + off;
+  const int64_t tiles = (len + kTile - 1) / kTile;
+  const int64_t lpos = (int64_t)lane * kLeaf;
+  A m[V];
+  if constexpr (!BWD) {
+    A best[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) best[v] = -__builtin_huge_val();
+    for (int64_t t0 = 0; t0 < tiles; t0 += SW) {
+      A x[SW][V][kLeaf];
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) best[v] = leaf_max<A>(x[u][v], best[v]);
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) m[v] = group_max<A, 64>(best[v]);
+  }
+  A stk[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) stk[v] = A(0);
+  for (int64_t t0 = 0; t0 < tiles; t0 += SW) {
+    A x[SW][V][kLeaf], val[SW][V];
+    if constexpr (!BWD) {
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          val[u][v] = leaf_exp_sum<A>(x[u][v], m[v], (t0 + u) * kTile + lpos, len);
+    } else {
+      A gg[SW][V][kLeaf];
+#pragma unroll
+      for (int u = 0; u < SW; ++u) {
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, A(0), x[u]);
+        load_leaf_heads<T, V>(pg, H, (t0 + u) * kTile + lpos, len, A(0), gg[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) val[u][v] = leaf_dot<A>(x[u][v], gg[u][v]);
+    }
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+#pragma unroll
+      for (int v = 0; v < V; ++v) val[u][v] = group_sum<A, 64>(val[u][v]);
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+      if (t0 + u < tiles) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) stack_push<A>(stk[v], t0 + u, val[u][v], lane);
+      }
+  }
+  A s[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) s[v] = stack_fold<A>(stk[v], tiles);
+  for (int64_t t0 = 0; t0 < tiles; t0 += SW) {
+    A x[SW][V][kLeaf];
+    T res[SW][V][kLeaf];
+    if constexpr (!BWD) {
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          (void)leaf_exp_sum<A>(x[u][v], m[v], (t0 + u) * kTile + lpos, len);
+          leaf_divide<T>(x[u][v], s[v], res[u][v]);
+        }
+    } else {
+      A gg[SW][V][kLeaf];
+#pragma unroll
+      for (int u = 0; u < SW; ++u) {
+        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, A(0), x[u]);
+        load_leaf_heads<T, V>(pg, H, (t0 + u) * kTile + lpos, len, A(0), gg[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < SW; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) leaf_grad<T>(x[u][v], gg[u][v], s[v], res[u][v]);
+    }
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+      store_leaf_heads<T, V>(po, H, (t0 + u) * kTile + lpos, len, res[u]);
+  }
+}
+
+template <typename T, int V, bool BWD>
+__device__ __forceinline__ void row_by_wave(const T* a, const T* g,
+                                            T* out, int64_t H, int64_t off,
+                                            int64_t len, int lane) {
+  if (len <= kTile)
+    row_in_registers<T, V, 64, BWD>(a, g, out, H, off, len, lane);
+  else
+    row_in_tiles<T, V, BWD>(a, g, out, H, off, len, lane);
+}
+
+}  // namespace esmh
 }  // namespace ofx
 #endif  // __HIP__
 

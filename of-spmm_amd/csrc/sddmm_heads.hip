@@ -23,6 +23,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "heads_steps.h"
 #include "spmm_extremum.h"
 #include "spmm_items_dev.h"
 
@@ -31,20 +32,9 @@ namespace {
 
 using namespace item;
 
-constexpr int kLeaf = 8;
-constexpr int64_t kHeadsChunk = 256;          // items of at most this many nonzeros (work only)
-constexpr int64_t kMaxHeadsN = 256 * kLeaf;   // 64 lanes x 4 leaves
+using namespace hsteps;  // kLeaf, kMaxHeadsN, load_leaf and the item's scores (heads_steps.h)
 
-// A lane's leaf in the accumulation type; columns >= n read as +0.
-template <typename T, bool ALIGNED>
-__device__ __forceinline__ void load_leaf(const T* __restrict__ row, int64_t cb, int64_t n,
-                                          typename Num<T>::acc (&x)[kLeaf]) {
-  using A = typename Num<T>::acc;
-  T raw[kLeaf];
-  load_cols<T, kLeaf, ALIGNED>(row, cb, n, Num<T>::store(A(0)), raw);
-#pragma unroll
-  for (int e = 0; e < kLeaf; ++e) x[e] = Num<T>::load(raw[e]);
-}
+constexpr int64_t kHeadsChunk = 256;          // items of at most this many nonzeros (work only)
 
 template <typename T, typename I>
 __device__ __forceinline__ bool poison_head_nonzeros(const unsigned long long* __restrict__ counters,
@@ -73,7 +63,6 @@ __global__ void __launch_bounds__(kBlock)
                        const int64_t* __restrict__ items, const int64_t* __restrict__ order,
                        int64_t block_base, unsigned* err) {
 #pragma clang fp contract(off)
-  using A = typename Num<T>::acc;
   constexpr int GPW = 64 / LG;
   if (poison_head_nonzeros(counters, block_base, err, rp, row_begin, nrows, heads, out)) return;
   const int lane = threadIdx.x & 63;
@@ -85,125 +74,8 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t head = FAST ? 0 : g - gi * heads;
   Item it;
   if (!work_item<I>(rp, gi, row_begin, nrows, chunk, counters, items, order, &it, true)) return;
-  // the columns the group covers: [col0, col0 + w)
-  const int64_t col0 = FAST ? 0 : head * d;
-  const int64_t w = FAST ? heads * d : d;
-  // the tree: `lin` leaves of a head inside a lane, then `seg` lanes of a head
-  const int lin = FAST ? (lh < L ? lh : L) : L;
-  const int seg = FAST ? (lh / lin) : LG;
-  A av[L][kLeaf];
-  int hsel[L];  // FAST: the head whose result this lane's leaf l holds after the tree, or -1
-#pragma unroll
-  for (int l = 0; l < L; ++l) {
-    load_leaf<T, FAST>(a + it.lr * lda + col0, (int64_t)(gl * L + l) * kLeaf, w, av[l]);
-    hsel[l] = -1;
-    if constexpr (FAST) {
-      const int gleaf = gl * L + l;
-      const int h = gleaf / lh;
-      if ((l & (lin - 1)) == 0 && gleaf - h * lh == 0 && h < heads) hsel[l] = h;
-    }
-  }
-  for (int64_t jb = it.j0; jb < it.j1; jb += LG) {
-    const int cnt = (int)((it.j1 - jb) < LG ? (it.j1 - jb) : LG);
-    const I myc = gl < cnt ? col[jb + gl] : I(0);
-    for (int k = 0; k < cnt; k += U) {
-      A bv[U][L][kLeaf];
-      if constexpr (FAST) {
-        // Every load of the round is unconditional and stays a 16-byte word until all are issued
-        // (kb > 0 here, sd_heads_typed; as spmm_heads.hip): a slot past the batch's end repeats
-        // the batch's last nonzero, a column outside [0, k) reads row 0, a leaf past the row's
-        // width reads leaf 0; the last two are then replaced by zeros.
-        constexpr int Q = kLeaf * (int)sizeof(T) / 16, PER = 16 / (int)sizeof(T);
-        struct Words {
-          T v[PER];
-        };
-        static_assert(sizeof(Words) == sizeof(u32x4), "a 16-byte piece of a leaf");
-        u32x4 raw[U][L][Q];
-        unsigned inmask = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int ku = k + u < cnt ? k + u : cnt - 1;
-          const int64_t cu = (int64_t)__shfl((int64_t)myc, gbase + (ku & (LG - 1)), 64);
-          const bool in = (uint64_t)cu < (uint64_t)kb;
-          inmask |= (in ? 1u : 0u) << u;
-          const T* brow = B + (in ? cu : 0) * ldb;
-#pragma unroll
-          for (int l = 0; l < L; ++l) {
-            const int64_t cb = (int64_t)(gl * L + l) * kLeaf;
-            const u32x4* src = reinterpret_cast<const u32x4*>(brow + (cb < w ? cb : 0));
-#pragma unroll
-            for (int q = 0; q < Q; ++q) raw[u][l][q] = src[q];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-          for (int l = 0; l < L; ++l) {
-            const bool keep = ((inmask >> u) & 1u) != 0 && (int64_t)(gl * L + l) * kLeaf < w;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-              const u32x4 r = keep ? raw[u][l][q] : u32x4{0u, 0u, 0u, 0u};
-              const Words wd = __builtin_bit_cast(Words, r);
-#pragma unroll
-              for (int e = 0; e < PER; ++e) bv[u][l][q * PER + e] = Num<T>::load(wd.v[e]);
-            }
-          }
-        }
-      } else {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int64_t cu = (int64_t)__shfl((int64_t)myc, gbase + ((k + u) & (LG - 1)), 64);
-          if (k + u < cnt) {
-            // a column outside [0, k): the forward gathered a zero row; every leaf reads as out
-            // of range and the row's address is never used
-            const bool in = (uint64_t)cu < (uint64_t)kb;
-#pragma unroll
-            for (int l = 0; l < L; ++l)
-              load_leaf<T, false>(B + (in ? cu : 0) * ldb + col0,
-                                  in ? (int64_t)(gl * L + l) * kLeaf : w, w, bv[u][l]);
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (k + u < cnt) {
-          const int64_t j = jb + k + u;
-          A leaf[L];
-#pragma unroll
-          for (int l = 0; l < L; ++l) {
-            A s = A(0);
-#pragma unroll
-            for (int e = 0; e < kLeaf; ++e) s = s + av[l][e] * bv[u][l][e];
-            leaf[l] = s;
-          }
-          // pairwise over the head's leaves in this lane (x < lin: pairs never cross a head)
-#pragma unroll
-          for (int x = 1; x < L; x <<= 1) {
-            if (x < lin) {
-#pragma unroll
-              for (int l = 0; l < L; l += 2 * x) leaf[l] = leaf[l] + leaf[l + x];
-            }
-          }
-          // the butterfly over the head's lanes (seg > 1 only when the lane holds one head)
-          A t = leaf[0];
-#pragma unroll
-          for (int x = 1; x < LG; x <<= 1)
-            if (x < seg) t = t + __shfl_xor(t, x, 64);
-          leaf[0] = t;
-          if constexpr (FAST) {
-#pragma unroll
-            for (int l = 0; l < L; ++l)
-              // a plain store: the H results of a nonzero are a 16-32 byte piece of a line, and
-              // the pieces of consecutive nonzeros merge in L2 (non-temporal, the pieces went out
-              // one by one: 11-12.7 ms for f32 N = 128 on the products graph)
-              if (hsel[l] >= 0) out[j * heads + hsel[l]] = Num<T>::store(leaf[l]);
-          } else {
-            if (gl == 0) out[j * heads + head] = Num<T>::store(t);
-          }
-        }
-      }
-    }
-  }
+  sddmm_heads_item<T, I, LG, L, U, FAST>(col, a + it.lr * lda, B, ldb, kb, out, heads, d, lh, head,
+                                         it.j0, it.j1, gl, gbase);
 }
 
 struct SdHeadsArgs {

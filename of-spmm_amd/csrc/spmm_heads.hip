@@ -21,6 +21,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "heads_steps.h"
 #include "spmm_extremum.h"
 #include "spmm_items_dev.h"
 
@@ -28,6 +29,7 @@ namespace ofx {
 namespace {
 
 using namespace item;
+using namespace hsteps;  // the accumulation of a run of nonzeros (heads_steps.h)
 
 // HEADVEC: ALIGNED rows and D % VEC == 0 (one head per lane).
 template <typename T, typename I, int VEC, int LPR, int U, bool HEADVEC>
@@ -51,7 +53,6 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t g = ((block_base + (int64_t)blockIdx.x) * (kBlock / 64) + wave) * GPW + lane / LPR;
   Item it;
   if (!work_item<I>(rp, g, row_begin, nrows, chunk, counters, items, order, &it)) return;
-  const T zero = Num<T>::store(A(0));
   for (int64_t c0 = 0; c0 < n; c0 += (int64_t)LPR * VEC) {
     const int64_t cb = c0 + (int64_t)gl * VEC;
     // the head of each of the lane's columns (a column >= n: head 0, its product is never stored)
@@ -61,69 +62,8 @@ __global__ void __launch_bounds__(kBlock)
     A acc[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[e] = A(0);
-    for (int64_t jb = it.j0; jb < it.j1; jb += LPR) {
-      const int cnt = (int)((it.j1 - jb) < LPR ? (it.j1 - jb) : LPR);
-      const I myc = gl < cnt ? col[jb + gl] : I(0);
-      for (int k = 0; k < cnt; k += U) {
-        T vv[U][NV];
-        if constexpr (HEADVEC) {
-          // Every load of the round is unconditional (kb > 0 here, heads_typed): a slot past the
-          // batch's end repeats the batch's last nonzero, a column outside [0, k) reads row 0 and
-          // is replaced by zeros, a lane past the row's width reads column 0.  Loads behind
-          // per-slot branches were issued one at a time (each followed by a full wait): the bf16
-          // H=8 D=32 launch on the products graph took 33.5 ms.  The row piece stays one 16-byte
-          // word until it is used (a per-element copy or select is narrowed into misaligned
-          // pieces for 16-bit types).
-          static_assert(sizeof(Pack<T, VEC>) == sizeof(u32x4), "a lane's columns are 16 bytes");
-          u32x4 raw[U];
-          unsigned inmask = 0;
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int ku = k + u < cnt ? k + u : cnt - 1;
-            const int64_t cu = (int64_t)__shfl((int64_t)myc, gbase + (ku & (LPR - 1)), 64);
-            const bool in = (uint64_t)cu < (uint64_t)kb;
-            inmask |= (in ? 1u : 0u) << u;
-            raw[u] = *reinterpret_cast<const u32x4*>(B + (in ? cu : 0) * ldb + (cb < n ? cb : 0));
-            vv[u][0] = val[(jb + ku) * heads + hd[0]];
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            // a column outside [0, k): the zero-filled gathered row of the sum op (+0 is all-zero
-            // bits in every value type)
-            const u32x4 r = ((inmask >> u) & 1u) ? raw[u] : u32x4{0u, 0u, 0u, 0u};
-            const Pack<T, VEC> p = __builtin_bit_cast(Pack<T, VEC>, r);
-            if (k + u < cnt) {
-              const A v = Num<T>::load(vv[u][0]);
-#pragma unroll
-              for (int e = 0; e < VEC; ++e)
-                acc[e] = acc[e] + Num<T>::mul(v, Num<T>::load(p.v[e]));
-            }
-          }
-        } else {
-          T bv[U][VEC];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int64_t cu = (int64_t)__shfl((int64_t)myc, gbase + ((k + u) & (LPR - 1)), 64);
-            if (k + u < cnt) {
-              // a column outside [0, k): the zero-filled gathered row of the sum op
-              const bool in = (uint64_t)cu < (uint64_t)kb;
-              load_cols<T, VEC, false>(B + (in ? cu : 0) * ldb, in ? cb : n, n, zero, bv[u]);
-              const T* vrow = val + (jb + k + u) * heads;
-#pragma unroll
-              for (int e = 0; e < NV; ++e) vv[u][e] = vrow[hd[e]];
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            if (k + u < cnt) {
-#pragma unroll
-              for (int e = 0; e < VEC; ++e)
-                acc[e] = acc[e] + Num<T>::mul(Num<T>::load(vv[u][e]), Num<T>::load(bv[u][e]));
-            }
-          }
-        }
-      }
-    }
+    spmm_heads_accumulate<T, I, VEC, LPR, U, HEADVEC>(col, val, B, ldb, kb, n, heads, cb, hd, it.j0,
+                                                      it.j1, gl, gbase, acc);
     if (it.slot >= 0) {  // a hub chunk's partial: added in chunk order by spmm_heads_hub_kernel
 #pragma unroll
       for (int e = 0; e < VEC; ++e)

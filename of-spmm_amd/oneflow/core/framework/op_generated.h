@@ -149,6 +149,17 @@ class EdgeSoftmaxCsrHeadsGradOp {
                                     const user_op::UserOpConfWrapper& conf);
 };
 
+// The fused multi-head graph attention (oneflow/user/ops/graph_attention_heads_op.cpp).
+class GraphAttentionCsrHeadsOp {
+ public:
+  static Maybe<void> InferLogicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> InferPhysicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> GetSbp(user_op::SbpContext* ctx);
+  static Maybe<void> InferDataType(user_op::InferContext* ctx);
+  static Maybe<void> ModifyInputArg(const user_op::GetInputArgModifier& GetInputArgModifierFn,
+                                    const user_op::UserOpConfWrapper& conf);
+};
+
 // The S(0) -> B collectives the row-split op's B operand goes through: eager boxing
 // (oneflow/user/ops/eager_nccl_ops.cpp:188-233) and the lazy graph's logical collective
 // (oneflow/user/ops/nccl_logical_ops.cpp:104-142, ODS OneFlowUserOps.td:5341-5357).

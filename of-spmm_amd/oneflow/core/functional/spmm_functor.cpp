@@ -934,3 +934,23 @@ extern "C" int ofx_functional_edge_softmax_csr_heads_grad(
                                0);
   });
 }
+
+// ---- functional::GraphAttentionCsrHeads ----------------------------------------------------------
+// Op "graph_attention_csr_heads" (oneflow/user/ops/graph_attention_heads_op.cpp) through the same
+// op-registry dispatch; two outputs.
+extern "C" int ofx_functional_graph_attention_csr_heads(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* q, const ofx_tensor_desc* k, const ofx_tensor_desc* v,
+    int64_t num_heads, ofx_tensor_desc* out, ofx_tensor_desc* attn, void* tmp, size_t tmp_bytes,
+    size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(q != nullptr && k != nullptr && v != nullptr, OFX_EINVAL,
+                "graph_attention_csr_heads: NULL input q, k or v");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("graph_attention_csr_heads");
+    return ToStatus(RunUserOp("graph_attention_csr_heads",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"q", q},
+                               {"k", k}, {"v", v}},
+                              {{"out", out}, {"attn", attn}}, {{"num_heads", num_heads}}, stream,
+                              tmp, tmp_bytes, tmp_size_out));
+  });
+}

@@ -430,22 +430,24 @@ def edge_softmax_csr_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tens
 
 
 def _heads_inputs(op, rp, ci, named):
-    """The index checks the two multi-head ops share, ahead of the op layer's own, and the dtype
-    equality of their value tensors (`named`: [(name, tensor)], "b" last)."""
+    """The index checks the multi-head ops share, ahead of the op layer's own, and the dtype
+    equality of their value tensors (`named`: [(name, tensor)], the [K, heads * D] operand the
+    others are compared with last: "b", or "k" for the fused attention)."""
     if rp.dtype != ci.dtype:
         raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
                         f"({ci.dtype} vs {rp.dtype})")
     dtype_code(rp.dtype)
-    b = named[-1][1]
+    ref, b = named[-1]
     if b.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
         raise TypeError(f"{op} supports float, double, float16, bfloat16; got {b.dtype}")
     for name, t in named[:-1]:
         if t.dtype != b.dtype:
-            raise TypeError(f"{op}: {name} datatype should be equal to b ({t.dtype} vs {b.dtype})")
+            raise TypeError(f"{op}: {name} datatype should be equal to {ref} ({t.dtype} vs "
+                            f"{b.dtype})")
         if t.dim() != 2:
             raise RuntimeError(f"{op}: {name} should be 2-D, got shape {tuple(t.shape)}")
     if b.dim() != 2:
-        raise RuntimeError(f"{op}: b should be 2-D [K, heads * D], got shape {tuple(b.shape)}")
+        raise RuntimeError(f"{op}: {ref} should be 2-D [K, heads * D], got shape {tuple(b.shape)}")
 
 
 def _check_out(op, out, shape, like, contiguous=False):
@@ -513,6 +515,49 @@ def sddmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a:
         return out.zero_()
     _run_grad_op(LIB.ofx_functional_sddmm_csr_heads, bb, [rp, ci, a, bb], [out], [heads])
     return out
+
+
+def graph_attention_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                              q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, *,
+                              out: torch.Tensor | None = None,
+                              attn_out: torch.Tensor | None = None):
+    """Op "graph_attention_csr_heads": dot-product graph attention through one fused kernel for
+    the rows below the SpMM's hub threshold, with the hub rows in follow-up launches.  For
+    q [M, H*D], k and v [K, H*D] with H = num_heads, returns (out [M, H*D], attn [nnz, H]) with
+    attn = edge_softmax_csr_heads(sddmm_csr_heads(q, k)) and out = spmm_csr_heads(attn, v), both
+    with exactly the bits of that composition (contract in include/ofx_spmm.h).  `out`: a [M, H*D]
+    tensor; `attn_out`: a contiguous [nnz, H] tensor; both written directly."""
+    op = "graph_attention_csr_heads"
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    q = _prep(q, "q", matrix=True)
+    kk, vv = _prep(k, "k", matrix=True), _prep(v, "v", matrix=True)
+    _heads_inputs(op, rp, ci, [("q", q), ("v", vv), ("k", kk)])
+    heads = int(num_heads)
+    if heads < 1 or kk.shape[1] % heads != 0:
+        raise RuntimeError(f"{op}: k's columns ({kk.shape[1]}) should be a multiple of "
+                           f"num_heads ({heads})")
+    if q.shape[1] != kk.shape[1] or vv.shape[1] != kk.shape[1]:
+        raise RuntimeError(f"{op}: q, k and v should have the same number of columns "
+                           f"({q.shape[1]}, {kk.shape[1]}, {vv.shape[1]})")
+    if vv.shape[0] != kk.shape[0]:
+        raise RuntimeError(f"{op}: k and v should have the same number of rows "
+                           f"({kk.shape[0]} vs {vv.shape[0]})")
+    m = rp.numel() - 1
+    if q.shape[0] != m:
+        raise RuntimeError(f"{op}: q should have a_num_rows = {m} rows, got {q.shape[0]}")
+    if out is None:
+        out = torch.empty((m, kk.shape[1]), dtype=kk.dtype, device=kk.device)
+    else:
+        _check_out(op, out, (m, kk.shape[1]), kk)
+    if attn_out is None:
+        attn_out = torch.empty((ci.numel(), heads), dtype=kk.dtype, device=kk.device)
+    else:
+        _check_out(op, attn_out, (ci.numel(), heads), kk, contiguous=True)
+    if out.numel() == 0:
+        return out, attn_out
+    _run_grad_op(LIB.ofx_functional_graph_attention_csr_heads, kk, [rp, ci, q, kk, vv],
+                 [out, attn_out], [heads])
+    return out, attn_out
 
 
 def _edge_softmax_heads_inputs(op, rp, ci, named):

@@ -200,6 +200,15 @@ def _load():
                                                    ctypes.POINTER(sz)], i32),
         "ofx_functional_edge_softmax_csr_heads_grad": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, p, sz,
                                                         ctypes.POINTER(sz)], i32),
+        "ofx_graph_attention_csr_heads_workspace_size": ([i32, i32, i64, i64, i64, i64, i64, popt,
+                                                          ctypes.POINTER(sz)], i32),
+        "ofx_graph_attention_csr_heads": ([p, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64, p,
+                                           i64, p, i64, p, i64, p, i64, i64, p, sz, popt], i32),
+        "ofx_graph_attention_csr_heads_cpu": ([i32, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64,
+                                               p, i64, p, i64, p, i64, p, i64, i64, popt], i32),
+        "ofx_functional_graph_attention_csr_heads": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64,
+                                                      pdesc, pdesc, p, sz, ctypes.POINTER(sz)],
+                                                     i32),
         "ofx_coo_to_csr_workspace_size": ([i32, i64, i64, i64, ctypes.POINTER(sz)], i32),
         "ofx_coo_to_csr": ([p, i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, p, p, p, sz], i32),
         "ofx_coo_to_csr_cpu": ([i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, ctypes.POINTER(i64)], i32),

@@ -379,6 +379,92 @@ def edge_softmax(a_csr_row_ptr, a_csr_col_idx, e, *, out=None):
     return _C.edge_softmax_csr(a_csr_row_ptr, a_csr_col_idx, e, out=out)
 
 
+class GraphAttentionFunction(torch.autograd.Function):
+    """(out [M, H, D], attn [nnz, H]) = graph attention of q [M, H, D], k and v [K, H, D] through
+    op "graph_attention_csr_heads", differentiable in q, k and v.  The weights are saved
+    and the backward consists of the composed layer's own ops, so every gradient has the bits of
+    the autograd of spmm(edge_softmax(sddmm(q, k)), v)."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, q, k, v):
+        heads, d = k.shape[1], k.shape[2]
+        q2, k2, v2 = _heads_2d(q, "q"), _heads_2d(k, "k"), _heads_2d(v, "v")
+        out, attn = _C.graph_attention_csr_heads(row_ptr, col_idx, q2, k2, v2, heads)
+        ctx.save_for_backward(row_ptr, col_idx, q2, k2, v2, attn)
+        ctx.heads, ctx.d = heads, d
+        # an output that did not enter the loss hands in None, not a tensor of zeros: no [nnz, H]
+        # allocation and no add (which would also turn a -0 of d_attn into +0) for unused weights
+        ctx.set_materialize_grads(False)
+        return out.view(q2.shape[0], heads, d), attn
+
+    @staticmethod
+    def backward(ctx, d_out, d_attn_up):
+        row_ptr, col_idx, q2, k2, v2, attn = ctx.saved_tensors
+        heads, d = ctx.heads, ctx.d
+        m, k = q2.shape[0], k2.shape[0]
+        d_q = d_k = d_v = None
+        g = None if d_out is None else d_out.contiguous().view(m, heads * d)
+        if g is None and d_attn_up is None:
+            return None, None, None, None, None
+        if ctx.needs_input_grad[4] and g is not None:
+            d_v = _heads_grad_b(row_ptr, col_idx, attn, m, k, g).view(k, heads, d)
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            if g is None:  # only the returned weights entered the loss
+                d_attn = d_attn_up
+            else:
+                d_attn = _C.sddmm_csr_heads(row_ptr, col_idx, g, v2, heads)
+                if d_attn_up is not None:  # the returned weights entered the loss as well
+                    d_attn = d_attn + d_attn_up
+            d_e = _C.edge_softmax_csr_heads_grad(row_ptr, col_idx, attn, d_attn.contiguous())
+            if ctx.needs_input_grad[2]:
+                d_q = _C.spmm_csr_heads(row_ptr, col_idx, d_e, m, k, k2).view(m, heads, d)
+            if ctx.needs_input_grad[3]:
+                d_k = _heads_grad_b(row_ptr, col_idx, d_e, m, k, q2).view(k, heads, d)
+        return None, None, d_q, d_k, d_v
+
+
+def graph_attention(a_csr_row_ptr, a_csr_col_idx, q, k, v, *, return_attention=False):
+    """Dot-product graph attention over a CSR:
+        attn[j, h] = softmax over j's row of <q[row(j), h, :], k[col[j], h, :]>
+        out[r, h, :] = sum over r's nonzeros j of attn[j, h] * v[col[j], h, :]
+    for q [M, H, D], k and v [K, H, D] (DGL's / PyG's fused dot-product attention).  Returns
+    out [M, H, D], or (out, attn [nnz, H]) with return_attention=True.  The 2-D forms q [M, D],
+    k and v [K, D] mean H = 1 and return out [M, D].  There is no scale factor: scale q.
+    On the GPU a row of at most the SpMM's hub threshold (512 nonzeros at D <= 128) goes through
+    scores, softmax and aggregation inside one kernel; longer rows take the planner's chunks and
+    three small follow-up launches.
+
+    out and attn have exactly the bits of `spmm(rp, ci, edge_softmax(rp, ci, sddmm(rp, ci, q, k)),
+    M, K, v)`, on CPU and GPU tensors, and so have the gradients in q, k and v: the backward is
+    that composition's.  Non-contiguous inputs are made contiguous first."""
+    if q.dim() != k.dim() or q.dim() != v.dim() or q.dim() not in (2, 3):
+        raise RuntimeError("graph_attention: q [M, H, D], k and v [K, H, D] (or q [M, D], k and v "
+                           f"[K, D]) are expected, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                           f"{tuple(v.shape)}")
+    flat = q.dim() == 2
+    if flat:
+        q, k, v = q.unsqueeze(1), k.unsqueeze(1), v.unsqueeze(1)
+    if q.shape[1:] != k.shape[1:] or v.shape != k.shape:
+        raise RuntimeError("graph_attention: q [M, H, D] needs k and v [K, H, D] with the same "
+                           f"heads and D, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    if q.dtype != k.dtype or v.dtype != k.dtype:
+        raise TypeError("graph_attention: q, k and v should have one dtype, got "
+                        f"{q.dtype}, {k.dtype}, {v.dtype}")
+    if q.device != k.device or v.device != k.device:
+        raise RuntimeError("graph_attention: expected all tensors on the same device, got "
+                           f"{q.device}, {k.device}, {v.device}")
+    heads, d = k.shape[1], k.shape[2]
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        out, attn = GraphAttentionFunction.apply(a_csr_row_ptr, a_csr_col_idx, q, k, v)
+    else:
+        out, attn = _C.graph_attention_csr_heads(a_csr_row_ptr, a_csr_col_idx, _heads_2d(q, "q"),
+                                                 _heads_2d(k, "k"), _heads_2d(v, "v"), heads)
+        out = out.view(q.shape[0], heads, d)
+    if flat:
+        out = out.view(q.shape[0], d)
+    return (out, attn) if return_attention else out
+
+
 class SpmmCsrReduceFunction(torch.autograd.Function):
     """(out, arg) = spmm_csr_reduce(..., reduce) for reduce in {"mean", "max", "min"},
     differentiable in `a_csr_values` and `b`; `arg` is not differentiable.

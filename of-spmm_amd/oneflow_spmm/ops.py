@@ -268,6 +268,42 @@ def sddmm_csr_heads(row_ptr, col_idx, a, b, m, k, heads, *, out=None, row_begin=
     return out
 
 
+def graph_attention_csr_heads(row_ptr, col_idx, q, k_mat, v, m, k, heads, *, out=None, attn=None,
+                              row_begin=0, row_end=None, options: Options | None = None,
+                              num_threads: int = 0, workspace_bytes: int | None = None):
+    """The fused multi-head graph attention at the C-ABI (ofx_graph_attention_csr_heads on device
+    tensors, the kCPU kernel ofx_graph_attention_csr_heads_cpu on host tensors): q holds rows
+    [row_begin, row_end) of the queries, k_mat and v are [K, heads * D], all with unit column
+    stride -> (out [row_end - row_begin, heads * D], attn [nnz, heads]); a row range writes its own
+    nonzeros' rows of attn.  workspace_bytes: the device workspace to pass instead of the query's
+    size (tests)."""
+    row_end = m if row_end is None else row_end
+    n, nnz = k_mat.shape[1], col_idx.numel()
+    d = n // heads if heads else 0
+    if out is None:
+        out = torch.empty((row_end - row_begin, n), dtype=k_mat.dtype, device=k_mat.device)
+    if attn is None:
+        attn = torch.empty((nnz, heads), dtype=k_mat.dtype, device=k_mat.device)
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(k_mat.dtype)
+    popt = ctypes.byref(options) if options else None
+    body = (idt, vdt, m, k, heads, d, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(q), q.stride(0),
+            _nz(k_mat), k_mat.stride(0), _nz(v), v.stride(0), _nz(out), out.stride(0), _nz(attn),
+            row_begin, row_end)
+    if k_mat.device.type == "cpu":
+        check(LIB.ofx_graph_attention_csr_heads_cpu(int(num_threads), *body, popt),
+              "graph_attention_csr_heads_cpu")
+        return out, attn
+    size = ctypes.c_size_t(0)
+    check(LIB.ofx_graph_attention_csr_heads_workspace_size(idt, vdt, m, k, heads, d, nnz, popt,
+                                                           ctypes.byref(size)),
+          "graph_attention_csr_heads")
+    ws = size.value if workspace_bytes is None else int(workspace_bytes)
+    wbuf = torch.empty(max(ws, 1), dtype=torch.uint8, device=k_mat.device)
+    check(LIB.ofx_graph_attention_csr_heads(current_stream_handle(k_mat), *body, wbuf.data_ptr(),
+                                            ws, popt), "graph_attention_csr_heads")
+    return out, attn
+
+
 def validate_csr(row_ptr, col_idx, m, k) -> int:
     """Device-side CSR check; returns 0 ok, 1 bad row_ptr, 2 column out of range (syncs)."""
     flag = torch.zeros(1, dtype=torch.int32, device=row_ptr.device)
