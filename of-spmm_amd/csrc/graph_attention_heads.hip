@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // The hubs' aggregation: a lane group per hub chunk, summed from +0 into the chunk's partial
-// (spmm_heads.hip's chunk items); gat_hub_reduce_kernel adds the partials in chunk order.
+// (spmm_heads.hip's chunk items); hub_sum_kernel adds the partials in chunk order.
 template <typename T, typename I, int VEC, int G, bool FAST>
 __global__ void __launch_bounds__(kBlock)
     gat_hub_chunks_kernel(const I* __restrict__ rp, const I* __restrict__ col, const T* attn,
@@ -220,29 +220,6 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-// The hub rows of out: the chunk partials added in chunk order into +0, rounded once
-// (spmm_heads.hip's hub kernel).  One block per hub, grid-strided; threads over the columns.
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-    gat_hub_reduce_kernel(const unsigned long long* __restrict__ counters,
-                          const int64_t* __restrict__ hubs,
-                          const typename Num<T>::acc* __restrict__ part, T* __restrict__ out,
-                          int64_t ldo, int64_t nrows, int64_t n) {
-#pragma clang fp contract(off)
-  using A = typename Num<T>::acc;
-  if (!plan::plan_valid(counters)) return;
-  const int64_t nhubs = (int64_t)counters[1];
-  for (int64_t h = blockIdx.x; h < nhubs; h += gridDim.x) {
-    const int64_t lr = hubs[3 * h], s0 = hubs[3 * h + 1], nc = hubs[3 * h + 2];
-    if ((uint64_t)lr >= (uint64_t)nrows) continue;  // never from a valid plan
-    for (int64_t c = threadIdx.x; c < n; c += kBlock) {
-      A acc = A(0);
-      for (int64_t q = 0; q < nc; ++q) acc = acc + part[(s0 + q) * n + c];
-      nt_store_one(out + lr * ldo + c, Num<T>::store(acc));
-    }
-  }
-}
-
 struct GatArgs {
   hipStream_t s;
   const void *rp, *col, *q, *k, *v;
@@ -252,9 +229,6 @@ struct GatArgs {
   size_t ws_bytes;
   const ofx_spmm_options* opts;
 };
-
-// The schedule: the sum op's, resolved from the width of ONE head (the numeric contract).
-Schedule gat_schedule(int64_t d, const ofx_spmm_options* opts) { return resolve_schedule(d, opts); }
 
 template <typename T, typename I, int G, int L, bool FAST>
 int gat_cfg(const GatArgs& a) {
@@ -270,7 +244,7 @@ int gat_cfg(const GatArgs& a) {
   Planned p;
   int rc = prepare_plan<I>("graph_attention_csr_heads", a.s, rp, a.row_begin, a.nrows, a.nnz,
                            launch_nnz(a.m, a.nrows, a.nnz, a.opts), n, sizeof(A),
-                           gat_schedule(a.d, a.opts), false, a.ws, a.ws_bytes, &p);
+                           resolve_schedule(a.d, a.opts), false, a.ws, a.ws_bytes, &p);
   if (rc) return rc;
   A* part = static_cast<A*>(p.wl.part);
   rc = launch_cut_grid(p.work, GPB, [&](dim3 grid, int64_t b0) {
@@ -294,11 +268,7 @@ int gat_cfg(const GatArgs& a) {
                        a.heads, a.d, p.chunk, p.wl.counters, p.wl.items, p.wl.order, part, b0);
   });
   if (rc) return rc;
-  const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
-  hipLaunchKernelGGL((gat_hub_reduce_kernel<T>), dim3(hgrid), dim3(kBlock), 0, a.s, p.wl.counters,
-                     p.wl.hubs, part, static_cast<T*>(a.out), a.ldo, a.nrows, n);
-  OFX_HIP_CHECK(hipGetLastError());
-  return OFX_OK;
+  return launch_hub_sum(a.s, p, static_cast<T*>(a.out), a.ldo, a.nrows, n);
 }
 
 // The lane group: a lane per 16 bytes of the H*D row, as spmm_heads.hip; at 64 lanes the leaves a
@@ -358,7 +328,7 @@ extern "C" int ofx_graph_attention_csr_heads_workspace_size(int idx_dtype, int v
     sh.n = heads * d;
     *bytes = sh.n == 0 ? 0
                        : plan::ws_layout(m, nnz, sh.n, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
-                                         gat_schedule(d, opts)).total;
+                                         resolve_schedule(d, opts)).total;
     return OFX_OK;
   });
 }
@@ -384,7 +354,7 @@ extern "C" int ofx_graph_attention_csr_heads(void* stream, int idx_dtype, int va
       return rc;
     if (sh.nothing) return OFX_OK;
     const size_t need = plan::ws_layout(sh.nrows, nnz, sh.n, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
-                                        gat_schedule(d, opts)).total;
+                                        resolve_schedule(d, opts)).total;
     OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
                 "graph_attention_csr_heads: workspace of %zu bytes is smaller than the %zu bytes "
                 "required", workspace_bytes, need);

@@ -88,7 +88,7 @@ struct SdHeadsArgs {
 };
 
 // Work layout only (every out[j, h] is its own dot product): the narrow SDDMM's items.
-Schedule sddmm_heads_schedule() {
+Schedule sddmm_schedule() {
   Schedule s = resolve_schedule(1, nullptr);
   s.split = s.chunk = kHeadsChunk;
   return s;
@@ -100,7 +100,7 @@ int sd_heads_cfg(const SdHeadsArgs& x, int lh) {
   Planned p;
   if (const int rc = prepare_plan<I>("sddmm_csr_heads", x.s, static_cast<const I*>(x.rp),
                                      x.row_begin, x.nrows, x.nnz, x.nnz, 0, 0,
-                                     sddmm_heads_schedule(), false, x.ws, x.ws_bytes, &p))
+                                     sddmm_schedule(), false, x.ws, x.ws_bytes, &p))
     return rc;
   const int64_t groups = FAST ? p.work : p.work * x.heads;
   return launch_cut_grid(groups, (kBlock / 64) * (64 / LG), [&](dim3 grid, int64_t b0) {
@@ -160,7 +160,7 @@ extern "C" int ofx_sddmm_csr_heads_workspace_size(int idx_dtype, int val_dtype, 
     if (const int rc = check_sd_heads_args("sddmm_csr_heads_workspace_size", idx_dtype, val_dtype,
                                            m, 0, heads, d, nnz))
       return rc;
-    *bytes = plan::ws_layout(m, nnz, 0, 0, sddmm_heads_schedule()).total;
+    *bytes = plan::ws_layout(m, nnz, 0, 0, sddmm_schedule()).total;
     return OFX_OK;
   });
 }
@@ -185,7 +185,7 @@ extern "C" int ofx_sddmm_csr_heads(void* stream, int idx_dtype, int val_dtype, i
                 (long long)kMaxHeadsN);
     OFX_REQUIRE(row_ptr && col_idx && out && a && b, OFX_EINVAL, "sddmm_csr_heads: NULL pointer");
     const size_t need =
-        plan::ws_layout(row_end - row_begin, nnz, 0, 0, sddmm_heads_schedule()).total;
+        plan::ws_layout(row_end - row_begin, nnz, 0, 0, sddmm_schedule()).total;
     OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
                 "sddmm_csr_heads: workspace of %zu bytes is smaller than the %zu bytes required",
                 workspace_bytes, need);

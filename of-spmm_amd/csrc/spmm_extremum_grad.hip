@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(kBlock)
         }
       }
     }
-    if (it.slot >= 0) {  // a hub chunk's partial: added in chunk order by select_hub_kernel
+    if (it.slot >= 0) {  // a hub chunk's partial: added in chunk order by hub_sum_kernel
 #pragma unroll
       for (int e = 0; e < VEC; ++e)
         if (cb + e < n) part[it.slot * n + cb + e] = acc[e];
@@ -101,28 +101,6 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
       for (int e = 0; e < VEC; ++e) o[e] = Num<T>::store(acc[e]);
       store_cols<T, VEC, ALIGNED>(db + it.lr * lddb, cb, n, o);
-    }
-  }
-}
-
-// Hub rows of A^T: the chunk partials added in chunk order into +0, one rounding to T.
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-    select_hub_kernel(const unsigned long long* __restrict__ counters,
-                      const int64_t* __restrict__ hubs,
-                      const typename Num<T>::acc* __restrict__ part, T* __restrict__ db,
-                      int64_t lddb, int64_t nrows, int64_t n) {
-#pragma clang fp contract(off)
-  using A = typename Num<T>::acc;
-  if (!plan::plan_valid(counters)) return;  // the main kernel has poisoned the output
-  const int64_t nhubs = (int64_t)counters[1];
-  for (int64_t h = blockIdx.x; h < nhubs; h += gridDim.x) {
-    const int64_t lr = hubs[3 * h], s0 = hubs[3 * h + 1], nc = hubs[3 * h + 2];
-    if ((uint64_t)lr >= (uint64_t)nrows) continue;  // never from a valid plan
-    for (int64_t c = threadIdx.x; c < n; c += kBlock) {
-      A acc = A(0);
-      for (int64_t q = 0; q < nc; ++q) acc = acc + part[(s0 + q) * n + c];
-      nt_store_one(db + lr * lddb + c, Num<T>::store(acc));
     }
   }
 }
@@ -157,13 +135,8 @@ int select_cfg(const SelArgs& a) {
                        p.chunk, p.wl.counters, p.wl.items, p.wl.order, part, b0, p.err);
   });
   if (rc) return rc;
-  if (p.has_plan && p.w.max_hubs > 0) {
-    const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
-    hipLaunchKernelGGL((select_hub_kernel<T>), dim3(hgrid), dim3(kBlock), 0, a.s, p.wl.counters,
-                       p.wl.hubs, part, static_cast<T*>(a.db), a.lddb, a.nrows, a.n);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
-  return OFX_OK;
+  // hub rows of A^T
+  return launch_hub_sum(a.s, p, static_cast<T*>(a.db), a.lddb, a.nrows, a.n);
 }
 
 template <typename T, typename I, bool ALIGNED>

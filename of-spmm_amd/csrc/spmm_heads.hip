@@ -15,7 +15,7 @@
 // D % VEC == 0 a lane's columns lie in one head h and it loads values[j*H + h] itself (the lanes
 // of a head read one address: one L1 / L2 hit per nonzero and head, the line fetched once);
 // otherwise (D < VEC, odd D, unaligned rows) every element carries its own head index and the
-// loads are scalar.  Hub chunks write accumulation-type partials, spmm_heads_hub_kernel adds them.
+// loads are scalar.  Hub chunks write accumulation-type partials, hub_sum_kernel adds them.
 // No atomics, no allocation, no host synchronisation.
 #pragma clang fp contract(off)
 
@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(kBlock)
     for (int e = 0; e < VEC; ++e) acc[e] = A(0);
     spmm_heads_accumulate<T, I, VEC, LPR, U, HEADVEC>(col, val, B, ldb, kb, n, heads, cb, hd, it.j0,
                                                       it.j1, gl, gbase, acc);
-    if (it.slot >= 0) {  // a hub chunk's partial: added in chunk order by spmm_heads_hub_kernel
+    if (it.slot >= 0) {  // a hub chunk's partial: added in chunk order by hub_sum_kernel
 #pragma unroll
       for (int e = 0; e < VEC; ++e)
         if (cb + e < n) part[it.slot * n + cb + e] = acc[e];
@@ -73,29 +73,6 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
       for (int e = 0; e < VEC; ++e) o[e] = Num<T>::store(acc[e]);
       store_cols<T, VEC, HEADVEC>(out + it.lr * ldc, cb, n, o);
-    }
-  }
-}
-
-// The hub rows: the chunk partials added in chunk order into +0, rounded once.  One block per hub,
-// grid-strided; threads over the columns.
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-    spmm_heads_hub_kernel(const unsigned long long* __restrict__ counters,
-                          const int64_t* __restrict__ hubs,
-                          const typename Num<T>::acc* __restrict__ part, T* __restrict__ out,
-                          int64_t ldc, int64_t nrows, int64_t n) {
-#pragma clang fp contract(off)
-  using A = typename Num<T>::acc;
-  if (!plan::plan_valid(counters)) return;  // the main kernel has poisoned the output
-  const int64_t nhubs = (int64_t)counters[1];
-  for (int64_t h = blockIdx.x; h < nhubs; h += gridDim.x) {
-    const int64_t lr = hubs[3 * h], s0 = hubs[3 * h + 1], nc = hubs[3 * h + 2];
-    if ((uint64_t)lr >= (uint64_t)nrows) continue;  // never from a valid plan
-    for (int64_t c = threadIdx.x; c < n; c += kBlock) {
-      A acc = A(0);
-      for (int64_t q = 0; q < nc; ++q) acc = acc + part[(s0 + q) * n + c];
-      nt_store_one(out + lr * ldc + c, Num<T>::store(acc));
     }
   }
 }
@@ -110,10 +87,6 @@ struct HeadsArgs {
   const ofx_spmm_options* opts;
 };
 
-// The schedule: the sum op's, resolved from the width of ONE head (the numeric contract), with
-// this launch's share of the nonzeros for the automatic heavy threshold.
-Schedule heads_schedule(int64_t d, const ofx_spmm_options* opts) { return resolve_schedule(d, opts); }
-
 template <typename T, typename I, int VEC, int LPR, bool HEADVEC>
 int heads_cfg(const HeadsArgs& a) {
   using A = typename Num<T>::acc;
@@ -121,9 +94,11 @@ int heads_cfg(const HeadsArgs& a) {
   constexpr int64_t GPB = (kBlock / 64) * (64 / LPR);
   const int64_t n = a.heads * a.d;
   Planned p;
+  // the schedule: the sum op's, resolved from the width of ONE head (the numeric contract), with
+  // this launch's share of the nonzeros for the automatic heavy threshold
   int rc = prepare_plan<I>("spmm_csr_heads", a.s, static_cast<const I*>(a.rp), a.row_begin,
                            a.nrows, a.nnz, launch_nnz(a.m, a.nrows, a.nnz, a.opts), n, sizeof(A),
-                           heads_schedule(a.d, a.opts), false, a.ws, a.ws_bytes, &p);
+                           resolve_schedule(a.d, a.opts), false, a.ws, a.ws_bytes, &p);
   if (rc) return rc;
   A* part = static_cast<A*>(p.wl.part);
   rc = launch_cut_grid(p.work, GPB, [&](dim3 grid, int64_t b0) {
@@ -134,13 +109,7 @@ int heads_cfg(const HeadsArgs& a) {
                        p.wl.counters, p.wl.items, p.wl.order, part, b0, p.err);
   });
   if (rc) return rc;
-  if (p.has_plan && p.w.max_hubs > 0) {
-    const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
-    hipLaunchKernelGGL((spmm_heads_hub_kernel<T>), dim3(hgrid), dim3(kBlock), 0, a.s,
-                       p.wl.counters, p.wl.hubs, part, static_cast<T*>(a.c), a.ldc, a.nrows, n);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
-  return OFX_OK;
+  return launch_hub_sum(a.s, p, static_cast<T*>(a.c), a.ldc, a.nrows, n);
 }
 
 // One layout per width class: the lanes of a group cover the H*D columns in one tile up to
@@ -192,7 +161,7 @@ extern "C" int ofx_spmm_csr_heads_workspace_size(int idx_dtype, int val_dtype, i
                                         k, heads, d, nnz, opts))
       return rc;
     *bytes = plan::ws_layout(m, nnz, heads * d, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
-                             heads_schedule(d, opts)).total;
+                             resolve_schedule(d, opts)).total;
     return OFX_OK;
   });
 }
@@ -219,7 +188,7 @@ extern "C" int ofx_spmm_csr_heads(void* stream, int idx_dtype, int val_dtype, in
                 "spmm_csr_heads: NULL col_idx/values/b with nnz=%lld", (long long)nnz);
     // these entries' wording of the size error, ahead of the shared check
     const size_t need = plan::ws_layout(nrows, nnz, n, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
-                                        heads_schedule(d, opts)).total;
+                                        resolve_schedule(d, opts)).total;
     OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
                 "spmm_csr_heads: workspace of %zu bytes is smaller than the %zu bytes required",
                 workspace_bytes, need);

@@ -1,9 +1,11 @@
 // spmm_items_dev.h — what the planned-item kernels share (the SDDMMs of spmm_backward.hip, the
-// max / min forward of spmm_extremum.hip and its d(b) of spmm_extremum_grad.hip): one lane-group
+// max / min forward of spmm_extremum.hip and its d(b) of spmm_extremum_grad.hip, the multi-head
+// SpMM of spmm_heads.hip and the attention of graph_attention_heads.hip): one lane-group
 // per work item (a row or a hub chunk from the shared planner, spmm_plan.h), a grid cut into
 // launches of fewer than 2^31 threads, a loud NaN fill when the plan is not valid.  Here are the
-// work item's decode, the poison fills, vector loads of a lane's columns, non-temporal stores, and
-// the host side that lays out and plans the workspace and runs the cut grid.
+// work item's decode, the poison fills, vector loads of a lane's columns, non-temporal stores,
+// the host side that lays out and plans the workspace and runs the cut grid, and hub_sum_kernel
+// with its launch: the one kernel that adds a summing op's hub-chunk partials.
 // Included by HIP translation units only.
 #ifndef OFX_SPMM_ITEMS_DEV_H_
 #define OFX_SPMM_ITEMS_DEV_H_
@@ -271,6 +273,42 @@ int launch_cut_grid(int64_t work, int64_t groups_per_block, F&& launch) {
     launch(dim3((unsigned)std::min(kLaunchBlocks, grid - b0)), b0);
     OFX_HIP_CHECK(hipGetLastError());
   }
+  return OFX_OK;
+}
+
+// The hub rows of a sum: the chunk partials added in chunk order into +0, rounded once.  One block
+// per hub, grid-strided; threads over the columns.
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+    hub_sum_kernel(const unsigned long long* __restrict__ counters,
+                   const int64_t* __restrict__ hubs,
+                   const typename Num<T>::acc* __restrict__ part, T* __restrict__ out,
+                   int64_t ldc, int64_t nrows, int64_t n) {
+#pragma clang fp contract(off)
+  using A = typename Num<T>::acc;
+  if (!plan::plan_valid(counters)) return;  // the main kernel has poisoned the output
+  const int64_t nhubs = (int64_t)counters[1];
+  for (int64_t h = blockIdx.x; h < nhubs; h += gridDim.x) {
+    const int64_t lr = hubs[3 * h], s0 = hubs[3 * h + 1], nc = hubs[3 * h + 2];
+    if ((uint64_t)lr >= (uint64_t)nrows) continue;  // never from a valid plan
+    for (int64_t c = threadIdx.x; c < n; c += kBlock) {
+      A acc = A(0);
+      for (int64_t q = 0; q < nc; ++q) acc = acc + part[(s0 + q) * n + c];
+      nt_store_one(out + lr * ldc + c, Num<T>::store(acc));
+    }
+  }
+}
+
+// Launches it over the hubs of plan `p` (nothing without a plan or without room for a hub).
+template <typename T>
+int launch_hub_sum(hipStream_t stream, const Planned& p, T* out, int64_t ldc, int64_t nrows,
+                   int64_t n) {
+  if (!p.has_plan || p.w.max_hubs == 0) return OFX_OK;
+  const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
+  hipLaunchKernelGGL((hub_sum_kernel<T>), dim3(hgrid), dim3(kBlock), 0, stream, p.wl.counters,
+                     p.wl.hubs, static_cast<const typename Num<T>::acc*>(p.wl.part), out, ldc,
+                     nrows, n);
+  OFX_HIP_CHECK(hipGetLastError());
   return OFX_OK;
 }
 

@@ -45,26 +45,6 @@ Maybe<void> CheckDesc(const ofx_tensor_desc* d, const char* name) {
   return Maybe<void>::Ok();
 }
 
-Maybe<void> CheckArgs(const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
-                      const ofx_tensor_desc* values, const ofx_tensor_desc* b) {
-  CHECK_OR_RETURN(row_ptr && col_idx && values && b)
-      << Error::RuntimeError() << "spmm_csr: NULL tensor argument";
-  JUST(CheckDesc(row_ptr, "a_csr_row_ptr"));
-  JUST(CheckDesc(col_idx, "a_csr_col_idx"));
-  JUST(CheckDesc(values, "a_csr_values"));
-  JUST(CheckDesc(b, "b"));
-  CHECK_OR_RETURN(row_ptr->ndim >= 1 && row_ptr->ndim <= 2 && col_idx->ndim >= 1 &&
-                  col_idx->ndim <= 2 && values->ndim >= 1 && values->ndim <= 2 && b->ndim >= 1 &&
-                  b->ndim <= 2)
-      << Error::RuntimeError() << "spmm_csr: tensors must be 1-D or 2-D";
-  CHECK_OR_RETURN(row_ptr->device == col_idx->device && row_ptr->device == values->device &&
-                  row_ptr->device == b->device)
-      << Error::RuntimeError() << "spmm_csr: expected all tensors on the same device, got "
-      << row_ptr->device << ", " << col_idx->device << ", " << values->device << ", "
-      << b->device;
-  return Maybe<void>::Ok();
-}
-
 // Stride contract of the kernels: a 2-D tensor is rows of unit-stride elements at row_stride
 // >= shape[1] (b may be a row-strided view; out too).  A column stride != 1 (e.g. out[:, ::2])
 // cannot be expressed to the kernel, which takes only the row stride, and is refused.
@@ -110,43 +90,65 @@ Maybe<void> MakePlacement(int hierarchy_ndim, const int64_t* hierarchy, const in
   return Maybe<void>::Ok();
 }
 
-// Logical inference (the op's logical rule on the logical b: K x b_logical_cols), then the
-// physical out of this rank (the op's physical rule on the physical inputs + placement).
-Maybe<void> Infer(const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
-                  const ofx_tensor_desc* values, int64_t m, int64_t k, const ofx_tensor_desc* b,
-                  int64_t b_logical_cols, const Placement& pl, user_op::TensorDesc* logical_out,
-                  user_op::TensorDesc* physical_out) {
-  JUST(CheckArgs(row_ptr, col_idx, values, b));
-  JUST(CheckUnitColumnStride(b, "b"));
-  const user_op::OpRegistryResult* op = user_op::UserOpRegistryMgr::Get().GetOpRegistryResult("spmm_csr");
-  CHECK_OR_RETURN(op != nullptr) << Error::RuntimeError() << "op spmm_csr is not registered";
+struct Arg {
+  const char* name;
+  const ofx_tensor_desc* d;
+};
+
+// What inference leaves for the dispatch: the op's attributes (the registered defaults, then the
+// call's values), the physical inputs, and per output the NdSbp, the logical and the physical desc.
+struct Inferred {
+  user_op::AttrMap attrs;
   DescMap in;
-  in[{"a_csr_row_ptr", 0}] = user_op::TensorDesc(ShapeOf(row_ptr), (DataType)row_ptr->dtype);
-  in[{"a_csr_col_idx", 0}] = user_op::TensorDesc(ShapeOf(col_idx), (DataType)col_idx->dtype);
-  in[{"a_csr_values", 0}] = user_op::TensorDesc(ShapeOf(values), (DataType)values->dtype);
-  DescMap logical_in = in;
-  Shape b_logical = ShapeOf(b);
-  if (b_logical.NumAxes() == 2 && b_logical_cols >= 0) b_logical.Set(1, b_logical_cols);
-  logical_in[{"b", 0}] = user_op::TensorDesc(b_logical, (DataType)b->dtype);
-  const user_op::AttrMap attrs = {{"a_num_rows", m}, {"a_num_cols", k}};
-  user_op::InferContext lctx(logical_in, attrs);
+  std::map<std::string, NdSbp> nd_sbp;
+  std::map<std::string, user_op::TensorDesc> logical, physical;
+};
+
+// Inference of a registered user op on one rank of a placement (input "b" and every output follow
+// the placement's NdSbp, the other inputs are broadcast): the op's logical rule on the logical b
+// (K x b_logical_cols), then its physical rule on the physical inputs.
+Maybe<void> InferUserOp(const std::string& op_name, const std::vector<Arg>& ins,
+                        const user_op::AttrMap& call_attrs, const Placement& pl,
+                        int64_t b_logical_cols, Inferred* r) {
+  const user_op::OpRegistryResult* op = user_op::UserOpRegistryMgr::Get().GetOpRegistryResult(op_name);
+  CHECK_OR_RETURN(op != nullptr) << Error::RuntimeError() << "op " << op_name << " is not registered";
+  for (const auto& a : op->attrs) r->attrs[a.first] = a.second;
+  for (const auto& a : call_attrs) r->attrs[a.first] = a.second;
+  for (const Arg& a : ins)
+    CHECK_OR_RETURN(a.d != nullptr) << Error::RuntimeError() << op_name << ": NULL input " << a.name;
+  const int device = ins.front().d->device;
+  for (const Arg& a : ins) {
+    JUST(CheckDesc(a.d, a.name));
+    CHECK_OR_RETURN(a.d->ndim >= 1 && a.d->ndim <= 2)
+        << Error::RuntimeError() << op_name << ": " << a.name << " must be 1-D or 2-D";
+    CHECK_EQ_OR_RETURN(a.d->device, device)
+        << Error::RuntimeError() << op_name << ": expected all tensors on the same device";
+    JUST(CheckUnitColumnStride(a.d, a.name));
+    r->in[{a.name, 0}] = user_op::TensorDesc(ShapeOf(a.d), (DataType)a.d->dtype);
+  }
+  DescMap logical_in = r->in;
+  auto b_it = logical_in.find({"b", 0});
+  if (b_it != logical_in.end() && b_it->second.shape().NumAxes() == 2 && b_logical_cols >= 0) {
+    Shape b_logical = b_it->second.shape();
+    b_logical.Set(1, b_logical_cols);
+    b_it->second = user_op::TensorDesc(b_logical, b_it->second.data_type());
+  }
+  user_op::InferContext lctx(logical_in, r->attrs);
   JUST(op->logical_infer(&lctx));
   JUST(op->dtype_infer(&lctx));
-  *logical_out = lctx.OutputTensorDesc("out", 0);
-  in[{"b", 0}] = user_op::TensorDesc(ShapeOf(b), (DataType)b->dtype);
-  user_op::InferContext pctx(in, attrs);
+  r->nd_sbp["b"] = pl.b_sbp;
+  for (const std::string& o : op->outputs) {
+    r->nd_sbp[o] = pl.out_sbp;
+    r->logical[o] = lctx.OutputTensorDesc(o, 0);
+  }
+  user_op::InferContext pctx(r->in, r->attrs);
   pctx.SetParallel(ParallelContext(pl.parallel_id, pl.parallel_num()), ParallelDesc(pl.hierarchy),
-                   {{"out", pl.out_sbp}, {"b", pl.b_sbp}}, {{"out", *logical_out}});
+                   r->nd_sbp, r->logical);
   JUST(op->physical_infer(&pctx));
   JUST(op->dtype_infer(&pctx));
-  *physical_out = pctx.OutputTensorDesc("out", 0);
+  for (const std::string& o : op->outputs) r->physical[o] = pctx.OutputTensorDesc(o, 0);
   return Maybe<void>::Ok();
 }
-
-struct KernelEntry {
-  const user_op::OpKernelRegistryResult* reg;
-  std::unique_ptr<user_op::OpKernel> kernel;
-};
 
 // Kernel objects are shared and const, cached per registration (stateful_opkernel.cpp:887-908).
 const user_op::OpKernel* GetKernel(const user_op::OpKernelRegistryResult* reg) {
@@ -156,15 +158,6 @@ const user_op::OpKernel* GetKernel(const user_op::OpKernelRegistryResult* reg) {
   auto& slot = cache[reg];
   if (!slot) slot.reset(reg->create_fn());
   return slot.get();
-}
-
-Maybe<void> Choose(const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* b, int device,
-                   const user_op::OpKernelRegistryResult** reg) {
-  user_op::KernelRegContext rc;
-  rc.device_type_ = device < 0 ? DeviceType::kCPU : DeviceType::kHIP;
-  rc.dtypes[{"out", 0}] = (DataType)b->dtype;
-  rc.dtypes[{"a_csr_row_ptr", 0}] = (DataType)row_ptr->dtype;
-  return user_op::UserOpRegistryMgr::Get().GetOpKernelRegistryResult("spmm_csr", rc, reg);
 }
 
 // The eager op's kernel states: one per (kernel registration, device), as OneFlow's functor
@@ -190,96 +183,118 @@ user_op::OpKernelState* EagerKernelState(const user_op::OpKernelRegistryResult* 
   return raw;
 }
 
-// functional::SpmmCsr on a local or global tensor set: inference, kernel choice, then either the
-// tmp size (tmp_size_out != NULL) or the kernel's cache init + Compute on the stream.  `state`:
-// the compiled job's own kernel state (NULL: the eager op's, per registration and device).
-int RunSpmmCsr(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
-               const ofx_tensor_desc* values, int64_t m, int64_t k, const ofx_tensor_desc* b,
-               int64_t b_logical_cols, ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
-               const Placement& pl, int num_threads, size_t* tmp_size_out, int64_t static_csr = 0,
-               std::shared_ptr<user_op::OpKernelState>* state = nullptr) {
-  user_op::TensorDesc logical_od, od;
-  int rc = ToStatus(Infer(row_ptr, col_idx, values, m, k, b, b_logical_cols, pl, &logical_od, &od));
-  if (rc) return rc;
+// Eager dispatch of a registered user op on one rank of a placement (a local call is the 1-device
+// placement): inference -> kernel choice (HOB on every arg's dtype) -> the tmp size (tmp_size_out
+// != NULL) or output check, the kernel's cache init and Compute on the stream.  `state`: the
+// compiled job's own kernel state (NULL: the eager op's, per registration and device, and only
+// for a static CSR).
+Maybe<void> RunUserOp(const std::string& op_name, const std::vector<Arg>& ins,
+                      const std::vector<Arg>& outs, const user_op::AttrMap& call_attrs, void* stream,
+                      void* tmp, size_t tmp_bytes, size_t* tmp_size_out,
+                      const Placement& pl = Placement(), int64_t b_logical_cols = -1,
+                      int num_threads = 0,
+                      std::shared_ptr<user_op::OpKernelState>* state = nullptr) {
+  Inferred inf;
+  JUST(InferUserOp(op_name, ins, call_attrs, pl, b_logical_cols, &inf));
+  const int device = ins.front().d->device;
+  user_op::KernelRegContext rc;
+  rc.device_type_ = device < 0 ? DeviceType::kCPU : DeviceType::kHIP;
+  for (const Arg& a : ins) rc.dtypes[{a.name, 0}] = (DataType)a.d->dtype;
+  for (const auto& o : inf.physical) rc.dtypes[{o.first, 0}] = o.second.data_type();
   const user_op::OpKernelRegistryResult* reg = nullptr;
-  rc = ToStatus(Choose(row_ptr, b, b->device, &reg));
-  if (rc) return rc;
+  JUST(user_op::UserOpRegistryMgr::Get().GetOpKernelRegistryResult(op_name, rc, &reg));
   if (tmp_size_out) {
     user_op::InferSizeContext sc;
-    sc.descs[{"a_csr_row_ptr", 0}] = user_op::TensorDesc(ShapeOf(row_ptr), (DataType)row_ptr->dtype);
-    sc.descs[{"a_csr_col_idx", 0}] = user_op::TensorDesc(ShapeOf(col_idx), (DataType)col_idx->dtype);
-    sc.descs[{"b", 0}] = user_op::TensorDesc(ShapeOf(b), (DataType)b->dtype);
-    sc.attrs = {{"a_num_rows", m}, {"a_num_cols", k}};
-    sc.logical["out"] = logical_od;
+    sc.descs = inf.in;
+    sc.attrs = inf.attrs;
+    sc.logical = inf.logical;
     *tmp_size_out = reg->infer_tmp_size ? reg->infer_tmp_size(&sc) : 0;
-    return OFX_OK;
+    return Maybe<void>::Ok();
   }
-  OFX_REQUIRE(out, OFX_EINVAL, "spmm_csr: out is NULL");
-  // an earlier launch's loud failure comes back here as OFX_EPLAN, before this call launches
-  // (the functional call is a library entry like ofx_spmm_csr; VERDICT r5 item 3)
-  OFX_TAKE_DEVICE_ERROR("spmm_csr");
-  rc = ToStatus(CheckDesc(out, "out"));
-  if (rc) return rc;
-  const int64_t phys_rows = od.shape().At(0);
-  OFX_REQUIRE(out->ndim == 2 && out->shape[0] == phys_rows && out->shape[1] == od.shape().At(1) &&
-                  out->dtype == (int32_t)od.data_type() && out->device == b->device,
-              OFX_EINVAL,
-              "spmm_csr: out must be a (%lld, %lld) tensor of dtype %d on device %d",
-              (long long)phys_rows, (long long)od.shape().At(1), (int)od.data_type(), b->device);
-  rc = ToStatus(CheckUnitColumnStride(out, "out"));
-  if (rc) return rc;
-  const user_op::OpKernel* kernel = GetKernel(reg);
-
-  user_op::Tensor t_rp(ShapeOf(row_ptr), (DataType)row_ptr->dtype, row_ptr->data);
-  user_op::Tensor t_ci(ShapeOf(col_idx), (DataType)col_idx->dtype, col_idx->data);
-  user_op::Tensor t_v(ShapeOf(values), (DataType)values->dtype, values->data);
-  user_op::Tensor t_b(ShapeOf(b), (DataType)b->dtype, b->data, b->ndim == 2 ? b->stride[0] : -1);
-  user_op::Tensor t_o(ShapeOf(out), (DataType)out->dtype, out->data, out->stride[0]);
+  std::vector<std::unique_ptr<user_op::Tensor>> hold;
+  std::map<std::pair<std::string, int32_t>, user_op::Tensor*> tensors;
+  auto add = [&](const Arg& a) {
+    hold.emplace_back(new user_op::Tensor(ShapeOf(a.d), (DataType)a.d->dtype, a.d->data,
+                                          a.d->ndim == 2 ? a.d->stride[0] : -1));
+    tensors[{a.name, 0}] = hold.back().get();
+  };
+  for (const Arg& a : ins) add(a);
+  bool all_outputs_empty = true;
+  for (const Arg& o : outs) {
+    CHECK_OR_RETURN(o.d != nullptr) << Error::RuntimeError() << op_name << ": NULL output " << o.name;
+    JUST(CheckDesc(o.d, o.name));
+    const user_op::TensorDesc& want = inf.physical.at(o.name);
+    CHECK_OR_RETURN(ShapeOf(o.d) == want.shape() && (DataType)o.d->dtype == want.data_type() &&
+                    o.d->device == device)
+        << Error::RuntimeError() << op_name << ": output " << o.name << " must be "
+        << want.shape().ToString() << " of dtype " << DataType_Name(want.data_type());
+    JUST(CheckUnitColumnStride(o.d, o.name));
+    add(o);
+    all_outputs_empty = all_outputs_empty && want.shape().elem_cnt() == 0;
+  }
   user_op::Tensor t_tmp(Shape({(int64_t)tmp_bytes}), kChar, tmp);
-  std::map<std::pair<std::string, int32_t>, user_op::Tensor*> tensors = {
-      {{"a_csr_row_ptr", 0}, &t_rp}, {{"a_csr_col_idx", 0}, &t_ci}, {{"a_csr_values", 0}, &t_v},
-      {{"b", 0}, &t_b},              {{"out", 0}, &t_o}};
   if (tmp) tensors[{"tmp_buffer", 0}] = &t_tmp;
-  const DeviceType dev = b->device < 0 ? DeviceType::kCPU : DeviceType::kHIP;
   ep::CpuStream cpu_stream(num_threads);
-  ep::HipStream hip_stream(stream, b->device);
-  ep::Stream* s = dev == DeviceType::kCPU ? static_cast<ep::Stream*>(&cpu_stream)
-                                          : static_cast<ep::Stream*>(&hip_stream);
-  // the op's attributes: the registered defaults, then this call's values
-  user_op::AttrMap attrs;
-  if (const user_op::OpRegistryResult* op =
-          user_op::UserOpRegistryMgr::Get().GetOpRegistryResult("spmm_csr"))
-    for (const auto& a : op->attrs) attrs[a.first] = a.second;
-  attrs["a_num_rows"] = m;
-  attrs["a_num_cols"] = k;
-  attrs["static_csr"] = static_csr;
+  ep::HipStream hip_stream(stream, device);
+  ep::Stream* s = device < 0 ? static_cast<ep::Stream*>(&cpu_stream) : static_cast<ep::Stream*>(&hip_stream);
+  user_op::KernelComputeContext ctx(s, tensors, inf.attrs, rc.device_type());
+  const user_op::OpKernel* kernel = GetKernel(reg);
+  const ParallelContext pc(pl.parallel_id, pl.parallel_num());
+  auto sc = inf.attrs.find("static_csr");
   user_op::OpKernelState* kstate = nullptr;
   if (state != nullptr) {
     if (!*state) {
       // a compiled op's launches are ordered on its one (named) stream
-      user_op::KernelInitContext ictx(ParallelContext(pl.parallel_id, pl.parallel_num()),
-                                      ParallelDesc(pl.hierarchy), dev, "compiled_job");
+      user_op::KernelInitContext ictx(pc, ParallelDesc(pl.hierarchy), rc.device_type(),
+                                      "compiled_job");
       *state = kernel->CreateOpKernelState(&ictx);
     }
     kstate = state->get();
-  } else if (static_csr != 0) {
-    kstate = EagerKernelState(reg, kernel, b->device, dev);
+  } else if (sc != inf.attrs.end() && static_cast<int64_t>(sc->second) != 0) {
+    // a static CSR's plan lives in the eager op's kernel state (per registration and device)
+    kstate = EagerKernelState(reg, kernel, device, rc.device_type());
   }
-  user_op::KernelCacheContext cache_ctx(ParallelContext(pl.parallel_id, pl.parallel_num()),
-                                        ParallelDesc(pl.hierarchy),
-                                        {{"out", pl.out_sbp}, {"b", pl.b_sbp}},
-                                        {{"out", logical_od}}, dev);
-  user_op::KernelComputeContext ctx(s, tensors, attrs, dev);
+  user_op::KernelCacheContext cache_ctx(pc, ParallelDesc(pl.hierarchy), inf.nd_sbp, inf.logical,
+                                        rc.device_type());
   try {
     std::shared_ptr<user_op::OpKernelCache> cache = kernel->InitOpKernelCache(&cache_ctx);
-    if (phys_rows == 0 || od.shape().At(1) == 0) {
-      if (!kernel->AlwaysComputeWhenAllOutputsEmpty()) return OFX_OK;
-    }
+    if (all_outputs_empty && !kernel->AlwaysComputeWhenAllOutputsEmpty()) return Maybe<void>::Ok();
     kernel->Compute(&ctx, kstate, cache.get());
   } catch (const KernelCheckError& e) {
-    return ofx::fail(OFX_EINVAL, "%s", e.msg.c_str());
+    return Maybe<void>("KernelCheckError", e.msg);
   }
+  return Maybe<void>::Ok();
+}
+
+// The call's ofx_spmm_attrs (NULL: the defaults), checked as a versioned struct: its static_csr.
+int ReadStaticCsr(const ofx_spmm_attrs* attrs, const char* op_name, int64_t* static_csr) {
+  *static_csr = 0;
+  if (attrs == nullptr) return OFX_OK;
+  const uint32_t min_size = OFX_SPMM_ATTRS_MIN_SIZE;
+  const char* why = ofx::versioned_struct_problem(attrs, min_size);
+  OFX_REQUIRE(why == nullptr, OFX_EINVAL,
+              "%s: ofx_spmm_attrs %s (%u bytes): initialise it with OFX_SPMM_ATTRS_INIT", op_name,
+              why ? why : "", min_size);
+  *static_csr = attrs->static_csr;
   return OFX_OK;
+}
+
+// functional::SpmmCsr on a local or global tensor set.
+int SpmmCsr(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+            const ofx_tensor_desc* values, int64_t m, int64_t k, const ofx_tensor_desc* b,
+            int64_t b_logical_cols, ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+            const Placement& pl, int num_threads, size_t* tmp_size_out, int64_t static_csr = 0,
+            std::shared_ptr<user_op::OpKernelState>* state = nullptr) {
+  // an earlier launch's loud failure comes back here as OFX_EPLAN, before this call launches
+  // (the functional call is a library entry like ofx_spmm_csr; VERDICT r5 item 3)
+  if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr");
+  return ToStatus(RunUserOp("spmm_csr",
+                            {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                             {"a_csr_values", values}, {"b", b}},
+                            {{"out", out}},
+                            {{"a_num_rows", m}, {"a_num_cols", k}, {"static_csr", static_csr}},
+                            stream, tmp, tmp_bytes, tmp_size_out, pl, b_logical_cols, num_threads,
+                            state));
 }
 
 }  // namespace
@@ -294,8 +309,8 @@ int SpmmCsrGlobalWithState(void* stream, const ofx_tensor_desc* row_ptr,
   Placement pl;
   int rc = ToStatus(MakePlacement(hierarchy_ndim, hierarchy, out_split_axes, parallel_id, &pl));
   if (rc) return rc;
-  return RunSpmmCsr(stream, row_ptr, col_idx, values, m, k, b, b_logical_cols, out, tmp,
-                    tmp_bytes, pl, 0, nullptr, static_csr, state);
+  return SpmmCsr(stream, row_ptr, col_idx, values, m, k, b, b_logical_cols, out, tmp, tmp_bytes,
+                 pl, 0, nullptr, static_csr, state);
 }
 
 }  // namespace oneflow
@@ -308,12 +323,16 @@ extern "C" int ofx_functional_spmm_csr_infer(const ofx_tensor_desc* row_ptr,
                                              int64_t a_num_cols, const ofx_tensor_desc* b,
                                              ofx_tensor_desc* out) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    user_op::TensorDesc lod, od;
-    int rc = ToStatus(Infer(row_ptr, col_idx, values, a_num_rows, a_num_cols, b, -1, Placement(),
-                            &lod, &od));
+    Inferred inf;
+    int rc = ToStatus(InferUserOp("spmm_csr",
+                                  {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                                   {"a_csr_values", values}, {"b", b}},
+                                  {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols}},
+                                  Placement(), -1, &inf));
     if (rc) return rc;
     rc = ToStatus(CheckDesc(out, "out"));
     if (rc) return rc;
+    const user_op::TensorDesc& od = inf.physical.at("out");
     if (out) {
       out->dtype = od.data_type();
       out->ndim = (int32_t)od.shape().NumAxes();
@@ -331,8 +350,8 @@ extern "C" int ofx_functional_spmm_csr_tmp_size(const ofx_tensor_desc* row_ptr,
                                                 size_t* bytes) {
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_REQUIRE(bytes, OFX_EINVAL, "spmm_csr_tmp_size: bytes is NULL");
-    return RunSpmmCsr(nullptr, row_ptr, col_idx, values, a_num_rows, a_num_cols, b, -1, nullptr,
-                      nullptr, 0, Placement(), 0, bytes);
+    return SpmmCsr(nullptr, row_ptr, col_idx, values, a_num_rows, a_num_cols, b, -1, nullptr,
+                   nullptr, 0, Placement(), 0, bytes);
   });
 }
 
@@ -342,13 +361,10 @@ extern "C" int ofx_functional_spmm_csr_global(
     const ofx_tensor_desc* b, int64_t b_logical_cols, ofx_tensor_desc* out, void* tmp,
     size_t tmp_bytes, int hierarchy_ndim, const int64_t* hierarchy, const int32_t* out_split_axes,
     int64_t parallel_id, int num_threads, size_t* tmp_size_out) {
-  return ::ofx::guarded(__func__, [&]() -> int {
-    Placement pl;
-    int rc = ToStatus(MakePlacement(hierarchy_ndim, hierarchy, out_split_axes, parallel_id, &pl));
-    if (rc) return rc;
-    return RunSpmmCsr(stream, row_ptr, col_idx, values, a_num_rows, a_num_cols, b, b_logical_cols,
-                      out, tmp, tmp_bytes, pl, num_threads, tmp_size_out);
-  });
+  return ofx_functional_spmm_csr_global_attrs(stream, row_ptr, col_idx, values, a_num_rows,
+                                              a_num_cols, b, b_logical_cols, out, tmp, tmp_bytes,
+                                              hierarchy_ndim, hierarchy, out_split_axes,
+                                              parallel_id, num_threads, tmp_size_out, nullptr);
 }
 
 extern "C" int ofx_functional_spmm_csr_global_attrs(
@@ -358,19 +374,13 @@ extern "C" int ofx_functional_spmm_csr_global_attrs(
     size_t tmp_bytes, int hierarchy_ndim, const int64_t* hierarchy, const int32_t* out_split_axes,
     int64_t parallel_id, int num_threads, size_t* tmp_size_out, const ofx_spmm_attrs* attrs) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    int64_t static_csr = 0;
-    if (attrs != nullptr) {
-      const char* why = ofx::versioned_struct_problem(attrs, OFX_SPMM_ATTRS_MIN_SIZE);
-      OFX_REQUIRE(why == nullptr, OFX_EINVAL,
-                  "spmm_csr: ofx_spmm_attrs %s (%u bytes): initialise it with OFX_SPMM_ATTRS_INIT",
-                  why ? why : "", OFX_SPMM_ATTRS_MIN_SIZE);
-      static_csr = attrs->static_csr;
-    }
+    int64_t static_csr;
+    if (int rc = ReadStaticCsr(attrs, "spmm_csr", &static_csr)) return rc;
     Placement pl;
-    int rc = ToStatus(MakePlacement(hierarchy_ndim, hierarchy, out_split_axes, parallel_id, &pl));
-    if (rc) return rc;
-    return RunSpmmCsr(stream, row_ptr, col_idx, values, a_num_rows, a_num_cols, b, b_logical_cols,
-                      out, tmp, tmp_bytes, pl, num_threads, tmp_size_out, static_csr);
+    if (int rc = ToStatus(MakePlacement(hierarchy_ndim, hierarchy, out_split_axes, parallel_id, &pl)))
+      return rc;
+    return SpmmCsr(stream, row_ptr, col_idx, values, a_num_rows, a_num_cols, b, b_logical_cols,
+                   out, tmp, tmp_bytes, pl, num_threads, tmp_size_out, static_csr);
   });
 }
 
@@ -413,8 +423,8 @@ extern "C" int ofx_functional_spmm_csr(void* stream, const ofx_tensor_desc* row_
                                        int64_t a_num_cols, const ofx_tensor_desc* b,
                                        ofx_tensor_desc* out, void* tmp, size_t tmp_bytes) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    return RunSpmmCsr(stream, row_ptr, col_idx, values, a_num_rows, a_num_cols, b, -1, out, tmp,
-                      tmp_bytes, Placement(), 0, nullptr);
+    return SpmmCsr(stream, row_ptr, col_idx, values, a_num_rows, a_num_cols, b, -1, out, tmp,
+                   tmp_bytes, Placement(), 0, nullptr);
   });
 }
 
@@ -473,132 +483,7 @@ extern "C" int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len) {
 
 // ---- gradient functors: functional::SddmmCsr / functional::CsrTranspose ----------------------
 // The grad function of spmm_csr calls these; the Python autograd binding
-// (oneflow_spmm/autograd.py) goes through the same entries.  Generic eager-local dispatch of a
-// registered user op: inference -> output check -> kernel choice (HOB on every arg's dtype) ->
-// tmp size or Compute.
-namespace oneflow {
-namespace {
-
-struct Arg {
-  const char* name;
-  const ofx_tensor_desc* d;
-};
-
-Maybe<void> RunUserOp(const std::string& op_name, const std::vector<Arg>& ins,
-                      const std::vector<Arg>& outs, const user_op::AttrMap& call_attrs, void* stream,
-                      void* tmp, size_t tmp_bytes, size_t* tmp_size_out,
-                      const Placement* pl = nullptr, int64_t b_logical_cols = -1,
-                      int num_threads = 0) {
-  // pl != NULL: a global op on one rank of a placement (input "b" and every output follow the
-  // placement's NdSbp, the other inputs are broadcast): logical inference on the logical b, then
-  // the op's physical inference, and the kernel's OpKernelCache from the same placement.
-  const user_op::OpRegistryResult* op = user_op::UserOpRegistryMgr::Get().GetOpRegistryResult(op_name);
-  CHECK_OR_RETURN(op != nullptr) << Error::RuntimeError() << "op " << op_name << " is not registered";
-  // the op's attributes: the registered defaults, then this call's values
-  user_op::AttrMap attrs;
-  for (const auto& a : op->attrs) attrs[a.first] = a.second;
-  for (const auto& a : call_attrs) attrs[a.first] = a.second;
-  const int device = ins.front().d->device;
-  DescMap in;
-  for (const Arg& a : ins) {
-    CHECK_OR_RETURN(a.d != nullptr) << Error::RuntimeError() << op_name << ": NULL input " << a.name;
-    JUST(CheckDesc(a.d, a.name));
-    CHECK_OR_RETURN(a.d->ndim >= 1 && a.d->ndim <= 2)
-        << Error::RuntimeError() << op_name << ": " << a.name << " must be 1-D or 2-D";
-    CHECK_EQ_OR_RETURN(a.d->device, device)
-        << Error::RuntimeError() << op_name << ": expected all tensors on the same device";
-    JUST(CheckUnitColumnStride(a.d, a.name));
-    in[{a.name, 0}] = user_op::TensorDesc(ShapeOf(a.d), (DataType)a.d->dtype);
-  }
-  user_op::InferContext ictx(in, attrs);
-  std::map<std::string, NdSbp> nd_sbp;
-  std::map<std::string, user_op::TensorDesc> logical;
-  if (pl == nullptr) {
-    JUST(op->logical_infer(&ictx));
-  } else {
-    DescMap logical_in = in;
-    auto b_it = logical_in.find({"b", 0});
-    if (b_it != logical_in.end() && b_it->second.shape().NumAxes() == 2 && b_logical_cols >= 0) {
-      Shape b_logical = b_it->second.shape();
-      b_logical.Set(1, b_logical_cols);
-      b_it->second = user_op::TensorDesc(b_logical, b_it->second.data_type());
-    }
-    user_op::InferContext lctx(logical_in, attrs);
-    JUST(op->logical_infer(&lctx));
-    JUST(op->dtype_infer(&lctx));
-    nd_sbp["b"] = pl->b_sbp;
-    for (const std::string& o : op->outputs) {
-      nd_sbp[o] = pl->out_sbp;
-      logical[o] = lctx.OutputTensorDesc(o, 0);
-    }
-    ictx.SetParallel(ParallelContext(pl->parallel_id, pl->parallel_num()),
-                     ParallelDesc(pl->hierarchy), nd_sbp, logical);
-    JUST(op->physical_infer(&ictx));
-  }
-  JUST(op->dtype_infer(&ictx));
-  user_op::KernelRegContext rc;
-  rc.device_type_ = device < 0 ? DeviceType::kCPU : DeviceType::kHIP;
-  for (const Arg& a : ins) rc.dtypes[{a.name, 0}] = (DataType)a.d->dtype;
-  for (const std::string& o : op->outputs) rc.dtypes[{o, 0}] = ictx.OutputTensorDesc(o, 0).data_type();
-  const user_op::OpKernelRegistryResult* reg = nullptr;
-  JUST(user_op::UserOpRegistryMgr::Get().GetOpKernelRegistryResult(op_name, rc, &reg));
-  if (tmp_size_out) {
-    user_op::InferSizeContext sc;
-    sc.descs = in;
-    sc.attrs = attrs;
-    sc.logical = logical;
-    *tmp_size_out = reg->infer_tmp_size ? reg->infer_tmp_size(&sc) : 0;
-    return Maybe<void>::Ok();
-  }
-  std::vector<std::unique_ptr<user_op::Tensor>> hold;
-  std::map<std::pair<std::string, int32_t>, user_op::Tensor*> tensors;
-  auto add = [&](const Arg& a) {
-    hold.emplace_back(new user_op::Tensor(ShapeOf(a.d), (DataType)a.d->dtype, a.d->data,
-                                          a.d->ndim == 2 ? a.d->stride[0] : -1));
-    tensors[{a.name, 0}] = hold.back().get();
-  };
-  for (const Arg& a : ins) add(a);
-  for (const Arg& o : outs) {
-    CHECK_OR_RETURN(o.d != nullptr) << Error::RuntimeError() << op_name << ": NULL output " << o.name;
-    JUST(CheckDesc(o.d, o.name));
-    const user_op::TensorDesc& want = ictx.OutputTensorDesc(o.name, 0);
-    CHECK_OR_RETURN(ShapeOf(o.d) == want.shape() && (DataType)o.d->dtype == want.data_type() &&
-                    o.d->device == device)
-        << Error::RuntimeError() << op_name << ": output " << o.name << " must be "
-        << want.shape().ToString() << " of dtype " << DataType_Name(want.data_type());
-    JUST(CheckUnitColumnStride(o.d, o.name));
-    add(o);
-  }
-  user_op::Tensor t_tmp(Shape({(int64_t)tmp_bytes}), kChar, tmp);
-  if (tmp) tensors[{"tmp_buffer", 0}] = &t_tmp;
-  ep::CpuStream cpu_stream(num_threads);
-  ep::HipStream hip_stream(stream, device);
-  ep::Stream* s = device < 0 ? static_cast<ep::Stream*>(&cpu_stream) : static_cast<ep::Stream*>(&hip_stream);
-  user_op::KernelComputeContext ctx(s, tensors, attrs, rc.device_type());
-  const user_op::OpKernel* kernel = GetKernel(reg);
-  std::shared_ptr<user_op::OpKernelCache> cache;
-  // a static CSR's plan lives in the eager op's kernel state (per registration and device)
-  auto sc = attrs.find("static_csr");
-  user_op::OpKernelState* kstate = nullptr;
-  if (sc != attrs.end() && static_cast<int64_t>(sc->second) != 0)
-    kstate = EagerKernelState(reg, kernel, device, rc.device_type());
-  try {
-    if (pl != nullptr) {
-      user_op::KernelCacheContext cache_ctx(ParallelContext(pl->parallel_id, pl->parallel_num()),
-                                            ParallelDesc(pl->hierarchy), nd_sbp, logical,
-                                            rc.device_type());
-      cache = kernel->InitOpKernelCache(&cache_ctx);
-    }
-    kernel->Compute(&ctx, kstate, cache.get());
-  } catch (const KernelCheckError& e) {
-    return Maybe<void>("KernelCheckError", e.msg);
-  }
-  return Maybe<void>::Ok();
-}
-
-}  // namespace
-}  // namespace oneflow
-
+// (oneflow_spmm/autograd.py) goes through the same entries.  Through RunUserOp, as every op.
 extern "C" int ofx_functional_sddmm_csr(void* stream, const ofx_tensor_desc* row_ptr,
                                         const ofx_tensor_desc* col_idx, const ofx_tensor_desc* a,
                                         const ofx_tensor_desc* b, int64_t a_num_rows,
@@ -617,14 +502,8 @@ extern "C" int ofx_functional_sddmm_csr_attrs(void* stream, const ofx_tensor_des
                                               ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
                                               size_t* tmp_size_out, const ofx_spmm_attrs* attrs) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    int64_t static_csr = 0;
-    if (attrs != nullptr) {
-      const char* why = ofx::versioned_struct_problem(attrs, OFX_SPMM_ATTRS_MIN_SIZE);
-      OFX_REQUIRE(why == nullptr, OFX_EINVAL,
-                  "sddmm_csr: ofx_spmm_attrs %s (%u bytes): initialise it with "
-                  "OFX_SPMM_ATTRS_INIT", why ? why : "", OFX_SPMM_ATTRS_MIN_SIZE);
-      static_csr = attrs->static_csr;
-    }
+    int64_t static_csr;
+    if (int rc = ReadStaticCsr(attrs, "sddmm_csr", &static_csr)) return rc;
     return ToStatus(RunUserOp("sddmm_csr",
                               {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"a", a}, {"b", b}},
                               {{"out", out}},
@@ -669,14 +548,8 @@ extern "C" int ofx_functional_spmm_csr_gathered_attrs(
     int64_t a_num_rows, int64_t a_num_cols, ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
     size_t* tmp_size_out, const ofx_spmm_attrs* attrs) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    int64_t static_csr = 0;
-    if (attrs != nullptr) {
-      const char* why = ofx::versioned_struct_problem(attrs, OFX_SPMM_ATTRS_MIN_SIZE);
-      OFX_REQUIRE(why == nullptr, OFX_EINVAL,
-                  "spmm_csr_gathered: ofx_spmm_attrs %s (%u bytes): initialise it with "
-                  "OFX_SPMM_ATTRS_INIT", why ? why : "", OFX_SPMM_ATTRS_MIN_SIZE);
-      static_csr = attrs->static_csr;
-    }
+    int64_t static_csr;
+    if (int rc = ReadStaticCsr(attrs, "spmm_csr_gathered", &static_csr)) return rc;
     return ToStatus(RunUserOp("spmm_csr_gathered",
                               {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
                                {"a_csr_values", values}, {"values_perm", values_perm}, {"b", b}},
@@ -709,14 +582,8 @@ extern "C" int ofx_functional_fused_spmm_csr_attrs(
     int64_t a_num_rows, int64_t a_num_cols, int relu, ofx_tensor_desc* out, void* tmp,
     size_t tmp_bytes, size_t* tmp_size_out, const ofx_spmm_attrs* attrs) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    int64_t static_csr = 0;
-    if (attrs != nullptr) {
-      const char* why = ofx::versioned_struct_problem(attrs, OFX_SPMM_ATTRS_MIN_SIZE);
-      OFX_REQUIRE(why == nullptr, OFX_EINVAL,
-                  "fused_spmm_csr: ofx_spmm_attrs %s (%u bytes): initialise it with "
-                  "OFX_SPMM_ATTRS_INIT", why ? why : "", OFX_SPMM_ATTRS_MIN_SIZE);
-      static_csr = attrs->static_csr;
-    }
+    int64_t static_csr;
+    if (int rc = ReadStaticCsr(attrs, "fused_spmm_csr", &static_csr)) return rc;
     // an earlier launch's loud failure comes back here as OFX_EPLAN (as for spmm_csr)
     if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("fused_spmm_csr");
     std::vector<Arg> ins = {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
@@ -756,7 +623,7 @@ extern "C" int ofx_functional_spmm_csr_reduce(
                               outs,
                               {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols},
                                {"reduce", reduce}},
-                              stream, tmp, tmp_bytes, tmp_size_out, &pl, b_logical_cols,
+                              stream, tmp, tmp_bytes, tmp_size_out, pl, b_logical_cols,
                               num_threads));
   });
 }
@@ -811,12 +678,12 @@ int EdgeSoftmaxCsr(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tenso
   if (grad == nullptr)
     return ToStatus(RunUserOp("edge_softmax_csr",
                               {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"e", in}},
-                              {{"out", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                              {{"out", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, Placement(), -1,
                               num_threads));
   return ToStatus(RunUserOp("edge_softmax_csr_grad",
                             {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"y", in},
                              {"dy", grad}},
-                            {{"dx", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                            {{"dx", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, Placement(), -1,
                             num_threads));
 }
 
@@ -900,12 +767,12 @@ int EdgeSoftmaxCsrHeads(void* stream, const ofx_tensor_desc* row_ptr,
   if (grad == nullptr)
     return ToStatus(RunUserOp("edge_softmax_csr_heads",
                               {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"e", in}},
-                              {{"out", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                              {{"out", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, Placement(), -1,
                               num_threads));
   return ToStatus(RunUserOp("edge_softmax_csr_heads_grad",
                             {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"y", in},
                              {"dy", grad}},
-                            {{"dx", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, nullptr, -1,
+                            {{"dx", out}}, {}, stream, tmp, tmp_bytes, tmp_size_out, Placement(), -1,
                             num_threads));
 }
 

@@ -4,13 +4,12 @@
  * pattern as edge_softmax_kernel.cpp; device work through the C-ABI of include/ofx_spmm.h).
  */
 #include "oneflow/core/framework/framework.h"
+#include "oneflow/user/kernels/csr_kernel_util.h"
 #include "ofx_spmm.h"
 
 namespace oneflow {
 
 namespace {
-
-int DtCode(DataType dt) { return static_cast<int>(dt); }
 
 // GRAD: inputs y, dy [nnz, H] -> dx; else input e [nnz, H] -> out.
 template <DeviceType device_type, bool GRAD>
@@ -38,17 +37,15 @@ class EdgeSoftmaxCsrHeadsKernel final : public user_op::OpKernel,
                      name << ": the per-nonzero tensors should be contiguous [nnz, heads]");
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
-      void* ws = tmp ? tmp->mut_dptr() : nullptr;
-      const size_t ws_bytes = tmp ? (size_t)tmp->shape_view().elem_cnt() : 0;
+      const TmpBuffer tmp(ctx);
       void* stream = ctx->stream()->As<ep::HipStream>()->hip_stream();
       if (GRAD)
         rc = ofx_edge_softmax_csr_heads_grad(stream, idx_dt, val_dt, m, heads, nnz,
                                              row_ptr->dptr(), a->dptr(), dy->dptr(),
-                                             out->mut_dptr(), 0, m, ws, ws_bytes, nullptr);
+                                             out->mut_dptr(), 0, m, tmp.ptr, tmp.bytes, nullptr);
       else
         rc = ofx_edge_softmax_csr_heads(stream, idx_dt, val_dt, m, heads, nnz, row_ptr->dptr(),
-                                        a->dptr(), out->mut_dptr(), 0, m, ws, ws_bytes, nullptr);
+                                        a->dptr(), out->mut_dptr(), 0, m, tmp.ptr, tmp.bytes, nullptr);
     } else {
       const int threads = ctx->stream()->As<ep::CpuStream>()->num_threads();
       if (GRAD)
@@ -75,31 +72,15 @@ size_t InferEdgeSoftmaxHeadsTmpSize(user_op::InferSizeContext* ctx) {
   return rc == OFX_OK ? bytes : 0;
 }
 
-size_t NoTmp(user_op::InferSizeContext*) { return 0; }
-
 }  // namespace
 
-#define REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, dtype, itype)           \
-  REGISTER_USER_KERNEL(op)                                                                   \
-      .SetCreateFn<EdgeSoftmaxCsrHeadsKernel<device, grad>>()                                \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                  \
-                       && (user_op::HobDataType(outname, 0) == dtype)                        \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))               \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferEdgeSoftmaxHeadsTmpSize<grad> : NoTmp);
-
-#define REGISTER_EDGE_SOFTMAX_HEADS_KERNEL_ALL(op, grad, outname, device)                     \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kFloat, kInt32)               \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kFloat, kInt64)               \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kDouble, kInt32)              \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kDouble, kInt64)              \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kFloat16, kInt32)             \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kFloat16, kInt64)             \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kBFloat16, kInt32)            \
-  REGISTER_EDGE_SOFTMAX_HEADS_KERNEL(op, grad, outname, device, kBFloat16, kInt64)
-
-REGISTER_EDGE_SOFTMAX_HEADS_KERNEL_ALL("edge_softmax_csr_heads", false, "out", DeviceType::kCPU)
-REGISTER_EDGE_SOFTMAX_HEADS_KERNEL_ALL("edge_softmax_csr_heads", false, "out", DeviceType::kHIP)
-REGISTER_EDGE_SOFTMAX_HEADS_KERNEL_ALL("edge_softmax_csr_heads_grad", true, "dx", DeviceType::kCPU)
-REGISTER_EDGE_SOFTMAX_HEADS_KERNEL_ALL("edge_softmax_csr_heads_grad", true, "dx", DeviceType::kHIP)
+REGISTER_CSR_KERNEL_ALL_DTYPES("edge_softmax_csr_heads", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               EdgeSoftmaxCsrHeadsKernel<DeviceType::kCPU, false>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("edge_softmax_csr_heads", "out", "a_csr_row_ptr", DeviceType::kHIP, InferEdgeSoftmaxHeadsTmpSize<false>,
+                               EdgeSoftmaxCsrHeadsKernel<DeviceType::kHIP, false>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("edge_softmax_csr_heads_grad", "dx", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               EdgeSoftmaxCsrHeadsKernel<DeviceType::kCPU, true>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("edge_softmax_csr_heads_grad", "dx", "a_csr_row_ptr", DeviceType::kHIP, InferEdgeSoftmaxHeadsTmpSize<true>,
+                               EdgeSoftmaxCsrHeadsKernel<DeviceType::kHIP, true>)
 
 }  // namespace oneflow

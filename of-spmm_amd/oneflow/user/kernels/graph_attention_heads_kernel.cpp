@@ -5,13 +5,12 @@
  * attn [nnz, H], the latter also the HIP kernel's hand-off buffer between its phases.
  */
 #include "oneflow/core/framework/framework.h"
+#include "oneflow/user/kernels/csr_kernel_util.h"
 #include "ofx_spmm.h"
 
 namespace oneflow {
 
 namespace {
-
-int DtCode(DataType dt) { return static_cast<int>(dt); }
 
 template <DeviceType device_type>
 class GraphAttentionCsrHeadsKernel final : public user_op::OpKernel,
@@ -39,15 +38,13 @@ class GraphAttentionCsrHeadsKernel final : public user_op::OpKernel,
     const int idx_dt = DtCode(row_ptr->data_type()), val_dt = DtCode(k->data_type());
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
-      void* ws = tmp ? tmp->mut_dptr() : nullptr;
-      const size_t ws_bytes = tmp ? (size_t)tmp->shape_view().elem_cnt() : 0;
+      const TmpBuffer tmp(ctx);
       void* stream = ctx->stream()->As<ep::HipStream>()->hip_stream();
       rc = ofx_graph_attention_csr_heads(stream, idx_dt, val_dt, m, kk, heads, d, nnz,
                                          row_ptr->dptr(), col_idx->dptr(), q->dptr(),
                                          q->row_stride(), k->dptr(), k->row_stride(), v->dptr(),
                                          v->row_stride(), out->mut_dptr(), out->row_stride(),
-                                         attn->mut_dptr(), 0, m, ws, ws_bytes, nullptr);
+                                         attn->mut_dptr(), 0, m, tmp.ptr, tmp.bytes, nullptr);
     } else {
       const int threads = ctx->stream()->As<ep::CpuStream>()->num_threads();
       rc = ofx_graph_attention_csr_heads_cpu(threads, idx_dt, val_dt, m, kk, heads, d, nnz,
@@ -74,29 +71,11 @@ size_t InferGraphAttentionTmpSize(user_op::InferSizeContext* ctx) {
   return rc == OFX_OK ? bytes : 0;
 }
 
-size_t NoTmp(user_op::InferSizeContext*) { return 0; }
-
 }  // namespace
 
-#define REGISTER_GRAPH_ATTENTION_KERNEL(device, dtype, itype)                                \
-  REGISTER_USER_KERNEL("graph_attention_csr_heads")                                          \
-      .SetCreateFn<GraphAttentionCsrHeadsKernel<device>>()                                   \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                  \
-                       && (user_op::HobDataType("out", 0) == dtype)                          \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))               \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferGraphAttentionTmpSize : NoTmp);
-
-#define REGISTER_GRAPH_ATTENTION_KERNEL_ALL(device)                 \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kFloat, kInt32)           \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kFloat, kInt64)           \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kDouble, kInt32)          \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kDouble, kInt64)          \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kFloat16, kInt32)         \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kFloat16, kInt64)         \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kBFloat16, kInt32)        \
-  REGISTER_GRAPH_ATTENTION_KERNEL(device, kBFloat16, kInt64)
-
-REGISTER_GRAPH_ATTENTION_KERNEL_ALL(DeviceType::kCPU)
-REGISTER_GRAPH_ATTENTION_KERNEL_ALL(DeviceType::kHIP)
+REGISTER_CSR_KERNEL_ALL_DTYPES("graph_attention_csr_heads", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               GraphAttentionCsrHeadsKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("graph_attention_csr_heads", "out", "a_csr_row_ptr", DeviceType::kHIP, InferGraphAttentionTmpSize,
+                               GraphAttentionCsrHeadsKernel<DeviceType::kHIP>)
 
 }  // namespace oneflow

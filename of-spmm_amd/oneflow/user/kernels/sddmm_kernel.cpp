@@ -4,14 +4,13 @@
  * work through the C-ABI of include/ofx_spmm.h).
  */
 #include "oneflow/core/framework/framework.h"
+#include "oneflow/user/kernels/csr_kernel_util.h"
 #include "oneflow/user/kernels/spmm_plan_state.h"
 #include "ofx_spmm.h"
 
 namespace oneflow {
 
 namespace {
-
-int DtCode(DataType dt) { return static_cast<int>(dt); }
 
 template <DeviceType device_type>
 class SddmmCsrKernel final : public user_op::OpKernel, public user_op::CudaGraphSupport {
@@ -41,9 +40,9 @@ class SddmmCsrKernel final : public user_op::OpKernel, public user_op::CudaGraph
     const int idx_dt = DtCode(row_ptr->data_type()), val_dt = DtCode(b->data_type());
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
-      void* ws = tmp ? tmp->mut_dptr() : nullptr;
-      size_t ws_bytes = tmp ? (size_t)tmp->shape_view().elem_cnt() : 0;
+      const TmpBuffer tmp(ctx);
+      void* ws = tmp.ptr;  // replaced by a static plan's own workspace
+      size_t ws_bytes = tmp.bytes;
       ep::HipStream* hs = ctx->stream()->As<ep::HipStream>();
       void* stream = hs->hip_stream();
       ofx_spmm_options opts = OFX_SPMM_OPTIONS_INIT;
@@ -100,12 +99,11 @@ class CsrTransposeKernel final : public user_op::OpKernel {
     const int idx_dt = DtCode(row_ptr->data_type());
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
+      const TmpBuffer tmp(ctx);
       rc = ofx_csr_transpose(ctx->stream()->As<ep::HipStream>()->hip_stream(), idx_dt, m, k, nnz,
                              row_ptr->dptr(), col_idx->dptr(), out_rp->mut_dptr(),
                              out_ci->mut_dptr(), out_perm->mut_dptr(),
-                             tmp ? tmp->mut_dptr() : nullptr,
-                             tmp ? (size_t)tmp->shape_view().elem_cnt() : 0);
+                             tmp.ptr, tmp.bytes);
     } else {
       rc = ofx_csr_transpose_cpu(idx_dt, m, k, nnz, row_ptr->dptr(), col_idx->dptr(),
                                  out_rp->mut_dptr(), out_ci->mut_dptr(), out_perm->mut_dptr());
@@ -135,30 +133,12 @@ size_t InferTransposeTmpSize(user_op::InferSizeContext* ctx) {
   return rc == OFX_OK ? bytes : 0;
 }
 
-size_t NoTmp(user_op::InferSizeContext*) { return 0; }
-
 }  // namespace
 
-#define REGISTER_SDDMM_CSR_KERNEL(device, dtype, itype)                                       \
-  REGISTER_USER_KERNEL("sddmm_csr")                                                         \
-      .SetCreateFn<SddmmCsrKernel<device>>()                                                \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                 \
-                       && (user_op::HobDataType("out", 0) == dtype)                         \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))              \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferSddmmTmpSize : NoTmp);
-
-#define REGISTER_SDDMM_CSR_KERNEL_ALL(device)                                                 \
-  REGISTER_SDDMM_CSR_KERNEL(device, kFloat, kInt32)                                          \
-  REGISTER_SDDMM_CSR_KERNEL(device, kFloat, kInt64)                                          \
-  REGISTER_SDDMM_CSR_KERNEL(device, kDouble, kInt32)                                         \
-  REGISTER_SDDMM_CSR_KERNEL(device, kDouble, kInt64)                                         \
-  REGISTER_SDDMM_CSR_KERNEL(device, kFloat16, kInt32)                                        \
-  REGISTER_SDDMM_CSR_KERNEL(device, kFloat16, kInt64)                                        \
-  REGISTER_SDDMM_CSR_KERNEL(device, kBFloat16, kInt32)                                       \
-  REGISTER_SDDMM_CSR_KERNEL(device, kBFloat16, kInt64)
-
-REGISTER_SDDMM_CSR_KERNEL_ALL(DeviceType::kCPU)
-REGISTER_SDDMM_CSR_KERNEL_ALL(DeviceType::kHIP)
+REGISTER_CSR_KERNEL_ALL_DTYPES("sddmm_csr", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               SddmmCsrKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("sddmm_csr", "out", "a_csr_row_ptr", DeviceType::kHIP, InferSddmmTmpSize,
+                               SddmmCsrKernel<DeviceType::kHIP>)
 
 #define REGISTER_CSR_TRANSPOSE_KERNEL(device, itype)                                          \
   REGISTER_USER_KERNEL("csr_transpose")                                                     \

@@ -4,13 +4,12 @@
  * device work through the C-ABI of include/ofx_spmm.h).
  */
 #include "oneflow/core/framework/framework.h"
+#include "oneflow/user/kernels/csr_kernel_util.h"
 #include "ofx_spmm.h"
 
 namespace oneflow {
 
 namespace {
-
-int DtCode(DataType dt) { return static_cast<int>(dt); }
 
 // SDDMM: inputs a, b -> out [nnz, H]; else inputs a_csr_values [nnz, H], b -> out [M, N].
 template <DeviceType device_type, bool SDDMM>
@@ -37,18 +36,16 @@ class CsrHeadsKernel final : public user_op::OpKernel, public user_op::CudaGraph
     const char* name = SDDMM ? "sddmm_csr_heads" : "spmm_csr_heads";
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
-      void* ws = tmp ? tmp->mut_dptr() : nullptr;
-      const size_t ws_bytes = tmp ? (size_t)tmp->shape_view().elem_cnt() : 0;
+      const TmpBuffer tmp(ctx);
       void* stream = ctx->stream()->As<ep::HipStream>()->hip_stream();
       if (SDDMM)
         rc = ofx_sddmm_csr_heads(stream, idx_dt, val_dt, m, k, heads, d, nnz, row_ptr->dptr(),
                                  col_idx->dptr(), x->dptr(), x->row_stride(), b->dptr(),
-                                 b->row_stride(), out->mut_dptr(), 0, m, ws, ws_bytes);
+                                 b->row_stride(), out->mut_dptr(), 0, m, tmp.ptr, tmp.bytes);
       else
         rc = ofx_spmm_csr_heads(stream, idx_dt, val_dt, m, k, heads, d, nnz, row_ptr->dptr(),
                                 col_idx->dptr(), x->dptr(), b->dptr(), b->row_stride(),
-                                out->mut_dptr(), out->row_stride(), 0, m, ws, ws_bytes, nullptr);
+                                out->mut_dptr(), out->row_stride(), 0, m, tmp.ptr, tmp.bytes, nullptr);
     } else {
       const int threads = ctx->stream()->As<ep::CpuStream>()->num_threads();
       if (SDDMM)
@@ -82,31 +79,15 @@ size_t InferHeadsTmpSize(user_op::InferSizeContext* ctx) {
   return rc == OFX_OK ? bytes : 0;
 }
 
-size_t NoTmp(user_op::InferSizeContext*) { return 0; }
-
 }  // namespace
 
-#define REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, dtype, itype)                            \
-  REGISTER_USER_KERNEL(op)                                                                   \
-      .SetCreateFn<CsrHeadsKernel<device, sddmm>>()                                          \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                  \
-                       && (user_op::HobDataType("out", 0) == dtype)                          \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))               \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferHeadsTmpSize<sddmm> : NoTmp);
-
-#define REGISTER_CSR_HEADS_KERNEL_ALL(op, sddmm, device)                                      \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kFloat, kInt32)                                \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kFloat, kInt64)                                \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kDouble, kInt32)                               \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kDouble, kInt64)                               \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kFloat16, kInt32)                              \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kFloat16, kInt64)                              \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kBFloat16, kInt32)                             \
-  REGISTER_CSR_HEADS_KERNEL(op, sddmm, device, kBFloat16, kInt64)
-
-REGISTER_CSR_HEADS_KERNEL_ALL("spmm_csr_heads", false, DeviceType::kCPU)
-REGISTER_CSR_HEADS_KERNEL_ALL("spmm_csr_heads", false, DeviceType::kHIP)
-REGISTER_CSR_HEADS_KERNEL_ALL("sddmm_csr_heads", true, DeviceType::kCPU)
-REGISTER_CSR_HEADS_KERNEL_ALL("sddmm_csr_heads", true, DeviceType::kHIP)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_heads", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               CsrHeadsKernel<DeviceType::kCPU, false>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_heads", "out", "a_csr_row_ptr", DeviceType::kHIP, InferHeadsTmpSize<false>,
+                               CsrHeadsKernel<DeviceType::kHIP, false>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("sddmm_csr_heads", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               CsrHeadsKernel<DeviceType::kCPU, true>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("sddmm_csr_heads", "out", "a_csr_row_ptr", DeviceType::kHIP, InferHeadsTmpSize<true>,
+                               CsrHeadsKernel<DeviceType::kHIP, true>)
 
 }  // namespace oneflow

@@ -11,6 +11,7 @@
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/core/functional/spmm_functor.h"
+#include "oneflow/user/kernels/csr_kernel_util.h"
 #include "oneflow/user/kernels/spmm_plan_state.h"
 #include "ofx_spmm.h"
 
@@ -69,8 +70,6 @@ ofx_spmm_options OptionsOf(const SpmmCsrOpKernelCache* cache) {
   if (cache != nullptr) o.split_threshold = ofx_spmm_default_split(cache->logical_n());
   return o;
 }
-
-int DtCode(DataType dt) { return static_cast<int>(dt); }
 
 // The static plan of an spmm_csr-family launch: key and workspace size from the launch's
 // shapes, row range and schedule; the plan built by ofx_spmm_csr_plan.
@@ -136,9 +135,9 @@ void ComputeSpmmCsr(user_op::KernelComputeContext* ctx, const user_op::OpKernelC
   const int act = relu ? OFX_ACT_RELU : OFX_ACT_NONE;
   int rc;
   if (device_type == DeviceType::kHIP) {
-    user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
-    void* ws = tmp ? tmp->mut_dptr() : nullptr;
-    size_t ws_bytes = tmp ? (size_t)tmp->shape_view().elem_cnt() : 0;
+    const TmpBuffer tmp(ctx);
+    void* ws = tmp.ptr;  // replaced by a static plan's own workspace
+    size_t ws_bytes = tmp.bytes;
     ep::HipStream* hs = ctx->stream()->As<ep::HipStream>();
     void* stream = hs->hip_stream();
     StaticPlan sp;
@@ -256,7 +255,7 @@ class SpmmCsrGatheredKernel final : public user_op::OpKernel, public user_op::Cu
     const user_op::Tensor* perm = ctx->Tensor4ArgNameAndIndex("values_perm", 0);
     const user_op::Tensor* b = ctx->Tensor4ArgNameAndIndex("b", 0);
     user_op::Tensor* out = ctx->Tensor4ArgNameAndIndex("out", 0);
-    user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
+    const TmpBuffer tmp(ctx);
     const int64_t m = ctx->Attr<int64_t>("a_num_rows");
     const int64_t k = ctx->Attr<int64_t>("a_num_cols");
     const int64_t n = out->shape_view().At(1);
@@ -274,8 +273,8 @@ class SpmmCsrGatheredKernel final : public user_op::OpKernel, public user_op::Cu
                                  << row_end - row_begin);
     const int idx_dt = DtCode(row_ptr->data_type());
     const int val_dt = DtCode(values->data_type());
-    void* ws = tmp ? tmp->mut_dptr() : nullptr;
-    size_t ws_bytes = tmp ? (size_t)tmp->shape_view().elem_cnt() : 0;
+    void* ws = tmp.ptr;  // replaced by a static plan's own workspace
+    size_t ws_bytes = tmp.bytes;
     int rc;
     if (device_type == DeviceType::kHIP) {
       ep::HipStream* hs = ctx->stream()->As<ep::HipStream>();
@@ -327,55 +326,17 @@ size_t InferSpmmCsrTmpSize(user_op::InferSizeContext* ctx) {
 
 }  // namespace
 
-#define REGISTER_SPMM_CSR_KERNEL_OF(op, kernel, device, dtype, itype)                          \
-  REGISTER_USER_KERNEL(op)                                                                    \
-      .SetCreateFn<kernel<device>>()                                                          \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                   \
-                       && (user_op::HobDataType("out", 0) == dtype)                           \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))                \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP                                           \
-                             ? std::function<size_t(user_op::InferSizeContext*)>(             \
-                                   InferSpmmCsrTmpSize)                                       \
-                             : std::function<size_t(user_op::InferSizeContext*)>(             \
-                                   [](user_op::InferSizeContext*) -> size_t { return 0; }));
-
-#define REGISTER_SPMM_CSR_KERNEL(device, dtype, itype)                                     \
-  REGISTER_SPMM_CSR_KERNEL_OF("spmm_csr", SpmmCsrKernel, device, dtype, itype)            \
-  REGISTER_SPMM_CSR_KERNEL_OF("fused_spmm_csr", FusedSpmmCsrKernel, device, dtype, itype)
-
-#define REGISTER_SPMM_CSR_KERNEL_ALL_INDEX(device, dtype) \
-  REGISTER_SPMM_CSR_KERNEL(device, dtype, kInt32)         \
-  REGISTER_SPMM_CSR_KERNEL(device, dtype, kInt64)
-
-#define REGISTER_SPMM_CSR_KERNEL_ALL(device)              \
-  REGISTER_SPMM_CSR_KERNEL_ALL_INDEX(device, kFloat)      \
-  REGISTER_SPMM_CSR_KERNEL_ALL_INDEX(device, kDouble)     \
-  REGISTER_SPMM_CSR_KERNEL_ALL_INDEX(device, kFloat16)    \
-  REGISTER_SPMM_CSR_KERNEL_ALL_INDEX(device, kBFloat16)
-
-REGISTER_SPMM_CSR_KERNEL_ALL(DeviceType::kCPU)
-REGISTER_SPMM_CSR_KERNEL_ALL(DeviceType::kHIP)
-
-#define REGISTER_SPMM_CSR_GATHERED_KERNEL(device, dtype, itype)                                \
-  REGISTER_USER_KERNEL("spmm_csr_gathered")                                                   \
-      .SetCreateFn<SpmmCsrGatheredKernel<device>>()                                           \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                   \
-                       && (user_op::HobDataType("out", 0) == dtype)                           \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))                \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferSpmmCsrTmpSize                     \
-                                                    : InferSpmmCsrGatheredCpuTmpSize);
-
-#define REGISTER_SPMM_CSR_GATHERED_KERNEL_ALL(device)                 \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kFloat, kInt32)           \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kFloat, kInt64)           \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kDouble, kInt32)          \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kDouble, kInt64)          \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kFloat16, kInt32)         \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kFloat16, kInt64)         \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kBFloat16, kInt32)        \
-  REGISTER_SPMM_CSR_GATHERED_KERNEL(device, kBFloat16, kInt64)
-
-REGISTER_SPMM_CSR_GATHERED_KERNEL_ALL(DeviceType::kCPU)
-REGISTER_SPMM_CSR_GATHERED_KERNEL_ALL(DeviceType::kHIP)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               SpmmCsrKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr", "out", "a_csr_row_ptr", DeviceType::kHIP, InferSpmmCsrTmpSize,
+                               SpmmCsrKernel<DeviceType::kHIP>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("fused_spmm_csr", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               FusedSpmmCsrKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("fused_spmm_csr", "out", "a_csr_row_ptr", DeviceType::kHIP, InferSpmmCsrTmpSize,
+                               FusedSpmmCsrKernel<DeviceType::kHIP>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_gathered", "out", "a_csr_row_ptr", DeviceType::kCPU, InferSpmmCsrGatheredCpuTmpSize,
+                               SpmmCsrGatheredKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_gathered", "out", "a_csr_row_ptr", DeviceType::kHIP, InferSpmmCsrTmpSize,
+                               SpmmCsrGatheredKernel<DeviceType::kHIP>)
 
 }  // namespace oneflow

@@ -8,13 +8,12 @@
  * needs no fix-up.  The hub schedule is the logical width's (numeric for sum / mean only).
  */
 #include "oneflow/core/framework/framework.h"
+#include "oneflow/user/kernels/csr_kernel_util.h"
 #include "ofx_spmm.h"
 
 namespace oneflow {
 
 namespace {
-
-int DtCode(DataType dt) { return static_cast<int>(dt); }
 
 class SpmmCsrReduceOpKernelCache final : public user_op::OpKernelCache {
  public:
@@ -95,13 +94,12 @@ class SpmmCsrReduceKernel final : public user_op::OpKernel, public user_op::Cuda
     const int idx_dt = DtCode(row_ptr->data_type()), val_dt = DtCode(values->data_type());
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
+      const TmpBuffer tmp(ctx);
       rc = ofx_spmm_csr_reduce(ctx->stream()->As<ep::HipStream>()->hip_stream(), idx_dt, val_dt, m,
                                k, n, nnz, row_ptr->dptr(), col_idx->dptr(), values->dptr(),
                                b->dptr(), b->row_stride(), out->mut_dptr(), out->row_stride(),
                                arg_ptr, ldarg, row_begin, row_end, reduce,
-                               tmp ? tmp->mut_dptr() : nullptr,
-                               tmp ? (size_t)tmp->shape_view().elem_cnt() : 0, &opts);
+                               tmp.ptr, tmp.bytes, &opts);
     } else {
       rc = ofx_spmm_csr_reduce_cpu(ctx->stream()->As<ep::CpuStream>()->num_threads(), idx_dt,
                                    val_dt, m, k, n, nnz, row_ptr->dptr(), col_idx->dptr(),
@@ -138,13 +136,12 @@ class SpmmCsrReduceGradBKernel final : public user_op::OpKernel, public user_op:
     ofx_spmm_options opts = OFX_SPMM_OPTIONS_INIT;
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
+      const TmpBuffer tmp(ctx);
       rc = ofx_spmm_csr_select(ctx->stream()->As<ep::HipStream>()->hip_stream(), idx_dt, val_dt, m,
                                k, n, nnz, rp_t->dptr(), ci_t->dptr(), perm->dptr(), values->dptr(),
                                arg->dptr(), arg->row_stride(), dy->dptr(), dy->row_stride(),
                                out->mut_dptr(), out->row_stride(), 0, k,
-                               tmp ? tmp->mut_dptr() : nullptr,
-                               tmp ? (size_t)tmp->shape_view().elem_cnt() : 0, &opts);
+                               tmp.ptr, tmp.bytes, &opts);
     } else {
       rc = ofx_spmm_csr_select_cpu(ctx->stream()->As<ep::CpuStream>()->num_threads(), idx_dt,
                                    val_dt, m, k, n, nnz, rp_t->dptr(), ci_t->dptr(), perm->dptr(),
@@ -180,13 +177,12 @@ class SpmmCsrReduceGradValuesKernel final : public user_op::OpKernel,
     const int idx_dt = DtCode(row_ptr->data_type()), val_dt = DtCode(b->data_type());
     int rc;
     if (device_type == DeviceType::kHIP) {
-      user_op::Tensor* tmp = ctx->Tensor4ArgNameAndIndex("tmp_buffer", 0);
+      const TmpBuffer tmp(ctx);
       rc = ofx_sddmm_csr_select(ctx->stream()->As<ep::HipStream>()->hip_stream(), idx_dt, val_dt, m,
                                 k, n, nnz, row_ptr->dptr(), col_idx->dptr(), arg->dptr(),
                                 arg->row_stride(), dy->dptr(), dy->row_stride(), b->dptr(),
                                 b->row_stride(), out->mut_dptr(), 0, m,
-                                tmp ? tmp->mut_dptr() : nullptr,
-                                tmp ? (size_t)tmp->shape_view().elem_cnt() : 0);
+                                tmp.ptr, tmp.bytes);
     } else {
       rc = ofx_sddmm_csr_select_cpu(ctx->stream()->As<ep::CpuStream>()->num_threads(), idx_dt,
                                     val_dt, m, k, n, nnz, row_ptr->dptr(), col_idx->dptr(),
@@ -236,41 +232,19 @@ size_t InferGradValuesTmpSize(user_op::InferSizeContext* ctx) {
   return rc == OFX_OK ? bytes : 0;
 }
 
-size_t NoTmp(user_op::InferSizeContext*) { return 0; }
-
 }  // namespace
 
-#define REGISTER_SPMM_REDUCE_KERNELS(device, dtype, itype)                                    \
-  REGISTER_USER_KERNEL("spmm_csr_reduce")                                                   \
-      .SetCreateFn<SpmmCsrReduceKernel<device>>()                                           \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                 \
-                       && (user_op::HobDataType("out", 0) == dtype)                         \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))              \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferReduceTmpSize : NoTmp);          \
-  REGISTER_USER_KERNEL("spmm_csr_reduce_grad_b")                                            \
-      .SetCreateFn<SpmmCsrReduceGradBKernel<device>>()                                      \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                 \
-                       && (user_op::HobDataType("out", 0) == dtype)                         \
-                       && (user_op::HobDataType("at_row_ptr", 0) == itype))                 \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferGradBTmpSize : NoTmp);           \
-  REGISTER_USER_KERNEL("spmm_csr_reduce_grad_values")                                       \
-      .SetCreateFn<SpmmCsrReduceGradValuesKernel<device>>()                                 \
-      .SetIsMatchedHob((user_op::HobDeviceType() == device)                                 \
-                       && (user_op::HobDataType("out", 0) == dtype)                         \
-                       && (user_op::HobDataType("a_csr_row_ptr", 0) == itype))              \
-      .SetInferTmpSizeFn(device == DeviceType::kHIP ? InferGradValuesTmpSize : NoTmp);
-
-#define REGISTER_SPMM_REDUCE_KERNELS_ALL(device)                                              \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kFloat, kInt32)                                       \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kFloat, kInt64)                                       \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kDouble, kInt32)                                      \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kDouble, kInt64)                                      \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kFloat16, kInt32)                                     \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kFloat16, kInt64)                                     \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kBFloat16, kInt32)                                    \
-  REGISTER_SPMM_REDUCE_KERNELS(device, kBFloat16, kInt64)
-
-REGISTER_SPMM_REDUCE_KERNELS_ALL(DeviceType::kCPU)
-REGISTER_SPMM_REDUCE_KERNELS_ALL(DeviceType::kHIP)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               SpmmCsrReduceKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce", "out", "a_csr_row_ptr", DeviceType::kHIP, InferReduceTmpSize,
+                               SpmmCsrReduceKernel<DeviceType::kHIP>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_b", "out", "at_row_ptr", DeviceType::kCPU, NoTmp,
+                               SpmmCsrReduceGradBKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_b", "out", "at_row_ptr", DeviceType::kHIP, InferGradBTmpSize,
+                               SpmmCsrReduceGradBKernel<DeviceType::kHIP>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_values", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
+                               SpmmCsrReduceGradValuesKernel<DeviceType::kCPU>)
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_values", "out", "a_csr_row_ptr", DeviceType::kHIP, InferGradValuesTmpSize,
+                               SpmmCsrReduceGradValuesKernel<DeviceType::kHIP>)
 
 }  // namespace oneflow

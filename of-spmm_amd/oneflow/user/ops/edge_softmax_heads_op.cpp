@@ -15,26 +15,11 @@
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/core/framework/op_generated.h"
+#include "oneflow/user/ops/csr_op_util.h"
 
 namespace oneflow {
 
 namespace {
-
-constexpr const char* kRowPtr = "a_csr_row_ptr";
-constexpr const char* kColIdx = "a_csr_col_idx";
-
-Maybe<void> CheckStructure(user_op::InferContext* ctx, int64_t* nnz) {
-  const Shape& rp = ctx->InputShape(kRowPtr, 0);
-  const Shape& ci = ctx->InputShape(kColIdx, 0);
-  CHECK_EQ_OR_RETURN(rp.NumAxes(), 1)
-      << Error::RuntimeError() << kRowPtr << " should be 1-D, got shape " << rp.ToString();
-  CHECK_GE_OR_RETURN(rp.At(0), 1)
-      << Error::RuntimeError() << kRowPtr << " should have a_num_rows + 1 elements. ";
-  CHECK_EQ_OR_RETURN(ci.NumAxes(), 1)
-      << Error::RuntimeError() << kColIdx << " should be 1-D, got shape " << ci.ToString();
-  *nnz = ci.At(0);
-  return Maybe<void>::Ok();
-}
 
 Maybe<void> CheckPerNonzeroHeads(user_op::InferContext* ctx, const char* name, int64_t nnz,
                                  int64_t* heads) {
@@ -47,37 +32,12 @@ Maybe<void> CheckPerNonzeroHeads(user_op::InferContext* ctx, const char* name, i
   return Maybe<void>::Ok();
 }
 
-Maybe<void> CheckDTypes(user_op::InferContext* ctx, const char* value, const char* op,
-                        DataType* dtype) {
-  const DataType index_dtype = ctx->InputDType(kRowPtr, 0);
-  CHECK_OR_RETURN(IsIndexDataType(index_dtype))
-      << Error::TypeError() << kRowPtr << " should be int32 or int64, got "
-      << DataType_Name(index_dtype);
-  CHECK_EQ_OR_RETURN(ctx->InputDType(kColIdx, 0), index_dtype)
-      << Error::TypeError() << kColIdx << " should have the dtype of " << kRowPtr << ". ";
-  *dtype = ctx->InputDType(value, 0);
-  CHECK_OR_RETURN(*dtype == kFloat || *dtype == kDouble || *dtype == kFloat16 ||
-                  *dtype == kBFloat16)
-      << Error::TypeError() << op << " supports float, double, float16, bfloat16; got "
-      << DataType_Name(*dtype);
-  return Maybe<void>::Ok();
-}
-
-Maybe<void> IndexInputsNoGrad(const user_op::GetInputArgModifier& GetInputArgModifierFn) {
-  for (const char* name : {kRowPtr, kColIdx}) {
-    user_op::InputArgModifier* modifier = GetInputArgModifierFn(name, 0);
-    CHECK_NOTNULL_OR_RETURN(modifier);
-    modifier->set_requires_grad(false);
-  }
-  return Maybe<void>::Ok();
-}
-
 }  // namespace
 
 // ---- edge_softmax_csr_heads -----------------------------------------------------------------------
 /* static */ Maybe<void> EdgeSoftmaxCsrHeadsOp::InferLogicalTensorDesc(user_op::InferContext* ctx) {
-  int64_t nnz = 0, heads = 0;
-  JUST(CheckStructure(ctx, &nnz));
+  int64_t m = 0, nnz = 0, heads = 0;
+  JUST(CheckCsrStructure(ctx, &m, &nnz));
   JUST(CheckPerNonzeroHeads(ctx, "e", nnz, &heads));
   ctx->SetOutputShape("out", 0, Shape({nnz, heads}));
   return Maybe<void>::Ok();
@@ -88,17 +48,12 @@ Maybe<void> IndexInputsNoGrad(const user_op::GetInputArgModifier& GetInputArgMod
 }
 /* static */ Maybe<void> EdgeSoftmaxCsrHeadsOp::GetSbp(user_op::SbpContext* ctx) {
   // all-broadcast only: a split along nnz would cut rows
-  ctx->NewBuilder()
-      .Broadcast(user_op::OpArg(kRowPtr, 0))
-      .Broadcast(user_op::OpArg(kColIdx, 0))
-      .Broadcast(user_op::OpArg("e", 0))
-      .Broadcast(user_op::OpArg("out", 0))
-      .Build();
-  return Maybe<void>::Ok();
+  return BroadcastAll(ctx, {"e", "out"});
 }
 /* static */ Maybe<void> EdgeSoftmaxCsrHeadsOp::InferDataType(user_op::InferContext* ctx) {
-  DataType dtype;
-  JUST(CheckDTypes(ctx, "e", "edge_softmax_csr_heads", &dtype));
+  JUST(CheckIndexDTypes(ctx));
+  const DataType dtype = ctx->InputDType("e", 0);
+  JUST(CheckValueDType(dtype, "edge_softmax_csr_heads"));
   ctx->SetOutputDType("out", 0, dtype);
   return Maybe<void>::Ok();
 }
@@ -110,8 +65,8 @@ Maybe<void> IndexInputsNoGrad(const user_op::GetInputArgModifier& GetInputArgMod
 // ---- edge_softmax_csr_heads_grad ------------------------------------------------------------------
 /* static */ Maybe<void> EdgeSoftmaxCsrHeadsGradOp::InferLogicalTensorDesc(
     user_op::InferContext* ctx) {
-  int64_t nnz = 0, heads = 0, heads_dy = 0;
-  JUST(CheckStructure(ctx, &nnz));
+  int64_t m = 0, nnz = 0, heads = 0, heads_dy = 0;
+  JUST(CheckCsrStructure(ctx, &m, &nnz));
   JUST(CheckPerNonzeroHeads(ctx, "y", nnz, &heads));
   JUST(CheckPerNonzeroHeads(ctx, "dy", nnz, &heads_dy));
   CHECK_EQ_OR_RETURN(heads_dy, heads)
@@ -126,18 +81,12 @@ Maybe<void> IndexInputsNoGrad(const user_op::GetInputArgModifier& GetInputArgMod
 }
 /* static */ Maybe<void> EdgeSoftmaxCsrHeadsGradOp::GetSbp(user_op::SbpContext* ctx) {
   // all-broadcast only, as the forward: the sum runs over the whole row
-  ctx->NewBuilder()
-      .Broadcast(user_op::OpArg(kRowPtr, 0))
-      .Broadcast(user_op::OpArg(kColIdx, 0))
-      .Broadcast(user_op::OpArg("y", 0))
-      .Broadcast(user_op::OpArg("dy", 0))
-      .Broadcast(user_op::OpArg("dx", 0))
-      .Build();
-  return Maybe<void>::Ok();
+  return BroadcastAll(ctx, {"y", "dy", "dx"});
 }
 /* static */ Maybe<void> EdgeSoftmaxCsrHeadsGradOp::InferDataType(user_op::InferContext* ctx) {
-  DataType dtype;
-  JUST(CheckDTypes(ctx, "y", "edge_softmax_csr_heads_grad", &dtype));
+  JUST(CheckIndexDTypes(ctx));
+  const DataType dtype = ctx->InputDType("y", 0);
+  JUST(CheckValueDType(dtype, "edge_softmax_csr_heads_grad"));
   CHECK_EQ_OR_RETURN(ctx->InputDType("dy", 0), dtype)
       << Error::TypeError() << "dy datatype should be equal to y. ";
   ctx->SetOutputDType("dx", 0, dtype);

@@ -13,27 +13,14 @@
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/core/framework/op_generated.h"
+#include "oneflow/user/ops/csr_op_util.h"
 
 namespace oneflow {
 
-namespace {
-
-constexpr const char* kRowPtr = "a_csr_row_ptr";
-constexpr const char* kColIdx = "a_csr_col_idx";
-
-}  // namespace
-
 /* static */ Maybe<void> GraphAttentionCsrHeadsOp::InferLogicalTensorDesc(
     user_op::InferContext* ctx) {
-  const Shape& rp = ctx->InputShape(kRowPtr, 0);
-  const Shape& ci = ctx->InputShape(kColIdx, 0);
-  CHECK_EQ_OR_RETURN(rp.NumAxes(), 1)
-      << Error::RuntimeError() << kRowPtr << " should be 1-D, got shape " << rp.ToString();
-  CHECK_GE_OR_RETURN(rp.At(0), 1)
-      << Error::RuntimeError() << kRowPtr << " should have a_num_rows + 1 elements. ";
-  CHECK_EQ_OR_RETURN(ci.NumAxes(), 1)
-      << Error::RuntimeError() << kColIdx << " should be 1-D, got shape " << ci.ToString();
-  const int64_t m = rp.At(0) - 1, nnz = ci.At(0);
+  int64_t m = 0, nnz = 0;
+  JUST(CheckCsrStructure(ctx, &m, &nnz));
   const Shape& q = ctx->InputShape("q", 0);
   const Shape& k = ctx->InputShape("k", 0);
   const Shape& v = ctx->InputShape("v", 0);
@@ -61,45 +48,23 @@ constexpr const char* kColIdx = "a_csr_col_idx";
   return InferLogicalTensorDesc(ctx);
 }
 /* static */ Maybe<void> GraphAttentionCsrHeadsOp::GetSbp(user_op::SbpContext* ctx) {
-  ctx->NewBuilder()
-      .Broadcast(user_op::OpArg(kRowPtr, 0))
-      .Broadcast(user_op::OpArg(kColIdx, 0))
-      .Broadcast(user_op::OpArg("q", 0))
-      .Broadcast(user_op::OpArg("k", 0))
-      .Broadcast(user_op::OpArg("v", 0))
-      .Broadcast(user_op::OpArg("out", 0))
-      .Broadcast(user_op::OpArg("attn", 0))
-      .Build();
-  return Maybe<void>::Ok();
+  return BroadcastAll(ctx, {"q", "k", "v", "out", "attn"});
 }
 /* static */ Maybe<void> GraphAttentionCsrHeadsOp::InferDataType(user_op::InferContext* ctx) {
-  const DataType index_dtype = ctx->InputDType(kRowPtr, 0);
-  CHECK_OR_RETURN(IsIndexDataType(index_dtype))
-      << Error::TypeError() << kRowPtr << " should be int32 or int64, got "
-      << DataType_Name(index_dtype);
-  CHECK_EQ_OR_RETURN(ctx->InputDType(kColIdx, 0), index_dtype)
-      << Error::TypeError() << kColIdx << " should have the dtype of " << kRowPtr << ". ";
+  JUST(CheckIndexDTypes(ctx));
   const DataType dtype = ctx->InputDType("k", 0);
   CHECK_EQ_OR_RETURN(ctx->InputDType("q", 0), dtype)
       << Error::TypeError() << "q datatype should be equal to k. ";
   CHECK_EQ_OR_RETURN(ctx->InputDType("v", 0), dtype)
       << Error::TypeError() << "v datatype should be equal to k. ";
-  CHECK_OR_RETURN(dtype == kFloat || dtype == kDouble || dtype == kFloat16 || dtype == kBFloat16)
-      << Error::TypeError()
-      << "graph_attention_csr_heads supports float, double, float16, bfloat16; got "
-      << DataType_Name(dtype);
+  JUST(CheckValueDType(dtype, "graph_attention_csr_heads"));
   ctx->SetOutputDType("out", 0, dtype);
   ctx->SetOutputDType("attn", 0, dtype);
   return Maybe<void>::Ok();
 }
 /* static */ Maybe<void> GraphAttentionCsrHeadsOp::ModifyInputArg(
     const user_op::GetInputArgModifier& GetInputArgModifierFn, const user_op::UserOpConfWrapper&) {
-  for (const char* name : {kRowPtr, kColIdx}) {
-    user_op::InputArgModifier* modifier = GetInputArgModifierFn(name, 0);
-    CHECK_NOTNULL_OR_RETURN(modifier);
-    modifier->set_requires_grad(false);
-  }
-  return Maybe<void>::Ok();
+  return IndexInputsNoGrad(GetInputArgModifierFn);
 }
 
 }  // namespace oneflow

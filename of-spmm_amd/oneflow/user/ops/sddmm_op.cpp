@@ -10,12 +10,14 @@
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/core/framework/op_generated.h"
+#include "oneflow/user/ops/csr_op_util.h"
 
 namespace oneflow {
 
 namespace {
 
-Maybe<void> CheckCsrStructure(user_op::InferContext* ctx, int64_t* nnz) {
+// With the sizes from the attributes (a_num_rows, a_num_cols), in this op's own wording.
+Maybe<void> CheckCsrOfAttrs(user_op::InferContext* ctx, int64_t* nnz) {
   const user_op::TensorDesc& row_ptr = ctx->InputTensorDesc("a_csr_row_ptr", 0);
   const user_op::TensorDesc& col_idx = ctx->InputTensorDesc("a_csr_col_idx", 0);
   const int64_t m = ctx->Attr<int64_t>("a_num_rows");
@@ -32,21 +34,11 @@ Maybe<void> CheckCsrStructure(user_op::InferContext* ctx, int64_t* nnz) {
   return Maybe<void>::Ok();
 }
 
-Maybe<void> CheckIndexTypes(user_op::InferContext* ctx) {
-  const DataType index_dtype = ctx->InputDType("a_csr_row_ptr", 0);
-  CHECK_OR_RETURN(IsIndexDataType(index_dtype))
-      << Error::TypeError() << "a_csr_row_ptr should be int32 or int64, got "
-      << DataType_Name(index_dtype);
-  CHECK_EQ_OR_RETURN(ctx->InputDType("a_csr_col_idx", 0), index_dtype)
-      << Error::TypeError() << "a_csr_col_idx should have the dtype of a_csr_row_ptr. ";
-  return Maybe<void>::Ok();
-}
-
 }  // namespace
 
 /* static */ Maybe<void> SddmmCsrOp::InferLogicalTensorDesc(user_op::InferContext* ctx) {
   int64_t nnz = 0;
-  JUST(CheckCsrStructure(ctx, &nnz));
+  JUST(CheckCsrOfAttrs(ctx, &nnz));
   const user_op::TensorDesc& a = ctx->InputTensorDesc("a", 0);
   const user_op::TensorDesc& b = ctx->InputTensorDesc("b", 0);
   CHECK_EQ_OR_RETURN(a.shape().NumAxes(), 2) << Error::RuntimeError() << "a should be 2-D. ";
@@ -75,20 +67,18 @@ Maybe<void> CheckIndexTypes(user_op::InferContext* ctx) {
   return Maybe<void>::Ok();
 }
 /* static */ Maybe<void> SddmmCsrOp::InferDataType(user_op::InferContext* ctx) {
-  JUST(CheckIndexTypes(ctx));
+  JUST(CheckIndexDTypes(ctx));
   const DataType dtype = ctx->InputDType("b", 0);
   CHECK_EQ_OR_RETURN(ctx->InputDType("a", 0), dtype)
       << Error::TypeError() << "a datatype should be equal to b. ";
-  CHECK_OR_RETURN(dtype == kFloat || dtype == kDouble || dtype == kFloat16 || dtype == kBFloat16)
-      << Error::TypeError() << "sddmm_csr supports float, double, float16, bfloat16; got "
-      << DataType_Name(dtype);
+  JUST(CheckValueDType(dtype, "sddmm_csr"));
   ctx->SetOutputDType("out", 0, dtype);
   return Maybe<void>::Ok();
 }
 
 /* static */ Maybe<void> CsrTransposeOp::InferLogicalTensorDesc(user_op::InferContext* ctx) {
   int64_t nnz = 0;
-  JUST(CheckCsrStructure(ctx, &nnz));
+  JUST(CheckCsrOfAttrs(ctx, &nnz));
   ctx->SetOutputShape("out_row_ptr", 0, Shape({ctx->Attr<int64_t>("a_num_cols") + 1}));
   ctx->SetOutputShape("out_col_idx", 0, Shape({nnz}));
   ctx->SetOutputShape("out_perm", 0, Shape({nnz}));
@@ -98,17 +88,10 @@ Maybe<void> CheckIndexTypes(user_op::InferContext* ctx) {
   return InferLogicalTensorDesc(ctx);
 }
 /* static */ Maybe<void> CsrTransposeOp::GetSbp(user_op::SbpContext* ctx) {
-  ctx->NewBuilder()
-      .Broadcast(user_op::OpArg("a_csr_row_ptr", 0))
-      .Broadcast(user_op::OpArg("a_csr_col_idx", 0))
-      .Broadcast(user_op::OpArg("out_row_ptr", 0))
-      .Broadcast(user_op::OpArg("out_col_idx", 0))
-      .Broadcast(user_op::OpArg("out_perm", 0))
-      .Build();
-  return Maybe<void>::Ok();
+  return BroadcastAll(ctx, {"out_row_ptr", "out_col_idx", "out_perm"});
 }
 /* static */ Maybe<void> CsrTransposeOp::InferDataType(user_op::InferContext* ctx) {
-  JUST(CheckIndexTypes(ctx));
+  JUST(CheckIndexDTypes(ctx));
   const DataType index_dtype = ctx->InputDType("a_csr_row_ptr", 0);
   ctx->SetOutputDType("out_row_ptr", 0, index_dtype);
   ctx->SetOutputDType("out_col_idx", 0, index_dtype);

@@ -15,72 +15,14 @@
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/core/framework/op_generated.h"
+#include "oneflow/user/ops/csr_op_util.h"
 
 namespace oneflow {
-
-namespace {
-
-constexpr const char* kRowPtr = "a_csr_row_ptr";
-constexpr const char* kColIdx = "a_csr_col_idx";
-
-Maybe<void> CheckStructure(user_op::InferContext* ctx, int64_t* m, int64_t* nnz) {
-  const Shape& rp = ctx->InputShape(kRowPtr, 0);
-  const Shape& ci = ctx->InputShape(kColIdx, 0);
-  CHECK_EQ_OR_RETURN(rp.NumAxes(), 1)
-      << Error::RuntimeError() << kRowPtr << " should be 1-D, got shape " << rp.ToString();
-  CHECK_GE_OR_RETURN(rp.At(0), 1)
-      << Error::RuntimeError() << kRowPtr << " should have a_num_rows + 1 elements. ";
-  CHECK_EQ_OR_RETURN(ci.NumAxes(), 1)
-      << Error::RuntimeError() << kColIdx << " should be 1-D, got shape " << ci.ToString();
-  *m = rp.At(0) - 1;
-  *nnz = ci.At(0);
-  return Maybe<void>::Ok();
-}
-
-Maybe<void> CheckDTypes(user_op::InferContext* ctx, const char* other, const char* op,
-                        DataType* dtype) {
-  const DataType index_dtype = ctx->InputDType(kRowPtr, 0);
-  CHECK_OR_RETURN(IsIndexDataType(index_dtype))
-      << Error::TypeError() << kRowPtr << " should be int32 or int64, got "
-      << DataType_Name(index_dtype);
-  CHECK_EQ_OR_RETURN(ctx->InputDType(kColIdx, 0), index_dtype)
-      << Error::TypeError() << kColIdx << " should have the dtype of " << kRowPtr << ". ";
-  *dtype = ctx->InputDType("b", 0);
-  CHECK_EQ_OR_RETURN(ctx->InputDType(other, 0), *dtype)
-      << Error::TypeError() << other << " datatype should be equal to b. ";
-  CHECK_OR_RETURN(*dtype == kFloat || *dtype == kDouble || *dtype == kFloat16 ||
-                  *dtype == kBFloat16)
-      << Error::TypeError() << op << " supports float, double, float16, bfloat16; got "
-      << DataType_Name(*dtype);
-  return Maybe<void>::Ok();
-}
-
-Maybe<void> IndexInputsNoGrad(const user_op::GetInputArgModifier& GetInputArgModifierFn) {
-  for (const char* name : {kRowPtr, kColIdx}) {
-    user_op::InputArgModifier* modifier = GetInputArgModifierFn(name, 0);
-    CHECK_NOTNULL_OR_RETURN(modifier);
-    modifier->set_requires_grad(false);
-  }
-  return Maybe<void>::Ok();
-}
-
-Maybe<void> BroadcastAll(user_op::SbpContext* ctx, const char* x, const char* y) {
-  ctx->NewBuilder()
-      .Broadcast(user_op::OpArg(kRowPtr, 0))
-      .Broadcast(user_op::OpArg(kColIdx, 0))
-      .Broadcast(user_op::OpArg(x, 0))
-      .Broadcast(user_op::OpArg(y, 0))
-      .Broadcast(user_op::OpArg("out", 0))
-      .Build();
-  return Maybe<void>::Ok();
-}
-
-}  // namespace
 
 // ---- spmm_csr_heads -------------------------------------------------------------------------------
 /* static */ Maybe<void> SpmmCsrHeadsOp::InferLogicalTensorDesc(user_op::InferContext* ctx) {
   int64_t m = 0, nnz = 0;
-  JUST(CheckStructure(ctx, &m, &nnz));
+  JUST(CheckCsrStructure(ctx, &m, &nnz));
   CHECK_EQ_OR_RETURN(m, ctx->Attr<int64_t>("a_num_rows"))
       << Error::RuntimeError() << kRowPtr << " should have a_num_rows + 1 elements. ";
   const int64_t k = ctx->Attr<int64_t>("a_num_cols");
@@ -106,11 +48,14 @@ Maybe<void> BroadcastAll(user_op::SbpContext* ctx, const char* x, const char* y)
   return InferLogicalTensorDesc(ctx);
 }
 /* static */ Maybe<void> SpmmCsrHeadsOp::GetSbp(user_op::SbpContext* ctx) {
-  return BroadcastAll(ctx, "a_csr_values", "b");
+  return BroadcastAll(ctx, {kValues, "b", "out"});
 }
 /* static */ Maybe<void> SpmmCsrHeadsOp::InferDataType(user_op::InferContext* ctx) {
-  DataType dtype;
-  JUST(CheckDTypes(ctx, "a_csr_values", "spmm_csr_heads", &dtype));
+  JUST(CheckIndexDTypes(ctx));
+  const DataType dtype = ctx->InputDType("b", 0);
+  CHECK_EQ_OR_RETURN(ctx->InputDType("a_csr_values", 0), dtype)
+      << Error::TypeError() << "a_csr_values datatype should be equal to b. ";
+  JUST(CheckValueDType(dtype, "spmm_csr_heads"));
   ctx->SetOutputDType("out", 0, dtype);
   return Maybe<void>::Ok();
 }
@@ -122,7 +67,7 @@ Maybe<void> BroadcastAll(user_op::SbpContext* ctx, const char* x, const char* y)
 // ---- sddmm_csr_heads ------------------------------------------------------------------------------
 /* static */ Maybe<void> SddmmCsrHeadsOp::InferLogicalTensorDesc(user_op::InferContext* ctx) {
   int64_t m = 0, nnz = 0;
-  JUST(CheckStructure(ctx, &m, &nnz));
+  JUST(CheckCsrStructure(ctx, &m, &nnz));
   const Shape& a = ctx->InputShape("a", 0);
   const Shape& b = ctx->InputShape("b", 0);
   CHECK_EQ_OR_RETURN(a.NumAxes(), 2) << Error::RuntimeError() << "a should be 2-D. ";
@@ -142,11 +87,14 @@ Maybe<void> BroadcastAll(user_op::SbpContext* ctx, const char* x, const char* y)
   return InferLogicalTensorDesc(ctx);
 }
 /* static */ Maybe<void> SddmmCsrHeadsOp::GetSbp(user_op::SbpContext* ctx) {
-  return BroadcastAll(ctx, "a", "b");
+  return BroadcastAll(ctx, {"a", "b", "out"});
 }
 /* static */ Maybe<void> SddmmCsrHeadsOp::InferDataType(user_op::InferContext* ctx) {
-  DataType dtype;
-  JUST(CheckDTypes(ctx, "a", "sddmm_csr_heads", &dtype));
+  JUST(CheckIndexDTypes(ctx));
+  const DataType dtype = ctx->InputDType("b", 0);
+  CHECK_EQ_OR_RETURN(ctx->InputDType("a", 0), dtype)
+      << Error::TypeError() << "a datatype should be equal to b. ";
+  JUST(CheckValueDType(dtype, "sddmm_csr_heads"));
   ctx->SetOutputDType("out", 0, dtype);
   return Maybe<void>::Ok();
 }

@@ -18,14 +18,11 @@
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/core/framework/op_generated.h"
+#include "oneflow/user/ops/csr_op_util.h"
 
 namespace oneflow {
 
 namespace {
-
-constexpr const char* kRowPtr = "a_csr_row_ptr";
-constexpr const char* kColIdx = "a_csr_col_idx";
-constexpr const char* kValues = "a_csr_values";
 
 Maybe<void> InferTensorDesc4SpmmCsr(user_op::InferContext* ctx) {
   const user_op::TensorDesc& row_ptr = ctx->InputTensorDesc(kRowPtr, 0);
@@ -58,18 +55,11 @@ Maybe<void> InferTensorDesc4SpmmCsr(user_op::InferContext* ctx) {
 }
 
 Maybe<void> InferDataType4SpmmCsr(user_op::InferContext* ctx) {
-  const DataType index_dtype = ctx->InputDType(kRowPtr, 0);
-  CHECK_OR_RETURN(IsIndexDataType(index_dtype))
-      << Error::TypeError() << "a_csr_row_ptr should be int32 or int64, got "
-      << DataType_Name(index_dtype);
-  CHECK_EQ_OR_RETURN(ctx->InputDType(kColIdx, 0), index_dtype)
-      << Error::TypeError() << "a_csr_col_idx should have the dtype of a_csr_row_ptr. ";
+  JUST(CheckIndexDTypes(ctx));
   const DataType dtype = ctx->InputDType("b", 0);
   CHECK_EQ_OR_RETURN(ctx->InputDType(kValues, 0), dtype)
       << Error::TypeError() << "a_csr_values datatype should be equal to b. ";
-  CHECK_OR_RETURN(dtype == kFloat || dtype == kDouble || dtype == kFloat16 || dtype == kBFloat16)
-      << Error::TypeError() << "spmm_csr supports float, double, float16, bfloat16; got "
-      << DataType_Name(dtype);
+  JUST(CheckValueDType(dtype, "spmm_csr"));
   ctx->SetOutputDType("out", 0, dtype);
   return Maybe<void>::Ok();
 }
@@ -149,13 +139,7 @@ Maybe<void> SpmmCsrInferPhysicalOut(user_op::InferContext* ctx) {
 
 /* static */ Maybe<void> SpmmCsrOp::ModifyInputArg(
     const user_op::GetInputArgModifier& GetInputArgModifierFn, const user_op::UserOpConfWrapper&) {
-  user_op::InputArgModifier* row_ptr_modifier = GetInputArgModifierFn(kRowPtr, 0);
-  CHECK_NOTNULL_OR_RETURN(row_ptr_modifier);
-  row_ptr_modifier->set_requires_grad(false);
-  user_op::InputArgModifier* col_idx_modifier = GetInputArgModifierFn(kColIdx, 0);
-  CHECK_NOTNULL_OR_RETURN(col_idx_modifier);
-  col_idx_modifier->set_requires_grad(false);
-  return Maybe<void>::Ok();
+  return IndexInputsNoGrad(GetInputArgModifierFn);
 }
 
 // ---- spmm_csr_gathered ----------------------------------------------------------------------

@@ -22,36 +22,14 @@
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/core/framework/op_generated.h"
+#include "oneflow/user/ops/csr_op_util.h"
 #include "ofx_spmm.h"
 
 namespace oneflow {
 
 namespace {
 
-constexpr const char* kRowPtr = "a_csr_row_ptr";
-constexpr const char* kColIdx = "a_csr_col_idx";
-constexpr const char* kValues = "a_csr_values";
-
 bool HasArg(int64_t reduce) { return reduce == OFX_REDUCE_MAX || reduce == OFX_REDUCE_MIN; }
-
-Maybe<void> CheckValueDType(DataType dtype, const char* op) {
-  CHECK_OR_RETURN(dtype == kFloat || dtype == kDouble || dtype == kFloat16 || dtype == kBFloat16)
-      << Error::TypeError() << op << " supports float, double, float16, bfloat16; got "
-      << DataType_Name(dtype);
-  return Maybe<void>::Ok();
-}
-
-Maybe<void> CheckIndexDTypes(user_op::InferContext* ctx, const char* first,
-                             const std::vector<const char*>& rest) {
-  const DataType index_dtype = ctx->InputDType(first, 0);
-  CHECK_OR_RETURN(IsIndexDataType(index_dtype))
-      << Error::TypeError() << first << " should be int32 or int64, got "
-      << DataType_Name(index_dtype);
-  for (const char* name : rest)
-    CHECK_EQ_OR_RETURN(ctx->InputDType(name, 0), index_dtype)
-        << Error::TypeError() << name << " should have the dtype of " << first << ". ";
-  return Maybe<void>::Ok();
-}
 
 Maybe<void> Check1D(user_op::InferContext* ctx, const char* name, int64_t elems, const char* what) {
   const Shape& s = ctx->InputShape(name, 0);
@@ -155,12 +133,7 @@ Maybe<void> CheckSizes(user_op::InferContext* ctx) {
 
 /* static */ Maybe<void> SpmmCsrReduceOp::ModifyInputArg(
     const user_op::GetInputArgModifier& GetInputArgModifierFn, const user_op::UserOpConfWrapper&) {
-  for (const char* name : {kRowPtr, kColIdx}) {
-    user_op::InputArgModifier* modifier = GetInputArgModifierFn(name, 0);
-    CHECK_NOTNULL_OR_RETURN(modifier);
-    modifier->set_requires_grad(false);
-  }
-  return Maybe<void>::Ok();
+  return IndexInputsNoGrad(GetInputArgModifierFn);
 }
 
 // ---- spmm_csr_reduce_grad_b -----------------------------------------------------------------------

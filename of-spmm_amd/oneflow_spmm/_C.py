@@ -87,6 +87,16 @@ def _placement(_parallel, _placement_nd):
     return (int(pnum),), (int(axis),), int(pid), int(logical_n)
 
 
+def _attrs_arg(static_csr: int):
+    """The `attrs` argument of an `_attrs` entry: None (the op's defaults), or a pointer to an
+    ofx_spmm_attrs that carries the call's static_csr."""
+    if not static_csr:
+        return None
+    attrs = _lib.SpmmAttrs()
+    attrs.static_csr = int(static_csr)
+    return ctypes.byref(attrs)
+
+
 def spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
              a_csr_values: torch.Tensor, a_num_rows: int, a_num_cols: int, b: torch.Tensor, *,
              out: torch.Tensor | None = None, _parallel=None, _placement_nd=None,
@@ -154,18 +164,10 @@ def spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     tmp = None
     if tmp_bytes.value:
         tmp = torch.empty(tmp_bytes.value, dtype=torch.uint8, device=bb.device)
-    if static_csr:
-        attrs = _lib.SpmmAttrs()
-        attrs.static_csr = int(static_csr)
-        check(LIB.ofx_functional_spmm_csr_global_attrs(
-            current_stream_handle(bb), *common, ctypes.byref(d_o),
-            tmp.data_ptr() if tmp is not None else None, tmp_bytes.value, *tail, None,
-            ctypes.byref(attrs)), "spmm_csr")
-    else:
-        check(LIB.ofx_functional_spmm_csr_global(current_stream_handle(bb), *common,
-                                                 ctypes.byref(d_o),
-                                                 tmp.data_ptr() if tmp is not None else None,
-                                                 tmp_bytes.value, *tail, None), "spmm_csr")
+    check(LIB.ofx_functional_spmm_csr_global_attrs(
+        current_stream_handle(bb), *common, ctypes.byref(d_o),
+        tmp.data_ptr() if tmp is not None else None, tmp_bytes.value, *tail, None,
+        _attrs_arg(static_csr)), "spmm_csr")
     if memo is None and len(_SIG_MEMO) < 4096:
         _SIG_MEMO[key] = (tuple(out.shape), out.dtype, tmp_bytes.value)
     return out
@@ -212,15 +214,10 @@ def fused_spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     tmp = None
     if size.value and bb.device.type != "cpu":
         tmp = torch.empty(size.value, dtype=torch.uint8, device=bb.device)
-    attrs = None
-    if static_csr:
-        attrs = _lib.SpmmAttrs()
-        attrs.static_csr = int(static_csr)
-        attrs = ctypes.byref(attrs)
     check(LIB.ofx_functional_fused_spmm_csr_attrs(current_stream_handle(bb), *args,
                                                   tmp.data_ptr() if tmp is not None else None,
                                                   size.value if tmp is not None else 0, None,
-                                                  attrs),
+                                                  _attrs_arg(static_csr)),
           "fused_spmm_csr")
     return out
 
@@ -254,14 +251,8 @@ def sddmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a: torch
         out = torch.empty(ci.numel(), dtype=b.dtype, device=b.device)
     if b.dim() == 2 and b.shape[1] == 0 and a.dim() == 2 and a.shape[1] == 0:
         return out
-    if static_csr:
-        attrs = _lib.SpmmAttrs()
-        attrs.static_csr = int(static_csr)
-        _run_grad_op(LIB.ofx_functional_sddmm_csr_attrs, b, [rp, ci, a, b], [out],
-                     [int(a_num_rows), int(a_num_cols)], (ctypes.byref(attrs),))
-    else:
-        _run_grad_op(LIB.ofx_functional_sddmm_csr, b, [rp, ci, a, b], [out],
-                     [int(a_num_rows), int(a_num_cols)])
+    _run_grad_op(LIB.ofx_functional_sddmm_csr_attrs, b, [rp, ci, a, b], [out],
+                 [int(a_num_rows), int(a_num_cols)], (_attrs_arg(static_csr),))
     return out
 
 
@@ -280,14 +271,8 @@ def spmm_csr_gathered(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
                           device=bb.device)
     if out.numel() == 0:
         return out
-    if static_csr:
-        attrs = _lib.SpmmAttrs()
-        attrs.static_csr = int(static_csr)
-        _run_grad_op(LIB.ofx_functional_spmm_csr_gathered_attrs, bb, [rp, ci, vals, perm, bb],
-                     [out], [int(a_num_rows), int(a_num_cols)], (ctypes.byref(attrs),))
-    else:
-        _run_grad_op(LIB.ofx_functional_spmm_csr_gathered, bb, [rp, ci, vals, perm, bb], [out],
-                     [int(a_num_rows), int(a_num_cols)])
+    _run_grad_op(LIB.ofx_functional_spmm_csr_gathered_attrs, bb, [rp, ci, vals, perm, bb], [out],
+                 [int(a_num_rows), int(a_num_cols)], (_attrs_arg(static_csr),))
     return out
 
 
@@ -382,25 +367,36 @@ def spmm_csr_reduce_grad_values(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torc
     return out
 
 
-def _edge_softmax_inputs(op, rp, ci, named):
-    """The shape and dtype checks the two edge-softmax ops share, ahead of the op layer's own (its
-    messages name the C-ABI); `named`: the per-nonzero value tensors."""
+def _check_inputs(op, rp, ci, named, rank, ref, per_nonzero):
+    """The shape and dtype checks the edge-softmax and multi-head ops share, ahead of the op
+    layer's own (its messages name the C-ABI).  `named`: [(name, tensor)], each of `rank`
+    dimensions; `ref`: the name of the one whose dtype the others must have; per_nonzero: each
+    has nnz elements (rank 1) or nnz rows of one number of heads (rank 2)."""
+    ref_t = dict(named)[ref]
     for name, t in named:
-        if t.dim() != 1:
-            raise RuntimeError(f"{op}: {name} should be 1-D, got shape {tuple(t.shape)}")
-        if t.numel() != ci.numel():
-            raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} elements (as "
-                               f"a_csr_col_idx), got {t.numel()}")
+        layout = " [nnz, heads]" if per_nonzero and rank == 2 else ""
+        if name == ref and not per_nonzero:
+            layout = " [K, heads * D]"
+        if t.dim() != rank:
+            raise RuntimeError(f"{op}: {name} should be {rank}-D{layout}, got shape "
+                               f"{tuple(t.shape)}")
+        if per_nonzero and t.shape[0] != ci.numel():
+            raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} "
+                               f"{'elements' if rank == 1 else 'rows'} (as a_csr_col_idx), got "
+                               f"{t.shape[0]}")
+        if per_nonzero and rank == 2 and t.shape[1] != ref_t.shape[1]:
+            raise RuntimeError(f"{op}: {name} should have the number of heads of {ref} "
+                               f"({t.shape[1]} vs {ref_t.shape[1]})")
     if rp.dtype != ci.dtype:
         raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
                         f"({ci.dtype} vs {rp.dtype})")
     dtype_code(rp.dtype)
-    first = named[0][1]
-    if first.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
-        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {first.dtype}")
-    for name, t in named[1:]:
-        if t.dtype != first.dtype:
-            raise TypeError(f"{op}: {name} datatype should be equal to {named[0][0]}")
+    if ref_t.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {ref_t.dtype}")
+    for name, t in named:
+        if t.dtype != ref_t.dtype:
+            detail = "" if per_nonzero else f" ({t.dtype} vs {ref_t.dtype})"
+            raise TypeError(f"{op}: {name} datatype should be equal to {ref}{detail}")
 
 
 def edge_softmax_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, e: torch.Tensor, *,
@@ -410,7 +406,7 @@ def edge_softmax_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, e
     launch on GPU tensors, the kCPU kernel on CPU tensors: the same bits."""
     rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
     e = _prep(e, "e")
-    _edge_softmax_inputs("edge_softmax_csr", rp, ci, [("e", e)])
+    _check_inputs("edge_softmax_csr", rp, ci, [("e", e)], 1, "e", True)
     if out is None:
         out = torch.empty_like(e)
     _run_grad_op(LIB.ofx_functional_edge_softmax_csr, e, [rp, ci, e], [out], [])
@@ -423,31 +419,10 @@ def edge_softmax_csr_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tens
     forward's stored y."""
     rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
     y, dy = _prep(y, "y"), _prep(dy, "dy")
-    _edge_softmax_inputs("edge_softmax_csr_grad", rp, ci, [("y", y), ("dy", dy)])
+    _check_inputs("edge_softmax_csr_grad", rp, ci, [("y", y), ("dy", dy)], 1, "y", True)
     dx = torch.empty_like(y)
     _run_grad_op(LIB.ofx_functional_edge_softmax_csr_grad, y, [rp, ci, y, dy], [dx], [])
     return dx
-
-
-def _heads_inputs(op, rp, ci, named):
-    """The index checks the multi-head ops share, ahead of the op layer's own, and the dtype
-    equality of their value tensors (`named`: [(name, tensor)], the [K, heads * D] operand the
-    others are compared with last: "b", or "k" for the fused attention)."""
-    if rp.dtype != ci.dtype:
-        raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
-                        f"({ci.dtype} vs {rp.dtype})")
-    dtype_code(rp.dtype)
-    ref, b = named[-1]
-    if b.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
-        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {b.dtype}")
-    for name, t in named[:-1]:
-        if t.dtype != b.dtype:
-            raise TypeError(f"{op}: {name} datatype should be equal to {ref} ({t.dtype} vs "
-                            f"{b.dtype})")
-        if t.dim() != 2:
-            raise RuntimeError(f"{op}: {name} should be 2-D, got shape {tuple(t.shape)}")
-    if b.dim() != 2:
-        raise RuntimeError(f"{op}: {ref} should be 2-D [K, heads * D], got shape {tuple(b.shape)}")
 
 
 def _check_out(op, out, shape, like, contiguous=False):
@@ -468,7 +443,7 @@ def spmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
     vals = _prep(a_csr_values, "a_csr_values")
     bb = _prep(b, "b", matrix=True)
-    _heads_inputs("spmm_csr_heads", rp, ci, [("a_csr_values", vals), ("b", bb)])
+    _check_inputs("spmm_csr_heads", rp, ci, [("a_csr_values", vals), ("b", bb)], 2, "b", False)
     if vals.shape[0] != ci.numel():
         raise RuntimeError(f"spmm_csr_heads: a_csr_values should have nnz = {ci.numel()} rows (as "
                            f"a_csr_col_idx), got {vals.shape[0]}")
@@ -496,7 +471,7 @@ def sddmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a:
     sddmm_csr on its slice."""
     rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
     a, bb = _prep(a, "a", matrix=True), _prep(b, "b", matrix=True)
-    _heads_inputs("sddmm_csr_heads", rp, ci, [("a", a), ("b", bb)])
+    _check_inputs("sddmm_csr_heads", rp, ci, [("a", a), ("b", bb)], 2, "b", False)
     heads = int(num_heads)
     if heads < 1 or bb.shape[1] % heads != 0:
         raise RuntimeError(f"sddmm_csr_heads: b's columns ({bb.shape[1]}) should be a multiple of "
@@ -531,7 +506,7 @@ def graph_attention_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.
     rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
     q = _prep(q, "q", matrix=True)
     kk, vv = _prep(k, "k", matrix=True), _prep(v, "v", matrix=True)
-    _heads_inputs(op, rp, ci, [("q", q), ("v", vv), ("k", kk)])
+    _check_inputs(op, rp, ci, [("q", q), ("v", vv), ("k", kk)], 2, "k", False)
     heads = int(num_heads)
     if heads < 1 or kk.shape[1] % heads != 0:
         raise RuntimeError(f"{op}: k's columns ({kk.shape[1]}) should be a multiple of "
@@ -560,31 +535,6 @@ def graph_attention_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.
     return out, attn_out
 
 
-def _edge_softmax_heads_inputs(op, rp, ci, named):
-    """The shape and dtype checks the two multi-head edge-softmax ops share, ahead of the op
-    layer's own; `named`: the [nnz, H] value tensors."""
-    first = named[0][1]
-    for name, t in named:
-        if t.dim() != 2:
-            raise RuntimeError(f"{op}: {name} should be 2-D [nnz, heads], got shape "
-                               f"{tuple(t.shape)}")
-        if t.shape[0] != ci.numel():
-            raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} rows (as "
-                               f"a_csr_col_idx), got {t.shape[0]}")
-        if t.shape[1] != first.shape[1]:
-            raise RuntimeError(f"{op}: {name} should have the number of heads of {named[0][0]} "
-                               f"({t.shape[1]} vs {first.shape[1]})")
-    if rp.dtype != ci.dtype:
-        raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
-                        f"({ci.dtype} vs {rp.dtype})")
-    dtype_code(rp.dtype)
-    if first.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
-        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {first.dtype}")
-    for name, t in named[1:]:
-        if t.dtype != first.dtype:
-            raise TypeError(f"{op}: {name} datatype should be equal to {named[0][0]}")
-
-
 def edge_softmax_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
                            e: torch.Tensor, *, out: torch.Tensor | None = None) -> torch.Tensor:
     """Op "edge_softmax_csr_heads": out[j, h] = softmax of the scores e[:, h] over the nonzeros of
@@ -593,7 +543,7 @@ def edge_softmax_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Ten
     include/ofx_spmm.h).  `out`: a contiguous [nnz, H] tensor, written directly."""
     rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
     e = _prep(e, "e")
-    _edge_softmax_heads_inputs("edge_softmax_csr_heads", rp, ci, [("e", e)])
+    _check_inputs("edge_softmax_csr_heads", rp, ci, [("e", e)], 2, "e", True)
     if out is None:
         out = torch.empty_like(e)
     else:
@@ -610,7 +560,7 @@ def edge_softmax_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torc
     y[:, h] * dy[:, h]) for y, dy [nnz, H], from the forward's stored y; one launch."""
     rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
     y, dy = _prep(y, "y"), _prep(dy, "dy")
-    _edge_softmax_heads_inputs("edge_softmax_csr_heads_grad", rp, ci, [("y", y), ("dy", dy)])
+    _check_inputs("edge_softmax_csr_heads_grad", rp, ci, [("y", y), ("dy", dy)], 2, "y", True)
     dx = torch.empty_like(y)
     if dx.numel() == 0:
         return dx
