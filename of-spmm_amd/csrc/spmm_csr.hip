@@ -1,7 +1,8 @@
 // spmm_csr.hip — the C-ABI of the CSR x dense SpMM forward (op "spmm_csr") and its small helper
 // kernels (CSR validation, row slices, synthetic dense inputs).  The forward kernels themselves
-// (plan / main / small form / reduce) are in spmm_csr_impl.h, compiled once per
-// (value, index) type pair in spmm_inst_*.hip and dispatched from here through launch_typed.
+// (plan / main / small form / reduce) are in spmm_csr_impl.h and their launch rules
+// in spmm_forward_rules.h, compiled once per (value, index) type pair in spmm_inst_*.hip and
+// dispatched from here through launch_typed.
 //
 // Reference semantics (OneFlow has no SpMM): the composition
 //   gather rows B[col[j]]      oneflow/user/kernels/gather_kernel_util.cpp:72-92
@@ -107,7 +108,9 @@ extern "C" int ofx_spmm_csr_workspace_size(int idx_dtype, int val_dtype, int64_t
     int rc = check_common(idx_dtype, val_dtype, m, k, n, nnz);
     if (rc) return rc;
     const Schedule s = launch_schedule(m, nnz, n, resolve_schedule(n, opts));
-    *bytes = use_small_form(m, nnz, n, s) ? 0 : ws_layout(m, nnz, n, acc_bytes_of(val_dtype), s).total;
+    *bytes = launch_form(m, nnz, n, s) == Form::Small
+                 ? 0
+                 : ws_layout(m, nnz, n, acc_bytes_of(val_dtype), s).total;
     return OFX_OK;
   });
 }
@@ -219,7 +222,7 @@ extern "C" int ofx_spmm_csr_plan(void* stream, int idx_dtype, int val_dtype, int
     if (nrows == 0 || n == 0) return OFX_OK;  // the launch writes nothing either
     const int64_t nnz_est = launch_nnz(m, nrows, nnz, opts);  // as the launch estimates it
     const Schedule s = launch_schedule(nrows, nnz_est, n, resolve_schedule(n, opts));
-    if (use_small_form(nrows, nnz_est, n, s)) return OFX_OK;  // the small form needs no plan
+    if (launch_form(nrows, nnz_est, n, s) == Form::Small) return OFX_OK;  // it needs no plan
     const plan::WsLayout w = plan::ws_layout(nrows, nnz, n, acc_bytes_of(val_dtype), s);
     if (w.total == 0) return OFX_OK;  // identity work list: nothing to plan
     OFX_REQUIRE(row_ptr != nullptr, OFX_EINVAL, "spmm_csr_plan: NULL row_ptr");

@@ -1,9 +1,9 @@
 #ifndef OFX_SPMM_CSR_IMPL_H_
 #define OFX_SPMM_CSR_IMPL_H_
-// spmm_csr_impl.h — the SpMM forward kernels for CDNA4 (gfx950) and their launch templates;
-// included by the per-type instantiation units (spmm_inst_*.hip) and the tuning table
-// (spmm_csr_tuned.hip) only, so the heavy template code compiles in parallel.
-//
+// spmm_csr_impl.h — the SpMM forward kernels for CDNA4 (gfx950): device code only.  The host side
+// (launchers, configuration families and the launch rules) is spmm_forward_rules.h, which includes
+// this header and is in turn included by the per-type instantiation units (spmm_inst_*.hip) and the
+// tuning table (spmm_csr_tuned.hip) only, so the heavy template code compiles in parallel.
 //
 // Reference semantics (OneFlow has no SpMM): the composition
 //   gather rows B[col[j]]      oneflow/user/kernels/gather_kernel_util.cpp:72-92
@@ -86,11 +86,7 @@ struct alignas(sizeof(T) * VEC) Pack {
 // HV (with HL): elements per lane of the wave items' HL-lane groups (1: one element per lane), so
 // that 16-bit rows of 33-64 columns take one pass of 32 lanes; with SH the last window is shifted
 // there as in the light rows.
-#ifndef OFX_AB_NO_LR
 constexpr bool kLR = true;  // the mid-size forms (prefetching, mid, narrow <= kPrefetchNnz): LR
-#else
-constexpr bool kLR = false;  // A/B builds only (probes/ab_build.sh): the spmm_reduce launch
-#endif
 template <int VEC_, int LPR_, int U_ = 8, int WPB_ = 4, bool NT_ = false, bool PF_ = false,
           bool BNT_ = false, bool WH_ = false, bool BI_ = false, bool BUF_ = true, int HL_ = 0,
           int HU_ = 16, bool SH_ = false, bool LR_ = false, int HV_ = 1, bool XL_ = false>
@@ -231,12 +227,8 @@ struct BRows {
   uint32_t ldb_bytes, cc_bytes, k32;
   template <typename I>
   __device__ __forceinline__ uint32_t clamp_row(I c) const {
-#ifdef OFX_AB_NO_ZERO_FILL  // A/B builds only (probes/ab_build.sh): no bound
-    return (uint32_t)c;
-#else
     if constexpr (sizeof(I) == 4) return __builtin_elementwise_min((uint32_t)c, k32);
     else return (uint64_t)c < (uint64_t)k ? (uint32_t)c : k32;
-#endif
   }
   __device__ __forceinline__ const T* row(int64_t c) const {
     return (uint64_t)c < (uint64_t)k ? base + c * ldb : zero;
@@ -312,13 +304,12 @@ __device__ __forceinline__ void accumulate(const I* __restrict__ col, const T* _
   using A = typename Num<T>::acc;
   using P = Pack<T, VEC>;
   if constexpr (LPR == 64) {
-#if !defined(OFX_AB_LPR64_SCALAR)
     // j0/j1 are wave-uniform.  Batches of 64 nonzeros: the (col, val) pairs are loaded coalesced,
     // one per lane, the next batch's during this one; each nonzero's pair reaches the wave as
     // scalars through v_readlane (no LDS), and U B rows are in flight per lane, issued branch-free
     // where B is one buffer (slots past the row end load row k: zeros from the range check, no
     // memory access).  The scalar-cache form this replaces (s_load of each col / val) paid two
-    // dependent round trips per U nonzeros (OFX_AB_LPR64_SCALAR keeps it for A/B builds).
+    // dependent round trips per U nonzeros.
     auto load_batch = [&](int64_t jb, I& c, A& v) {
       const int n_ = (int)((j1 - jb) < 64 ? (j1 - jb) : 64);
       c = 0;
@@ -360,30 +351,6 @@ __device__ __forceinline__ void accumulate(const I* __restrict__ col, const T* _
         }
       }
     }
-#else
-    // j0/j1 are wave-uniform: col/val come through the scalar cache.
-    for (int64_t j = j0; j < j1; j += kUnroll) {
-      const int cnt = (int)((j1 - j) < kUnroll ? (j1 - j) : kUnroll);
-      P bv[kUnroll];
-      A vv[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        if (u < cnt) {
-          const int64_t cu = (int64_t)ld_stream<K::NT>(col + j + u);
-          const int64_t jv = vperm ? (int64_t)ld_stream<K::NT>(vperm + j + u) : j + u;
-          vv[u] = Num<T>::load(ld_stream<K::NT>(val + jv));
-          if (active) bv[u] = br.template load<K::BNT, P>(cu);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        if (u < cnt && active) {
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) acc[e] = acc[e] + Num<T>::mul(vv[u], Num<T>::load(bv[u].v[e]));
-        }
-      }
-    }
-#endif
   } else {
     // A batch is R * LPR nonzeros: each lane loads R (col, val) pairs coalesced, the group
     // broadcasts them with ds_bpermute.  R > 1 only when more B-row loads are kept in flight
@@ -726,20 +693,14 @@ __device__ __forceinline__ void hub_tail(unsigned* __restrict__ arrive, int64_t 
   if (gl == 0) coh_store(arrive + slot0, 0u);
 }
 
-// Block-engine sizes (compile-time knobs for A/B builds: probes/ab_build.sh): bytes of products
-// per LDS buffer, nonzeros per batch, B-row loads per lane per batch.
-#ifndef OFX_BE_LDS
-#define OFX_BE_LDS 16384
-#endif
-#ifndef OFX_BE_NB_CAP
-#define OFX_BE_NB_CAP 128
-#endif
-#ifndef OFX_BE_UW_CAP
-#define OFX_BE_UW_CAP 8
-#endif
+// Block-engine sizes: bytes of products per LDS buffer, nonzeros per batch, B-row loads per lane
+// per batch.
+constexpr int kBeLds = 16384;
+constexpr int kBeNbCap = 128;
+constexpr int kBeUwCap = 8;
 
 // ---- small form: one launch, no plan, no workspace -------------------------------------------
-// Launches with few rows and little B-row traffic (use_small_form) run as ONE kernel.  Block b
+// Launches with few rows and little B-row traffic (Form::Small) run as ONE kernel.  Block b
 // owns rows [b*RPB, (b+1)*RPB), one lane-group per row.  A group takes its row when the row has at
 // most `light` nonzeros and is not split (accumulate, the group form).  The block's longer rows
 // are then taken one at a time by the whole block: each of its GB lane-groups loads the B rows of
@@ -757,10 +718,10 @@ struct SmallForm {
   static constexpr int RPB = GB;                          // rows per block
   static constexpr int D = 4;                             // batches of B-row loads in flight
   static constexpr int S = 8;                             // batches per (col, val) span
-  static constexpr int kLdsElems = OFX_BE_LDS / (int)sizeof(A);  // 16 KB of products per buffer
-  static constexpr int NB_RAW0 = kLdsElems / W < OFX_BE_NB_CAP ? kLdsElems / W : OFX_BE_NB_CAP;
+  static constexpr int kLdsElems = kBeLds / (int)sizeof(A);  // 16 KB of products per buffer
+  static constexpr int NB_RAW0 = kLdsElems / W < kBeNbCap ? kLdsElems / W : kBeNbCap;
   static constexpr int UW_RAW = NB_RAW0 / GB;
-  static constexpr int UW = UW_RAW > OFX_BE_UW_CAP ? OFX_BE_UW_CAP : (UW_RAW < 1 ? 1 : UW_RAW);  // loads per lane per batch
+  static constexpr int UW = UW_RAW > kBeUwCap ? kBeUwCap : (UW_RAW < 1 ? 1 : UW_RAW);  // loads per lane per batch
   static constexpr int NB = UW * GB;                      // nonzeros per batch
   static constexpr int SPAN = S * NB;                     // nonzeros per (col, val) span
   static constexpr int PT = (SPAN + kThreads - 1) / kThreads;  // span entries per thread
@@ -770,7 +731,7 @@ struct SmallForm {
   static constexpr int NBP = NB + 4;
   static constexpr int kBufElems = kColMajor ? W * NBP : NB * W;
   static_assert(S % D == 0 && S > D, "small form: span must hold whole rounds of the load ring");
-  static_assert(kBufElems * (int)sizeof(A) <= OFX_BE_LDS + 4 * W * (int)sizeof(A),
+  static_assert(kBufElems * (int)sizeof(A) <= kBeLds + 4 * W * (int)sizeof(A),
                 "small form: LDS batch too large");
 };
 
@@ -1081,11 +1042,6 @@ __global__ void __launch_bounds__(64 * K::WPB)
 
 // ---- main kernel: one work list = hub chunks, then rows in bin order ------------------------
 // Without a plan (`order` == nullptr) the list is simply the rows in index order.
-#ifdef OFX_AB_WPE  // A/B builds only (probes/ab_build.sh): waves per SIMD the registers must allow
-#define OFX_MAIN_WPE __attribute__((amdgpu_waves_per_eu(OFX_AB_WPE)))
-#else
-#define OFX_MAIN_WPE
-#endif
 // C[0, nrows) x [0, n) (row stride ldc) = the canonical quiet NaN, grid-stride over this launch.
 // The first consumer of an invalid plan runs it instead of its rows (spmm_plan.h plan_valid).
 template <typename T>
@@ -1099,7 +1055,7 @@ __device__ __attribute__((noinline)) void poison_output(T* __restrict__ C, int64
 }
 
 template <typename T, typename I, typename K>
-__global__ void __launch_bounds__(64 * K::WPB) OFX_MAIN_WPE
+__global__ void __launch_bounds__(64 * K::WPB)
     spmm_main_kernel(const I* __restrict__ rp, const I* __restrict__ col,
                      const T* __restrict__ val, const I* __restrict__ vperm,
                      const T* __restrict__ B, int64_t ldb, int64_t kb,
@@ -1257,11 +1213,6 @@ __global__ void __launch_bounds__(64 * K::WPB) OFX_MAIN_WPE
   // By index when hubs + heavy rows are at most 1/kIdxExcluded of the rows (power-law graphs:
   // 1.7-1.8%; Reddit-shaped: 53% hubs, where it cost 9%).
   constexpr int64_t kIdxExcluded = 16;
-#if defined(OFX_LIGHT_ORDER)
-  constexpr bool kIdx = false;  // A/B builds only (probes/ab_build.sh)
-#else
-  constexpr bool kIdx = true;
-#endif
   int64_t lr, c = -1;  // local row; chunk index or -1 for a whole row
   bool by_index = false;
   if (order == nullptr) {
@@ -1271,11 +1222,7 @@ __global__ void __launch_bounds__(64 * K::WPB) OFX_MAIN_WPE
     const int64_t nchunks = (int64_t)OFX_LD(counters + 0);
     const int64_t nhubs = (int64_t)OFX_LD(counters + 1);
     const int64_t nheavy = (int64_t)OFX_LD(counters + 3) - (int64_t)OFX_LD(counters + 2);  // bin 0
-#if defined(OFX_LIGHT_INDEX)
-    const bool idx = true;
-#else
-    const bool idx = kIdx && (nhubs + nheavy) * kIdxExcluded <= nrows;
-#endif
+    const bool idx = (nhubs + nheavy) * kIdxExcluded <= nrows;
     if (g < nchunks) {
       lr = OFX_LD(items + (2 * g + 0));
       c = OFX_LD(items + (2 * g + 1));
@@ -1386,594 +1333,7 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-template <typename T, int VEC>
-int launch_reduce_vec(hipStream_t s, int64_t max_hubs, int64_t n,
-                      const unsigned long long* counters, const int64_t* hubs,
-                      const typename Num<T>::acc* part, T* C, int64_t ldc, const T* bias, int act) {
-  const int64_t lanes = (n + VEC - 1) / VEC;
-  int l = 4;
-  while (l < 64 && l < lanes) l *= 2;
-  const int64_t per_block = kBlock / l;
-  int64_t grid = (max_hubs + per_block - 1) / per_block;
-  if (grid > kMaxReduceBlocks) grid = kMaxReduceBlocks;
-#define OFX_REDUCE(LL)                                                                        \
-  hipLaunchKernelGGL((spmm_reduce_kernel<T, VEC, LL>), dim3((unsigned)grid), dim3(kBlock), 0, s, \
-                     counters, hubs, part, C, ldc, n, bias, act)
-  switch (l) {
-    case 4: OFX_REDUCE(4); break;
-    case 8: OFX_REDUCE(8); break;
-    case 16: OFX_REDUCE(16); break;
-    case 32: OFX_REDUCE(32); break;
-    default: OFX_REDUCE(64); break;
-  }
-#undef OFX_REDUCE
-  OFX_HIP_CHECK(hipGetLastError());
-  return OFX_OK;
-}
-
-// 16-B partial loads when every partial row starts 16-B aligned (the workspace base is 256-B
-// aligned and rows are n accumulators apart), else one accumulator per lane.
-template <typename T>
-int launch_reduce(hipStream_t s, int64_t max_hubs, int64_t n, const unsigned long long* counters,
-                  const int64_t* hubs, const typename Num<T>::acc* part, T* C, int64_t ldc,
-                  const T* bias, int act) {
-  using A = typename Num<T>::acc;
-  constexpr int kVec = 16 / (int)sizeof(A);
-  if ((n * (int64_t)sizeof(A)) % 16 == 0)
-    return launch_reduce_vec<T, kVec>(s, max_hubs, n, counters, hubs, part, C, ldc, bias, act);
-  return launch_reduce_vec<T, 1>(s, max_hubs, n, counters, hubs, part, C, ldc, bias, act);
-}
-
-int pick_vec(int elem_bytes, const Launch& L, int forced_vec, int cap = 16) {
-  const int maxvec = std::min(16 / elem_bytes, cap);
-  for (int v = maxvec; v >= 1; v /= 2) {
-    if (forced_vec && v != forced_vec) continue;
-    const size_t vb = (size_t)v * elem_bytes;
-    if (L.n % v == 0 && L.ldb % v == 0 && L.ldc % v == 0 &&
-        ((uintptr_t)L.b % vb) == 0 && ((uintptr_t)L.c % vb) == 0)
-      return v;
-  }
-  return 0;
-}
-
-int pick_lpr(int64_t n, int vec) {
-  const int64_t lanes = (n + vec - 1) / vec;
-  int l = 4;
-  while (l < 64 && l < lanes) l *= 2;
-  return l;
-}
-
-// ofx_spmm_csr_describe: the configuration a launch takes (kind = "main" for the planned forms'
-// spmm_main_kernel, "small" for spmm_small_kernel), written instead of launching.  The form names
-// follow DESIGN.md §3: small, mid (block items), narrow (wave items of HL lanes), prefetch (PF
-// without block items), bandwidth (the rest).
-template <typename T, typename I, typename K>
-int describe_cfg(const Launch& L, const char* kind) {
-  const char* form = std::strcmp(kind, "small") == 0 ? "small"
-                     : K::BI                         ? "mid"
-                     : (K::WH && K::HL > 0)          ? "narrow"
-                     : K::PF                         ? "prefetch"
-                                                     : "bandwidth";
-  // the workspace this launch lays out (<= ofx_spmm_csr_workspace_size over the matrix's m)
-  const size_t ws = std::strcmp(kind, "small") == 0
-                        ? 0
-                        : ws_layout(L.nrows, L.nnz, L.n, sizeof(typename Num<T>::acc), L.sched).total;
-  std::snprintf(L.describe, L.describe_bytes,
-                "form=%s kernel=%s VEC=%d LPR=%d U=%d WPB=%d NT=%d PF=%d WH=%d BI=%d BUF=%d SH=%d "
-                "HL=%d HU=%d HV=%d XL=%d LR=%d elem=%d idx=%d ws=%zu",
-                form, kind, K::VEC, K::LPR, K::U, K::WPB, (int)K::NT, (int)K::PF, (int)K::WH,
-                (int)K::BI, (int)K::BUF, (int)K::SH, K::HL, K::HU, K::HV, (int)K::XL, (int)K::LR,
-                (int)sizeof(T),
-                (int)sizeof(I), ws);
-  return OFX_OK;
-}
-
-#ifdef OFX_DEBUG_BOUNDS
-// OFX_DEBUG_BOUNDS builds: the launch's allocations (dbg_bounds.h), published on its stream before
-// its kernels, and its configuration as the tag recorded with a violation:
-// VEC | LPR << 8 | U << 16 | flags << 24 (NT PF BNT WH BI BUF SH LR) | HL << 32 | HU << 40 |
-// kind << 48
-template <typename T, typename I, typename K>
-int debug_publish(const Launch& L, unsigned long long kind) {
-  dbg::HostBounds hb;
-  const int64_t si = (int64_t)sizeof(I), st = (int64_t)sizeof(T);
-  hb.add(L.rp, (uint64_t)((L.row_begin + L.nrows + 1) * si));
-  hb.add(L.col, (uint64_t)(L.nnz * si));
-  hb.add(L.val, (uint64_t)(L.nnz * st));
-  hb.add(L.vperm, (uint64_t)(L.nnz * si));
-  if (L.b_rows > 0) hb.add(L.b, (uint64_t)(((L.b_rows - 1) * L.ldb + L.n) * st));
-  hb.add(L.c, (uint64_t)(((L.nrows - 1) * L.ldc + L.n) * st));
-  hb.add(L.ws, L.ws_bytes);
-  hb.add(L.bias, (uint64_t)(L.n * st));
-  void* zero = nullptr;
-  OFX_HIP_CHECK(hipGetSymbolAddress(&zero, HIP_SYMBOL(g_zero_row)));
-  hb.add(zero, kZeroRowBytes);
-  const unsigned long long flags = (unsigned long long)K::NT | (unsigned long long)K::PF << 1 |
-                                   (unsigned long long)K::BNT << 2 | (unsigned long long)K::WH << 3 |
-                                   (unsigned long long)K::BI << 4 | (unsigned long long)K::BUF << 5 |
-                                   (unsigned long long)K::SH << 6 | (unsigned long long)K::LR << 7;
-  const unsigned long long tag = (unsigned long long)K::VEC | (unsigned long long)K::LPR << 8 |
-                                 (unsigned long long)K::U << 16 | flags << 24 |
-                                 (unsigned long long)K::HL << 32 | (unsigned long long)K::HU << 40 |
-                                 kind << 48;
-  OFX_REQUIRE(hb.publish(L.stream, tag) == 0, OFX_EDEVICE, "spmm_csr: debug bounds not published");
-  return OFX_OK;
-}
-#endif
-
-template <typename T, typename I, typename K>
-int launch_cfg(const Launch& L) {
-  if (L.describe != nullptr) return describe_cfg<T, I, K>(L, "main");
-  using A = typename Num<T>::acc;
-  constexpr int GPW = 64 / K::LPR;
-  constexpr int64_t GPB = (int64_t)K::WPB * GPW;  // lane-groups per block
-  const I* rp = static_cast<const I*>(L.rp);
-  const I* col = static_cast<const I*>(L.col);
-  const T* val = static_cast<const T*>(L.val);
-  const T* B = static_cast<const T*>(L.b);
-  T* C = static_cast<T*>(L.c);
-  const WsLayout w = ws_layout(L.nrows, L.nnz, L.n, sizeof(A), L.sched);
-  const bool plan = w.total > 0;
-#ifdef OFX_DEBUG_BOUNDS
-  if (const int rc = debug_publish<T, I, K>(L, 1)) return rc;
-#endif
-  WorkList wl{};
-  if (plan) {
-    OFX_REQUIRE(L.ws != nullptr && L.ws_bytes >= w.total, OFX_EWORKSPACE,
-                "spmm_csr: workspace of %zu bytes is smaller than the %zu bytes required",
-                L.ws_bytes, w.total);
-    if (L.sched.planned) {
-      plan::worklist_of(w, static_cast<char*>(L.ws), &wl);
-    } else {
-      const int rc = launch_plan<I>(L.stream, rp, L.row_begin, L.nrows, L.nnz_est, L.sched, w,
-                                    static_cast<char*>(L.ws), &wl);
-      if (rc) return rc;
-    }
-  }
-  unsigned long long* counters = wl.counters;
-  int64_t *hub = wl.hubs, *items = wl.items, *order = wl.order;
-  A* part = reinterpret_cast<A*>(wl.part);
-  // Work items: hub chunks, heavy rows, then every row by index (surplus groups exit at once).
-  // The WH / BI forms put one wave / block per hub chunk and heavy row first (upper bound: every
-  // chunk and every row longer than the heavy threshold), then the groups of the rows.
-  const int64_t heavy = L.sched.heavy == 0 ? auto_heavy(L.nrows, L.nnz_est) : L.sched.heavy;
-  const int64_t heavy_bound =
-      heavy == INT64_MAX ? 0 : std::min<int64_t>(L.nrows, L.nnz / (heavy + 1) + 1);
-  const int64_t bi_items = w.max_chunks + heavy_bound;
-  // wave items (one wave each) and block items (one block each) are bounded alike: hub chunks
-  // plus the rows above the heavy threshold.  The wave items loop (a wave strides over them), so
-  // their blocks are capped at kWaveItemBlocks; the light rows then need one group per row.
-  constexpr int64_t kWaveItemBlocks = 2048;
-  const bool wh = K::WH && K::LPR < 64 && plan;
-  const int64_t wave_blocks = wh ? std::min<int64_t>((bi_items + K::WPB - 1) / K::WPB, kWaveItemBlocks)
-                              : (K::BI && plan) ? bi_items
-                                                : 0;
-  const int64_t work = L.nrows + (plan && !wh && !K::BI ? bi_items : 0);
-  const int64_t grid = wave_blocks + (work + GPB - 1) / GPB;
-  // A launch holds fewer than 2^32 threads (papers-scale: 111M rows + items at 8 groups per block
-  // would not): the grid goes out in pieces of kLaunchBlocks, each told its first block.
-  constexpr int64_t kLaunchBlocks = ((int64_t)1 << 31) / (64 * K::WPB);
-  for (int64_t b0 = 0; b0 < grid; b0 += kLaunchBlocks) {
-    const int64_t nb = std::min(kLaunchBlocks, grid - b0);
-    hipLaunchKernelGGL((spmm_main_kernel<T, I, K>), dim3((unsigned)nb), dim3(64 * K::WPB), 0,
-                       L.stream, rp, col, val, static_cast<const I*>(L.vperm), B, L.ldb, L.b_rows,
-                       C, L.ldc, L.row_begin, L.nrows, L.n, plan ? L.sched.split : INT64_MAX,
-                       plan ? L.sched.chunk : INT64_MAX, heavy, counters, items, order, part,
-                       static_cast<const T*>(L.bias), L.act, wave_blocks, b0, wl.arrive,
-                       plan ? device_error_words() : nullptr);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
-  if (plan && w.max_hubs > 0 && !K::LR)  // LR: the main kernel added the hubs (hub_tail)
-    return launch_reduce<T>(L.stream, w.max_hubs, L.n, counters, hub, part, C, L.ldc,
-                            static_cast<const T*>(L.bias), L.act);
-  return OFX_OK;
-}
-
-
-template <typename T, typename I, typename K>
-int launch_small(const Launch& L) {
-  if (L.describe != nullptr) return describe_cfg<T, I, K>(L, "small");
-  using SF = SmallForm<T, I, K>;
-  // options.heavy_threshold > 0 overrides the light/whole-block cut (tuning; no numeric effect)
-  const int64_t light =
-      (L.sched.heavy > 0 && L.sched.heavy != INT64_MAX) ? L.sched.heavy : (int64_t)kSmallLight * K::U;
-  const int64_t grid = (L.nrows + SF::RPB - 1) / SF::RPB;
-#ifdef OFX_DEBUG_BOUNDS
-  if (const int rc = debug_publish<T, I, K>(L, 2)) return rc;
-#endif
-  OFX_REQUIRE(grid < (int64_t)UINT32_MAX, OFX_EINVAL, "spmm_csr: too many rows (%lld)",
-              (long long)L.nrows);
-  hipLaunchKernelGGL((spmm_small_kernel<T, I, K>), dim3((unsigned)grid), dim3(64 * K::WPB), 0,
-                     L.stream, static_cast<const I*>(L.rp), static_cast<const I*>(L.col),
-                     static_cast<const T*>(L.val), static_cast<const I*>(L.vperm),
-                     static_cast<const T*>(L.b), L.ldb, L.b_rows, static_cast<T*>(L.c), L.ldc,
-                     L.row_begin,
-                     L.nrows, L.n, L.sched.split, L.sched.chunk, light,
-                     static_cast<const T*>(L.bias), L.act);
-  OFX_HIP_CHECK(hipGetLastError());
-  return OFX_OK;
-}
-
-template <typename T, typename I, typename K>
-int launch_small_or_planned(const Launch& L) {
-  if (use_small_form(L.nrows, L.nnz_est, L.n, L.sched)) return launch_small<T, I, K>(L);
-  return launch_cfg<T, I, K>(L);
-}
-
-// B far larger than the Infinity Cache (> 1 GiB): the col/val/C streams are loaded and stored
-// non-temporally so they do not evict the hot (hub) B rows that still hit on-die.  Measured
-// (scripts/ab.py, bit-identical): papers-scale -1.8%, products -0.3%; with B at cache size
-// (1M power-law, 256 MB) the same hint costs +8%, hence the threshold.
-constexpr int64_t kNtBytes = int64_t(1) << 30;
-
-// Small problems (<= kSmallRows rows: too few lane-groups to be bandwidth-bound) run as long as
-// their longest non-split row, a chain of len / U dependent B-row load rounds; these launches keep
-// 32 (16 for 8-16 B lanes) loads in flight per lane instead of 8.  A Cora-shaped layer (max row
-// 253 nonzeros, N=16) took 25 us with U=8.  Same bits: U only changes how many loads are issued
-// ahead of the in-order adds.  Below kSmallFormElems products the launch is the small form.
-template <typename T, typename I, int VEC>
-int launch_vec_small(const Launch& L, int lpr) {
-  constexpr int U = VEC * sizeof(T) <= 4 ? 32 : 16;
-  switch (lpr) {
-    case 4: return launch_small_or_planned<T, I, Cfg<VEC, 4, U, 4, false, true, false, true>>(L);
-    case 8: return launch_small_or_planned<T, I, Cfg<VEC, 8, U, 4, false, true, false, true>>(L);
-    case 16: return launch_small_or_planned<T, I, Cfg<VEC, 16, U, 4, false, true, false, true>>(L);
-    case 32: return launch_small_or_planned<T, I, Cfg<VEC, 32, U, 4, false, true, false, true>>(L);
-    case 64: return launch_small_or_planned<T, I, Cfg<VEC, 64, U, 4, false, false, false, false>>(L);
-    default: return fail(OFX_EINVAL, "spmm_csr: unsupported lanes-per-row %d", lpr);
-  }
-}
-
-// The prefetching form (use_prefetch_form): U = 32 / 16 loads in flight per lane, the next batch's
-// (col, val) prefetched; WH: hub chunks and heavy rows take a whole wave (wave items).  Tuning
-// variants 30004 (WH) / 30005 force it at any size.
-template <typename T, typename I, int VEC, bool WH>
-int launch_vec_pf(const Launch& L, int lpr) {
-  constexpr int U = VEC * sizeof(T) <= 4 ? 32 : 16;
-  switch (lpr) {
-    case 4: return launch_cfg<T, I, Cfg<VEC, 4, U, 4, false, true, false, WH, false, true, 0, 16, false, kLR>>(L);
-    case 8: return launch_cfg<T, I, Cfg<VEC, 8, U, 4, false, true, false, WH, false, true, 0, 16, false, kLR>>(L);
-    case 16: return launch_cfg<T, I, Cfg<VEC, 16, U, 4, false, true, false, WH, false, true, 0, 16, false, kLR>>(L);
-    case 32: return launch_cfg<T, I, Cfg<VEC, 32, U, 4, false, true, false, WH, false, true, 0, 16, false, kLR>>(L);
-    case 64: return launch_cfg<T, I, Cfg<VEC, 64, U, 4, false, false, false, false, false, true, 0, 16, false, kLR>>(L);
-    default: return fail(OFX_EINVAL, "spmm_csr: unsupported lanes-per-row %d", lpr);
-  }
-}
-
-// Mid form (use_mid_form): block items first, then one lane-group per light row.  SR: the light
-// rows run the small-launch configuration (U = 32 / 16 loads in flight, next batch prefetched)
-// instead of the big-launch one (U = 8, 16 for one-element fp32 lanes).
-template <typename T, typename I, int VEC, bool SR>
-int launch_vec_mid(const Launch& L, int lpr) {
-  constexpr int U = SR ? (VEC * sizeof(T) <= 4 ? 32 : 16) : (VEC == 1 && sizeof(T) == 4 ? 16 : 8);
-  switch (lpr) {
-    case 4: return launch_cfg<T, I, Cfg<VEC, 4, U, 4, false, SR, false, false, true, true, 0, 16, false, kLR>>(L);
-    case 8: return launch_cfg<T, I, Cfg<VEC, 8, U, 4, false, SR, false, false, true, true, 0, 16, false, kLR>>(L);
-    case 16: return launch_cfg<T, I, Cfg<VEC, 16, U, 4, false, SR, false, false, true, true, 0, 16, false, kLR>>(L);
-    case 32: return launch_cfg<T, I, Cfg<VEC, 32, U, 4, false, SR, false, false, true, true, 0, 16, false, kLR>>(L);
-    case 64: return launch_cfg<T, I, Cfg<VEC, 64, U, 4, false, SR, false, false, true, true, 0, 16, false, kLR>>(L);
-    default: return fail(OFX_EINVAL, "spmm_csr: unsupported lanes-per-row %d", lpr);
-  }
-}
-
-// B's byte offsets fit the buffer descriptor's 32 bits (BRows): row k (the zero row) included.
-template <typename T>
-bool buffer_rows_ok(const Launch& L) {
-  return (unsigned __int128)(L.b_rows + 1) * (unsigned __int128)L.ldb * sizeof(T) <
-         ((unsigned __int128)1 << 32);
-}
-
-// B of 4 GiB or more (papers-scale): the bandwidth configurations with global loads (BUF = false).
-template <typename T, typename I, int VEC>
-int launch_vec_global(const Launch& L, int lpr, bool nt) {
-  switch (lpr) {
-    case 4: return launch_cfg<T, I, Cfg<VEC, 4, 8, 4, false, false, false, false, false, false>>(L);
-    case 8: return launch_cfg<T, I, Cfg<VEC, 8, 8, 4, false, false, false, false, false, false>>(L);
-    case 16:
-      if constexpr (VEC == 1 && sizeof(T) == 4)
-        return launch_cfg<T, I, Cfg<1, 16, 16, 4, false, false, false, false, false, false>>(L);
-      return launch_cfg<T, I, Cfg<VEC, 16, 8, 4, false, false, false, false, false, false>>(L);
-    case 32:
-      return nt ? launch_cfg<T, I, Cfg<VEC, 32, 8, 4, true, false, false, false, false, false>>(L)
-                : launch_cfg<T, I, Cfg<VEC, 32, 8, 4, false, false, false, false, false, false>>(L);
-    case 64:
-      return nt ? launch_cfg<T, I, Cfg<VEC, 64, 8, 4, true, false, false, false, false, false>>(L)
-                : launch_cfg<T, I, Cfg<VEC, 64, 8, 4, false, false, false, false, false, false>>(L);
-    default: return fail(OFX_EINVAL, "spmm_csr: unsupported lanes-per-row %d", lpr);
-  }
-}
-
-template <typename T, typename I, int VEC>
-int launch_vec(const Launch& L, int lpr, bool nt) {
-  const int v = L.sched.variant;
-  if (!buffer_rows_ok<T>(L)) {
-    OFX_REQUIRE(v == 0 || v == kForceBigVariant || v == kForceGlobalVariant || (v > 0 && v < 10000),
-                OFX_EINVAL,
-                "spmm_csr: variant %d needs B under 4 GiB (k=%lld, ldb=%lld)", v,
-                (long long)L.b_rows, (long long)L.ldb);
-    return launch_vec_global<T, I, VEC>(L, lpr, nt);
-  }
-  if (v == kForceSmallVariant || (v == 0 && use_small_form(L.nrows, L.nnz_est, L.n, L.sched)))
-    return launch_vec_small<T, I, VEC>(L, lpr);
-  if (v == kForceMidSmallVariant) return launch_vec_mid<T, I, VEC, true>(L, lpr);
-  if (v == kForceMidVariant) return launch_vec_mid<T, I, VEC, false>(L, lpr);
-  if (v == kForceWaveVariant) return launch_vec_pf<T, I, VEC, true>(L, lpr);
-  if (v == kForcePrefetchVariant) return launch_vec_pf<T, I, VEC, false>(L, lpr);
-  if (v == kForceGlobalVariant) return launch_vec_global<T, I, VEC>(L, lpr, nt);
-  // light rows of the mid form: the prefetching small-launch configuration above N = 16 (5-12%
-  // faster at N = 64 / 128 on 20k-170k-row power-law graphs), the big-launch one at N <= 16
-  // (profiles/r02n_probe_mid.json)
-  if (v == 0 && use_mid_form(L.nrows, L.nnz_est, L.n, L.sched)) {
-    return L.n > 16 ? launch_vec_mid<T, I, VEC, true>(L, lpr) : launch_vec_mid<T, I, VEC, false>(L, lpr);
-  }
-  // prefetching form: wave items at 16 < N <= 64 only (profiles/r03d_probe_forms.jsonl: at N = 16
-  // they cost more than they save, arxiv-shaped 206 against 96 us; at N = 32 / 64 they win or tie,
-  // 100 / 124 against 155 / 135 us; at N = 128 the form without them is 4-8% faster)
-  if (v == 0 && use_prefetch_form(L.nrows, L.nnz_est, L.n, L.sched))
-    return (L.n > 16 && L.n <= 64) ? launch_vec_pf<T, I, VEC, true>(L, lpr)
-                                   : launch_vec_pf<T, I, VEC, false>(L, lpr);
-  // the bandwidth configuration (forced variants keep it at every size)
-#ifdef OFX_AB_GLOBAL_LOADS  // A/B builds only (probes/ab_build.sh): global loads, not buffer loads
-  return launch_vec_global<T, I, VEC>(L, lpr, nt);
-#endif
-  switch (lpr) {
-    case 4: return launch_cfg<T, I, Cfg<VEC, 4>>(L);
-    case 8: return launch_cfg<T, I, Cfg<VEC, 8>>(L);
-    case 16:
-      // fp32 rows of <= 64 B (one element per lane): 16 loads in flight instead of 8, -1.2% on
-      // products-shaped N = 16 (tuning variant 10021, profiles/r02_ab_n16_bnt.log), same bits
-      if constexpr (VEC == 1 && sizeof(T) == 4) return launch_cfg<T, I, Cfg<1, 16, 16>>(L);
-      return launch_cfg<T, I, Cfg<VEC, 16>>(L);
-    case 32:
-      return nt ? launch_cfg<T, I, Cfg<VEC, 32, 8, 4, true>>(L) : launch_cfg<T, I, Cfg<VEC, 32>>(L);
-    case 64:
-      return nt ? launch_cfg<T, I, Cfg<VEC, 64, 8, 4, true>>(L) : launch_cfg<T, I, Cfg<VEC, 64>>(L);
-    default: return fail(OFX_EINVAL, "spmm_csr: unsupported lanes-per-row %d", lpr);
-  }
-}
-
-// fp32 rows whose width is not a multiple of 4 above N = 64 in the bandwidth configuration:
-// 16-B lanes with the last window shifted (Cfg::SH) instead of one element per lane, which needs
-// several 64-lane passes there: products N = 99 / 301 10.6 / 31.2 -> 8.5 / 25.2 ms.  At 17-63
-// columns one pass of single elements is as fast or faster (N = 41 / 47 / 63: 4.6 / 5.0 / 6.1 ms
-// against 4.8 / 5.2 / 6.2; such rows cost whole 128-B lines either way); profiles/r03ad_sweep.jsonl.
-// Round 5: 16-bit rows whose width is not a multiple of 8 above N = 64 the same way (8-element
-// windows at 2-B alignment, probes/unaligned_probe.hip) instead of one element per lane over 64
-// lanes: 1M power-law bf16 N = 99 / 127 / 255 1,490 / 1,556 / 3,031 -> 917 / 1,040 / 1,799 us
-// (tuning entries 10122 / 10123, gpurun_out/r05h_2_py.txt; N = 128 / 256: 853 / 1,489).
-// And 16-bit rows of 17-63 columns (but 32) in the bandwidth form, where the N / 16-element
-// lanes left them one element per lane over 32-64 lanes: 4-element windows over 8 lanes up to 31
-// columns, 8-element windows over 8 lanes above (entries 10175 / 10177, gpurun_out/r05t_1_py.txt,
-// 1M power-law bf16 N = 17 / 31 / 33 / 47 / 63: 521 / 551 / 823 / 841 / 862 -> 403 / 487 / 555 /
-// 609 / 674 us; N = 32 / 64 369 / 465 keep their layouts).  fp32 there stays one element per
-// lane: shifted windows moved it by -6..+3% on that graph and +4% on products (round 3).
-template <typename T, typename I>
-int launch_shift(const Launch& L, bool nt) {
-  constexpr int V = 16 / (int)sizeof(T);
-  if constexpr (sizeof(T) == 2) {
-    if (L.n < 32)
-      return launch_cfg<T, I, Cfg<4, 8, 8, 4, false, false, false, false, false, true, 0, 16, true>>(L);
-  }
-  const int lpr = pick_lpr(L.n, V);
-  switch (lpr) {
-    case 4: return launch_cfg<T, I, Cfg<V, 4, 8, 4, false, false, false, false, false, true, 0, 16, true>>(L);
-    case 8: return launch_cfg<T, I, Cfg<V, 8, 8, 4, false, false, false, false, false, true, 0, 16, true>>(L);
-    case 16: return launch_cfg<T, I, Cfg<V, 16, 8, 4, false, false, false, false, false, true, 0, 16, true>>(L);
-    case 32:
-      return nt ? launch_cfg<T, I, Cfg<V, 32, 8, 4, true, false, false, false, false, true, 0, 16, true>>(L)
-                : launch_cfg<T, I, Cfg<V, 32, 8, 4, false, false, false, false, false, true, 0, 16, true>>(L);
-    default:
-      return nt ? launch_cfg<T, I, Cfg<V, 64, 8, 4, true, false, false, false, false, true, 0, 16, true>>(L)
-                : launch_cfg<T, I, Cfg<V, 64, 8, 4, false, false, false, false, false, true, 0, 16, true>>(L);
-  }
-}
-
-// The prefetching form's (mid-size graphs) odd fp32 widths above 16: 16-B lanes with the shifted
-// last window, U = 16 loads in flight and the next (col, val) batch prefetched, instead of one
-// element per lane (N <= 64: up to 64 lanes, one row per wave).  Hubs added in the kernel (LR), as
-// in the rest of the prefetching form.
-// (Round 5: rows up to 128 / 256 columns take launch_mid_width_pf; this serves the wider ones,
-// and 16-bit rows in 8-element windows the same way.)
-template <typename T, typename I>
-int launch_shift_pf(const Launch& L) {
-  constexpr int V = 16 / (int)sizeof(T);
-  switch (pick_lpr(L.n, V)) {
-    case 4: return launch_cfg<T, I, Cfg<V, 4, 16, 4, false, true, false, false, false, true, 0, 16, true, kLR>>(L);
-    case 8: return launch_cfg<T, I, Cfg<V, 8, 16, 4, false, true, false, false, false, true, 0, 16, true, kLR>>(L);
-    case 16: return launch_cfg<T, I, Cfg<V, 16, 16, 4, false, true, false, false, false, true, 0, 16, true, kLR>>(L);
-    case 32: return launch_cfg<T, I, Cfg<V, 32, 16, 4, false, true, false, false, false, true, 0, 16, true, kLR>>(L);
-    default: return launch_cfg<T, I, Cfg<V, 64, 16, 4, false, false, false, false, false, true, 0, 16, true, kLR>>(L);
-  }
-}
-
-bool use_shift_pf_form(const Launch& L, int elem_bytes) {
-  const bool odd = (elem_bytes == 4 && L.n % 4 != 0) || (elem_bytes == 2 && L.n % 8 != 0);
-  return L.sched.variant == 0 && (elem_bytes == 4 || elem_bytes == 2) && L.n > 16 && odd &&
-         use_prefetch_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-         ((uintptr_t)L.b % elem_bytes) == 0 && ((uintptr_t)L.c % elem_bytes) == 0;
-}
-
-bool use_shift_form(const Launch& L, int elem_bytes) {
-  const bool odd = (elem_bytes == 4 && L.n > 64 && L.n % 4 != 0) ||
-                   (elem_bytes == 2 && L.n > 64 && L.n % 8 != 0) ||
-                   (elem_bytes == 2 && L.n > 16 && L.n < 64 && L.n != 32);
-  return L.sched.variant == 0 && (elem_bytes == 4 || elem_bytes == 2) && odd &&
-         !use_small_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-         !use_mid_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-         !use_prefetch_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-         ((uintptr_t)L.b % elem_bytes) == 0 && ((uintptr_t)L.c % elem_bytes) == 0;
-}
-
-// Rows of 64 B in fp32 (N = 16) above the mid form: four lanes of float4 per light row (16 rows
-// per wave, few registers, so many rows in flight: what bounds these launches) and the hub chunks
-// and heavy rows as wave items in 16-lane one-element groups (HL), so a 512-nonzero chunk is not
-// one 4-lane chain.  Up to kPrefetchNnz: U = 4 with 16 wave-item loads in flight per lane (arxiv-
-// shaped 71 -> 46 us, 2M nonzeros 65 -> 56 us); past it 2-lane float2 groups of U = 8 with 8 (5M
-// 111 -> 92 us, 1M power-law 406 -> 353 us, products 2,241 -> 2,184 us; a uniform-degree 20M graph
-// 396 -> 402 us).  profiles/r03n_graph.jsonl.  Same bits: only who adds changes.
-template <typename T, typename I>
-int launch_narrow(const Launch& L) {
-  // past kPrefetchNnz only (round 4's U = 8 in-kernel-reduce shape below it, entry 10082, gave
-  // way to launch_mid_width_pf's LDS-exchanged wave items in round 5)
-  return launch_cfg<T, I, Cfg<2, 8, 8, 4, false, true, false, true, false, true, 16, 8>>(L);
-}
-
-bool use_narrow_form(const Launch& L, int elem_bytes) {
-  // up to kPrefetchNnz the mid-width shape (its LDS-exchanged wave items) is faster since round 5
-  return L.sched.variant == 0 && elem_bytes == 4 && L.n == 16 && pick_vec(4, L, 0) == 4 &&
-         !use_small_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-         !use_mid_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-         !use_prefetch_form(L.nrows, L.nnz_est, L.n, L.sched);
-}
-
-// Narrow rows of mid-size launches (round 4, launch_narrow_pf, removed in round 5): 16-bit rows
-// of 8 or 16 columns and fp32 rows of 8 took four lanes per light row (8 B per lane) with 16-lane
-// one-element wave items (entries 10050-10063, profiles/r04k_variants.jsonl); the LDS-exchanged
-// wave items of launch_mid_width_pf below replaced it at every such width.
-
-// Rows of 17-64 columns of mid-size launches (round 5): the narrow form's
-// shape for every width -- shifted windows (Cfg::SH, any N; 2-B-aligned 8 / 16-B accesses are
-// exact and as fast on gfx950, probes/unaligned_probe.hip) over 8 lanes, hubs added in the
-// kernel -- with the wave items (hub chunks, heavy rows) in 32-lane groups, one column pass
-// (the reference gather's word choice, gather_kernel_util.cu:69-104, falls to 2-B words at odd
-// 16-bit widths; the shifted window keeps 8 / 16-B words at any width):
-// 1-element lanes up to 32 columns, 2-element lanes up to 64 (Cfg::HV).  The wave items' column
-// passes were what held these widths: the round-4 layouts ran 16-lane one-element wave items, two
-// to four passes per chunk.  Tuning entries 10100 / 10110 / 10117 / 10112 (profiles/
-// r05_width_sweep_midsize.jsonl), arxiv-shaped 169k x 1.17M: fp32 N = 17-32 77 -> 58 us, fp32
-// 33-64 97-103 -> 79-82, bf16 17 / 24 94 / 84 -> 68 / 66, bf16 33-63 125-160 -> 81-82 and N = 64
-// 94 -> 79; 60k x 1.5M fp32 N = 17 72 -> 55, bf16 N = 47 / 63 118 / -> 79.  Same bits: only who
-// adds changes.
-// The same shape either side (entries 10130-10142, gpurun_out/r05i_1_py.txt, arxiv-shaped):
-// rows of 1-15 columns (8 and 16 keep the narrow forms when aligned) in 4-lane groups, one
-// element per lane below 4 columns and shifted 4-element windows above, with 16-lane wave items
-// -- fp32 N = 1 / 4 / 12 / 15 75 / 86 / 73 / 83 -> 45 / 46 / 47 / 49 us, bf16 100 / 105 / 83 / 92
-// -> 47 / 48 / 50 / 50; rows of 65-128 columns in 8-element windows over 16 lanes with 4-element
-// wave lanes -- fp32 N = 65 / 99 / 128 143 / 148 / 147 -> 110 / 113 / 114, bf16 N = 65 / 99 / 128
-// 463 / 467 / 151 -> 111 / 112 / 109; and 16-bit rows of 129-256 columns, 8-element wave lanes
-// with 8 in flight -- bf16 N = 129 / 200 / 255 / 256 656 / 166 / 857 / 164 -> 155 / 150 / 158 /
-// 150.  fp32 rows above 128 columns keep their layouts (as fast: 173-210 us either way).
-// Up to 64 columns the wave items exchange their products through LDS (Cfg::XL,
-// accumulate_wave_xl): 8- / 16-lane groups of 2-4 elements, 32-64 nonzeros per round of B-row
-// loads without the cross-lane moves that made narrow groups lose (entries 10183-10198,
-// gpurun_out/r05aa_2_py.txt / r05z_2_py.txt, arxiv-shaped / 60k x 1.5M): fp32 N = 8 / 12 / 16
-// 43 / 44 / 44 -> 38 / 39 / 39 us, fp32 17-32 56 -> 48, fp32 47 / 64 78 -> 73 / 72 (76 -> 70),
-// bf16 17 / 24 57 -> 54 / 53, bf16 47 / 64 80 / 78 -> 71 / 65 (80 / 79 -> 77 / 74); and 16-bit
-// rows of 4-16 columns, aligned 8 / 16 included (round 4's narrow shape, launch_narrow_pf, is
-// gone; entries 10199-10202, gpurun_out/r05ae_1_py.txt): bf16 N = 4 / 8 / 12 / 16 44 / 46 / 47 /
-// 47 -> 37 / 40 / 42 / 42 us (60k x 1.5M 45 -> 43); fp32 rows of 65-128 columns too, two
-// 32-lane groups of 8 nonzeros (entry 10204, gpurun_out/r05ag_2_py.txt): N = 65 / 99 / 128 107 /
-// 111 / 112 -> 101 / 106 / 107 us (60k x 1.5M 101 / 106 / 107 -> 97 / 103 / 105); 16-bit rows
-// there gained nothing from it (-1..+3%) and keep the cross-lane groups.  Rows of 1-3 columns:
-// 16 four-lane groups of 8 nonzeros, 128 nonzeros per round of B-row loads (entry 10207,
-// gpurun_out/r05aj_2_py.txt): fp32 / bf16 N = 1-3 42-45 -> 29-31 us on both mid-size graphs.
-template <typename T, typename I>
-int launch_mid_width_pf(const Launch& L) {
-  if (L.n < 4)
-    return launch_cfg<T, I, Cfg<1, 4, 8, 4, false, true, false, true, false, true, 4, 8, false, kLR, 1, true>>(L);
-  if (L.n <= 16)
-    return launch_cfg<T, I, Cfg<4, 4, 8, 4, false, true, false, true, false, true, 8, 8, true, kLR, 2, true>>(L);
-  if (L.n <= 32)
-    return launch_cfg<T, I, Cfg<4, 8, 8, 4, false, true, false, true, false, true, 8, 8, true, kLR, 4, true>>(L);
-  if (L.n <= 64) {
-    if constexpr (sizeof(T) == 2)
-      return launch_cfg<T, I, Cfg<8, 8, 8, 4, false, true, false, true, false, true, 16, 8, true, kLR, 4, true>>(L);
-    else
-      return launch_cfg<T, I, Cfg<4, 16, 8, 4, false, true, false, true, false, true, 16, 8, true, kLR, 4, true>>(L);
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (L.n > 128)
-      return launch_cfg<T, I, Cfg<8, 32, 8, 4, false, true, false, true, false, true, 32, 8, true, kLR, 8>>(L);
-    return launch_cfg<T, I, Cfg<8, 16, 8, 4, false, true, false, true, false, true, 32, 16, true, kLR, 4>>(L);
-  } else {
-    return launch_cfg<T, I, Cfg<8, 16, 8, 4, false, true, false, true, false, true, 32, 8, true, kLR, 4, true>>(L);
-  }
-}
-
-bool use_mid_width_pf_form(const Launch& L, int elem_bytes) {
-  const int64_t top = elem_bytes == 2 ? 256 : 128;
-  return L.sched.variant == 0 && (elem_bytes == 2 || elem_bytes == 4) && L.n >= 1 && L.n <= top &&
-         use_prefetch_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-         ((uintptr_t)L.b % elem_bytes) == 0 && ((uintptr_t)L.c % elem_bytes) == 0;
-}
-
-
 }  // namespace
-
-template <typename T, typename I>
-int launch_typed(const Launch& L) {
-  const bool form = is_form_variant(L.sched.variant);  // auto configuration, forced form
-  if (L.sched.variant >= 10000 && !form) {
-    OFX_REQUIRE(buffer_rows_ok<T>(L), OFX_EINVAL,
-                "spmm_csr: tuning variant %d needs B under 4 GiB", L.sched.variant);
-    return launch_tuned<T, I>(L, L.sched.variant - 10000);
-  }
-  // the narrow form (fp32 N = 16 past kPrefetchNnz), then every width of a mid-size launch up
-  // to 128 (fp32) / 256 (16-bit) columns
-  if constexpr (sizeof(T) == 4) {
-    if (use_narrow_form(L, (int)sizeof(T)) && buffer_rows_ok<T>(L)) return launch_narrow<T, I>(L);
-  }
-  if constexpr (sizeof(T) == 2 || sizeof(T) == 4) {
-    if (use_mid_width_pf_form(L, (int)sizeof(T)) && buffer_rows_ok<T>(L))
-      return launch_mid_width_pf<T, I>(L);
-    if (use_shift_form(L, (int)sizeof(T)) && buffer_rows_ok<T>(L))
-      return launch_shift<T, I>(L, (L.b_rows * L.ldb * (int64_t)sizeof(T)) > kNtBytes);
-  }
-  if constexpr (sizeof(T) == 2 || sizeof(T) == 4) {
-#ifndef OFX_AB_NO_SHIFT_PF  // A/B builds only (probes/ab_build.sh)
-    if (use_shift_pf_form(L, (int)sizeof(T)) && buffer_rows_ok<T>(L)) return launch_shift_pf<T, I>(L);
-#endif
-  }
-  // variant = VEC * 100 + LPR forces a configuration (tuning / tests); 0 = auto.
-  const int forced_vec = (L.sched.variant > 0 && !form) ? L.sched.variant / 100 : 0;
-  const int forced_lpr = (L.sched.variant > 0 && !form) ? L.sched.variant % 100 : 0;
-  // fp32 rows of <= 64 B outside the narrow form (the small / mid forms, N < 16, forced forms):
-  // one element per lane over 16 lanes (+9% against 4 lanes of float4 in the round-2 bandwidth
-  // configuration, scripts/ab.py); wider rows keep the widest vector
-  // 16-bit rows of at most 128 B (N <= 64) in the bandwidth configuration: at least 16 lanes per
-  // row (VEC = N / 16: 2-8 B per lane) instead of the widest vector over 4-8 lanes; products bf16
-  // N = 8 / 16 / 32 / 64 -8 / -7 / -6 / -13%, Reddit-shaped N = 16 / 32 / 64 -27 / -19 / -6%
-  // (profiles/r03y_lanes_*.jsonl; fp32 keeps its layouts, DESIGN.md §3 tuning record)
-  // The prefetching form too (mid-size graphs): arxiv-shaped bf16 N = 16 took 214 us with 8-element
-  // lanes (two active lanes per 4-lane group) against 49 us for fp32 (profiles/r03ah_*.jsonl).
-  // The small and mid forms too (round 4, profiles/r04y_small16.jsonl, interleaved A/B): PubMed-
-  // shaped bf16 / f16 N = 8-32 33 -> 23 us, N = 64 36 -> 29; 20k rows x 400k N = 8-64 -4..-30%;
-  // Cora-shaped (host-bound) -1..-8%.
-  const bool narrow16 = !forced_vec && sizeof(T) == 2 && L.n <= 64 && L.sched.variant == 0;
-  int cap16 = 1;  // the largest power of two <= N / 16
-  while (cap16 * 32 <= L.n) cap16 *= 2;
-  const int vec = (!forced_vec && sizeof(T) == 4 && L.n <= 16) ? 1
-                  : narrow16 ? pick_vec((int)sizeof(T), L, 0, cap16)
-                             : pick_vec((int)sizeof(T), L, forced_vec);
-  OFX_REQUIRE(vec > 0, OFX_EINVAL,
-              "spmm_csr: variant %d not applicable (n=%lld ldb=%lld ldc=%lld or pointer alignment)",
-              L.sched.variant, (long long)L.n, (long long)L.ldb, (long long)L.ldc);
-  int lpr = forced_lpr ? forced_lpr : pick_lpr(L.n, vec);
-  // rows of fewer than 8 single-element lanes in the bandwidth configuration: 8-lane groups (idle
-  // lanes included), not 4-lane ones; fp32 N = 1 / 2 / 3 / 4 on products -11 / -9 / -8 / -9%, on
-  // the 1M power-law graph N = 1 / 4 -10 / -22%.  16 lanes won on products at N = 2-8 by 2-8% but
-  // lost on the power-law graph by 4-48% (profiles/r03af_sweep.jsonl)
-  if (!forced_lpr && vec == 1 && lpr < 8 && L.sched.variant == 0 &&
-      !use_small_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-      !use_mid_form(L.nrows, L.nnz_est, L.n, L.sched) &&
-      !use_prefetch_form(L.nrows, L.nnz_est, L.n, L.sched))
-    lpr = 8;
-  const bool nt = (L.b_rows * L.ldb * (int64_t)sizeof(T)) > kNtBytes;
-  switch (vec) {
-    case 1: return launch_vec<T, I, 1>(L, lpr, nt);
-    case 2: return launch_vec<T, I, 2>(L, lpr, nt);
-    case 4:
-      if constexpr (sizeof(T) <= 4) return launch_vec<T, I, 4>(L, lpr, nt);
-      break;
-    case 8:
-      if constexpr (sizeof(T) == 2) return launch_vec<T, I, 8>(L, lpr, nt);
-      break;
-  }
-  return fail(OFX_EINVAL, "spmm_csr: unsupported vector width %d", vec);
-}
-
 }  // namespace ofx
-
-#define OFX_SPMM_INSTANTIATE(T, I) template int ofx::launch_typed<T, I>(const ofx::Launch& L);
 
 #endif  // OFX_SPMM_CSR_IMPL_H_

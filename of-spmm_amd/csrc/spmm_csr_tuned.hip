@@ -1,14 +1,14 @@
 // spmm_csr_tuned.hip — the tuning table of the SpMM forward (variant = 10000 + id): forced
 // configurations for A/B runs (scripts/ab.py) and the tuning-table parity tests.
 //
-// No automatic rule launches through this table (the rules in spmm_csr_impl.h call launch_cfg
-// directly), so the release library is built without it: only
+// No automatic rule launches through this table (the rules in spmm_forward_rules.h call
+// launch_cfg directly), so the release library is built without it: only
 // `make -C of-spmm_amd tuning` compiles it (-DOFX_TUNING_TABLE, oneflow_spmm/libofx_spmm_tuning.so,
 // selected with OFX_SPMM_LIB), and ofx_version() then ends in "+tuning".  The tuning-table
 // tests skip on a library without it.
 #pragma clang fp contract(off)
 
-#include "spmm_csr_impl.h"
+#include "spmm_forward_rules.h"
 
 namespace ofx {
 

@@ -247,8 +247,8 @@ int prepare_plan(const char* fn, hipStream_t stream, const I* rp, int64_t m, int
                  const ofx_spmm_options* opts, void* ws, size_t ws_bytes, Planned* out) {
   const int64_t nnz_est = launch_nnz(m, nrows, nnz, opts);
   const Schedule sched = launch_schedule(nrows, nnz_est, n, resolve_schedule(n, opts));
-  const bool planned =
-      opts != nullptr && opts->planned != 0 && !use_small_form(nrows, nnz_est, n, sched);
+  const bool planned = opts != nullptr && opts->planned != 0 &&
+                       launch_form(nrows, nnz_est, n, sched) != Form::Small;
   // these entries' wording of the size error, ahead of the shared check
   const size_t need = plan::ws_layout(nrows, nnz, n, part_bytes_per_elem, sched).total;
   OFX_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need), OFX_EWORKSPACE,

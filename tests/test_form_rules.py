@@ -1,5 +1,5 @@
 """CPU: every form rule of the forward launch (of-spmm_amd/csrc/spmm_launch.h, launch_typed in
-spmm_csr_impl.h; DESIGN.md §3 "forms") on both sides of its threshold, through
+spmm_forward_rules.h; DESIGN.md §3 "forms") on both sides of its threshold, through
 ofx_spmm_csr_describe (the configuration a launch would take; nothing is launched, so no GPU is
 needed).  The GPU tests (test_gpu_forms.py) then run the same launches and compare the bits."""
 import os
