@@ -620,6 +620,77 @@ int ofx_graph_attention_csr_heads_cpu(int num_threads, int idx_dtype, int val_dt
                                       int64_t row_begin, int64_t row_end,
                                       const ofx_spmm_options* opts);
 
+/* ---- GAT attention weights (ops "gat_softmax_csr_heads" / "_grad") ---------------
+ * The attention weights of a GAT layer in one launch: additive scores, LeakyReLU and the per-row
+ * softmax.  s_row T[m, heads] and s_col T[k, heads] are the two halves of the score (a_l . W h_i
+ * and a_r . W h_j), attn, g, ds are T[nnz, heads] and d_row is T[m, heads], all row-major and
+ * contiguous.  `a` is the accumulation type of the edge softmax (f64 for f64, else f32) and
+ * slope_a is negative_slope converted to `a` once.  For nonzero j of row r with column
+ * c = col_idx[j], per head h:
+ *   1. z = load(s_row[r, h]) + load(s_col[c, h]): one add in `a`.  A column outside [0, k) reads
+ *      s_col = +0, like the zero row of the other gathers.
+ *   2. u = (z > 0) ? z : z * slope_a: one multiply in `a`; z = +-0 and NaN take the multiply branch.
+ *   3. e = u rounded to T as a step of its own (canonical NaN); the softmax runs on load(e).
+ *   4. attn[:, h] has exactly the bits of ofx_edge_softmax_csr_heads on that e.  Its whole contract
+ *      carries over: the max rule, one subtraction, exp_acc, 8-position leaves and the pairwise
+ *      tree along the row, one division, NaN / +inf / all -inf rows per head, heads never mix, an
+ *      empty row writes nothing.
+ * No score is stored: e exists in registers only.  slope_a must be finite and > 0, otherwise
+ * OFX_EINVAL: a slope of 0 would turn the -inf of a masked score into NaN (-inf * 0), and a
+ * negative one would turn it into +inf.
+ *
+ * Gradient, for the upstream g = d(attn), from the stored attn; z is formed again with the same add:
+ *   de_j = the gradient of ofx_edge_softmax_csr_heads_grad (q = y * g, the tree sum d_r,
+ *          y * (g - d_r)), rounded to T; it is not stored
+ *   ds_j = store(load(de_j) * (z_j > 0 ? 1 : slope_a)): one multiply in `a`, rounded to T
+ *   d_row[r, h] = store(the sum of load(ds_j) over r's nonzeros, in the softmax's leaf / tree
+ *          order); +0 for an empty row
+ * ds is the gradient per nonzero; d(s_row) is d_row.  d(s_col) is not an entry of its own: it is
+ * ofx_spmm_csr_heads on the transposed CSR (ofx_csr_transpose) with values ds[perm] and
+ * b = ones T[m, heads] (D = 1) under default options, whose order and hub rule are that op's.
+ *
+ * Row range [row_begin, row_end): s_row and d_row hold the rows from row_begin on; attn and ds are
+ * written at the global positions [row_ptr[row_begin]*heads, row_ptr[row_end]*heads).  Offsets are
+ * formed in 64 bits.  heads == 0, nnz == 0 or an empty range returns OFX_OK and writes nothing
+ * (not d_row either).  heads == 1 gives the bits of ofx_edge_softmax_csr on e.  opts: validated;
+ * no option has a numeric effect and `planned` is ignored.  Device versions: asynchronous on
+ * `stream`, no atomics, no allocation, no host synchronisation, capturable in a graph.  Workspace:
+ * 0 bytes (query it all the same); a NULL workspace with a non-zero size returns OFX_EWORKSPACE.
+ * OFX_EINVAL: a negative heads or size, a bad row range, a bad slope, int32 indices that cannot
+ * address the CSR, a NULL pointer, an output that overlaps an input or the other output;
+ * OFX_EUNSUPPORTED: a dtype.  Nothing is launched on an error.  HIP kernels and kCPU kernels give
+ * the same bits.                                                                                 */
+int ofx_gat_softmax_csr_heads_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                             int64_t heads, int64_t nnz,
+                                             const ofx_spmm_options* opts, size_t* bytes);
+int ofx_gat_softmax_csr_heads(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                              int64_t heads, int64_t nnz, const void* row_ptr, const void* col_idx,
+                              const void* s_row /* [m, heads] */,
+                              const void* s_col /* [k, heads] */, double negative_slope,
+                              void* attn /* [nnz, heads] */, int64_t row_begin, int64_t row_end,
+                              void* workspace, size_t workspace_bytes,
+                              const ofx_spmm_options* opts);
+/* kCPU version: host pointers, synchronous, the same bits, independent of num_threads.          */
+int ofx_gat_softmax_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                  int64_t k, int64_t heads, int64_t nnz, const void* row_ptr,
+                                  const void* col_idx, const void* s_row, const void* s_col,
+                                  double negative_slope, void* attn, int64_t row_begin,
+                                  int64_t row_end, const ofx_spmm_options* opts);
+/* ds[nnz, heads] and d_row[m, heads] from the forward's attn and the upstream g.                 */
+int ofx_gat_softmax_csr_heads_grad(void* stream, int idx_dtype, int val_dtype, int64_t m,
+                                   int64_t k, int64_t heads, int64_t nnz, const void* row_ptr,
+                                   const void* col_idx, const void* s_row, const void* s_col,
+                                   double negative_slope, const void* attn, const void* g, void* ds,
+                                   void* d_row, int64_t row_begin, int64_t row_end,
+                                   void* workspace, size_t workspace_bytes,
+                                   const ofx_spmm_options* opts);
+int ofx_gat_softmax_csr_heads_grad_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                       int64_t k, int64_t heads, int64_t nnz, const void* row_ptr,
+                                       const void* col_idx, const void* s_row, const void* s_col,
+                                       double negative_slope, const void* attn, const void* g,
+                                       void* ds, void* d_row, int64_t row_begin, int64_t row_end,
+                                       const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -1049,6 +1120,25 @@ int ofx_functional_edge_softmax_csr_heads_grad(void* stream, const ofx_tensor_de
                                                const ofx_tensor_desc* y, const ofx_tensor_desc* dy,
                                                ofx_tensor_desc* dx, void* tmp, size_t tmp_bytes,
                                                size_t* tmp_size_out);
+/* functional::GatSoftmaxCsrHeads / GatSoftmaxCsrHeadsGrad: ops "gat_softmax_csr_heads" (row_ptr
+ * [M+1], col_idx [nnz], s_row [M, H], s_col [K, H]; attr negative_slope -> out [nnz, H]) and
+ * "gat_softmax_csr_heads_grad" (+ y, dy [nnz, H] -> ds [nnz, H], d_row [M, H]) of
+ * oneflow/user/ops/gat_softmax_heads_op.cpp through the op-registry dispatch; the contract of
+ * ofx_gat_softmax_csr_heads(_grad).  tmp_size_out != NULL: only the tmp size is computed.        */
+int ofx_functional_gat_softmax_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                         const ofx_tensor_desc* col_idx,
+                                         const ofx_tensor_desc* s_row,
+                                         const ofx_tensor_desc* s_col, double negative_slope,
+                                         ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+                                         size_t* tmp_size_out);
+int ofx_functional_gat_softmax_csr_heads_grad(void* stream, const ofx_tensor_desc* row_ptr,
+                                              const ofx_tensor_desc* col_idx,
+                                              const ofx_tensor_desc* s_row,
+                                              const ofx_tensor_desc* s_col,
+                                              const ofx_tensor_desc* y, const ofx_tensor_desc* dy,
+                                              double negative_slope, ofx_tensor_desc* ds,
+                                              ofx_tensor_desc* d_row, void* tmp, size_t tmp_bytes,
+                                              size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

@@ -2,9 +2,13 @@
 // (edge_softmax.hip, edge_softmax_heads.hip) of ops "edge_softmax_csr", "edge_softmax_csr_heads"
 // and of their gradients share: the exponential, the constants of the sum's order, the argument
 // checks of their C-ABI entries and, for the HIP units, the device steps of a leaf, the lane-group
-// butterflies and the tile stack (contract in include/ofx_spmm.h).
+// butterflies and the tile stack (contract in include/ofx_spmm.h).  The
+// multi-head rows take a leaf source, so that gat_softmax_heads.hip runs the same
+// rows on scores it forms from a gather; gat_softmax_cpu.cpp shares the host's row step.
 #ifndef OFX_EDGE_SOFTMAX_H_
 #define OFX_EDGE_SOFTMAX_H_
+
+#include <vector>
 
 #include "ofx_internal.h"
 #include "spmm_common.h"
@@ -84,6 +88,47 @@ OFX_HD double exp_acc_of(double t) {
 template <typename A>
 OFX_HD A exp_acc(A t) {
   return exp_acc_of(t);
+}
+
+// ---- the row on the host (the kCPU kernels: edge_softmax_cpu.cpp, gat_softmax_cpu.cpp) -------------
+// The contract's sum of x[0 .. len): leaves of kLeaf positions from +0, zero-padded to a power of
+// two, pairwise level by level.  `leaf` is scratch.
+template <typename A>
+A tree_sum(const A* x, int64_t len, std::vector<A>& leaf) {
+#pragma clang fp contract(off)
+  const int64_t leaves = (len + kLeaf - 1) / kLeaf;
+  int64_t padded = 1;
+  while (padded < leaves) padded *= 2;
+  leaf.assign((size_t)padded, A(0));
+  for (int64_t i = 0; i < leaves; ++i) {
+    A s = A(0);
+    const int64_t end = (i + 1) * kLeaf < len ? (i + 1) * kLeaf : len;
+    for (int64_t p = i * kLeaf; p < end; ++p) s = s + x[p];
+    leaf[(size_t)i] = s;
+  }
+  for (int64_t w = 1; w < padded; w *= 2)
+    for (int64_t i = 0; i < padded; i += 2 * w) leaf[(size_t)i] = leaf[(size_t)i] + leaf[(size_t)(i + w)];
+  return leaf[0];
+}
+
+// One head's row: x[0 .. len) holds the loaded scores and is overwritten with their exponentials;
+// y[p * stride] = the softmax rounded to T.  len > 0.
+template <typename T>
+void softmax_row(typename Num<T>::acc* x, int64_t len, std::vector<typename Num<T>::acc>& leaf,
+                 T* y, int64_t stride) {
+#pragma clang fp contract(off)
+  using A = typename Num<T>::acc;
+  A best = x[0];
+  for (int64_t p = 1; p < len; ++p) best = better(x[p], best, true) ? x[p] : best;
+  for (int64_t p = 0; p < len; ++p) {
+    const A t = x[p] - best;
+    x[p] = exp_acc<A>(t);
+  }
+  const A s = tree_sum(x, len, leaf);
+  for (int64_t p = 0; p < len; ++p) {
+    const A q = x[p] / s;
+    y[p * stride] = Num<T>::store(canonical_nan(q));
+  }
 }
 
 // ---- argument checks shared by the device and host entries ----------------------------------
@@ -324,20 +369,48 @@ __device__ __forceinline__ void store_leaf_heads(T* p, int64_t H, int64_t pos,
   }
 }
 
+// Where a row's leaves come from.  A leaf source has load(pos, len, fill, x): x[v][i] = the value
+// of position pos + i and head v for the positions inside [0, len), `fill` for the others (len > 0).
+// The memory source reads a T[., H] array: p points at the row's first position and the lane's
+// first head.  gat_softmax_heads.hip has one that forms its scores from a gather instead.
+template <typename T, int V>
+struct MemoryLeaves {
+  const T* p;
+  int64_t H;
+  __device__ __forceinline__ void load(int64_t pos, int64_t len, typename Num<T>::acc fill,
+                                       typename Num<T>::acc (&x)[V][kLeaf]) const {
+    load_leaf_heads<T, V>(p, H, pos, len, fill, x);
+  }
+};
+
+// The same for a group that may have no row (len == 0: nothing is loaded).
+template <typename T, int V, typename Src>
+__device__ __forceinline__ void load_leaf_or_fill(const Src& src, int64_t pos, int64_t len,
+                                                  typename Num<T>::acc fill,
+                                                  typename Num<T>::acc (&x)[V][kLeaf]) {
+  if (len > 0) {
+    src.load(pos, len, fill, x);
+  } else {
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+#pragma unroll
+      for (int i = 0; i < kLeaf; ++i) x[v][i] = fill;
+  }
+}
+
 // A row of at most 8 LG positions over a group of LG lanes, lane gl holding leaf gl of V heads.
-// off: the element offset of the row's first position and the lane's first head.  len == 0:
-// nothing is loaded or stored (a group with no item, or whose row the wave takes over).
-// Forward: a = e, out = y.  Backward: a = y, g = the upstream gradient, out = de.
-template <typename T, int V, int LG, bool BWD>
-__device__ __forceinline__ void row_in_registers(const T* a, const T* g,
-                                                 T* out, int64_t H, int64_t off,
-                                                 int64_t len, int gl) {
+// off: the element offset in g and out of the row's first position and the lane's first head.
+// len == 0: nothing is loaded or stored (a group with no item, or whose row the wave takes over).
+// Forward: src = e, out = y.  Backward: src = y, g = the upstream gradient, out = de.
+template <typename T, int V, int LG, bool BWD, typename Src>
+__device__ __forceinline__ void row_in_registers_of(const Src& src, const T* g, T* out, int64_t H,
+                                                    int64_t off, int64_t len, int gl) {
   using A = typename Num<T>::acc;
   const int64_t pos = (int64_t)gl * kLeaf;
   A x[V][kLeaf];
   T res[V][kLeaf];
   if constexpr (!BWD) {
-    load_leaf_heads_or_fill<T, V>(a + off, H, pos, len, -__builtin_huge_val(), x);
+    load_leaf_or_fill<T, V>(src, pos, len, -__builtin_huge_val(), x);
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const A m = group_max<A, LG>(leaf_max<A>(x[v], x[v][0]));
@@ -346,7 +419,7 @@ __device__ __forceinline__ void row_in_registers(const T* a, const T* g,
     }
   } else {
     A gg[V][kLeaf];
-    load_leaf_heads_or_fill<T, V>(a + off, H, pos, len, A(0), x);
+    load_leaf_or_fill<T, V>(src, pos, len, A(0), x);
     load_leaf_heads_or_fill<T, V>(g + off, H, pos, len, A(0), gg);
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -357,15 +430,22 @@ __device__ __forceinline__ void row_in_registers(const T* a, const T* g,
   store_leaf_heads<T, V>(out + off, H, pos, len, res);
 }
 
+// The row from memory: off is the offset in a as well.
+template <typename T, int V, int LG, bool BWD>
+__device__ __forceinline__ void row_in_registers(const T* a, const T* g,
+                                                 T* out, int64_t H, int64_t off,
+                                                 int64_t len, int gl) {
+  row_in_registers_of<T, V, LG, BWD>(MemoryLeaves<T, V>{a + off, H}, g, out, H, off, len, gl);
+}
+
 // A row of more than kTile positions, by the whole wave, for V heads; SW tiles in flight (the
-// number has no numeric effect: tiles are pushed in tile order).
-template <typename T, int V, bool BWD>
-__device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
-                                             T* out, int64_t H, int64_t off,
-                                             int64_t len, int lane) {
+// number has no numeric effect: tiles are pushed in tile order).  Every pass loads its leaves from
+// the source again.
+template <typename T, int V, bool BWD, typename Src>
+__device__ __forceinline__ void row_in_tiles_of(const Src& pa, const T* g, T* out, int64_t H,
+                                                int64_t off, int64_t len, int lane) {
   using A = typename Num<T>::acc;
   constexpr int SW = V == 1 ? 2 : 1;
-  const T* pa = a + off;
   const T* pg = BWD ? g + off : nullptr;
   T* po = out + off;
   const int64_t tiles = (len + kTile - 1) / kTile;
@@ -379,7 +459,7 @@ __device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
       A x[SW][V][kLeaf];
 #pragma unroll
       for (int u = 0; u < SW; ++u)
-        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+        pa.load((t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
 #pragma unroll
       for (int u = 0; u < SW; ++u)
 #pragma unroll
@@ -396,7 +476,7 @@ __device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
     if constexpr (!BWD) {
 #pragma unroll
       for (int u = 0; u < SW; ++u)
-        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+        pa.load((t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
 #pragma unroll
       for (int u = 0; u < SW; ++u)
 #pragma unroll
@@ -406,7 +486,7 @@ __device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
       A gg[SW][V][kLeaf];
 #pragma unroll
       for (int u = 0; u < SW; ++u) {
-        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, A(0), x[u]);
+        pa.load((t0 + u) * kTile + lpos, len, A(0), x[u]);
         load_leaf_heads<T, V>(pg, H, (t0 + u) * kTile + lpos, len, A(0), gg[u]);
       }
 #pragma unroll
@@ -434,7 +514,7 @@ __device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
     if constexpr (!BWD) {
 #pragma unroll
       for (int u = 0; u < SW; ++u)
-        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
+        pa.load((t0 + u) * kTile + lpos, len, -__builtin_huge_val(), x[u]);
 #pragma unroll
       for (int u = 0; u < SW; ++u)
 #pragma unroll
@@ -446,7 +526,7 @@ __device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
       A gg[SW][V][kLeaf];
 #pragma unroll
       for (int u = 0; u < SW; ++u) {
-        load_leaf_heads<T, V>(pa, H, (t0 + u) * kTile + lpos, len, A(0), x[u]);
+        pa.load((t0 + u) * kTile + lpos, len, A(0), x[u]);
         load_leaf_heads<T, V>(pg, H, (t0 + u) * kTile + lpos, len, A(0), gg[u]);
       }
 #pragma unroll
@@ -458,6 +538,22 @@ __device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
     for (int u = 0; u < SW; ++u)
       store_leaf_heads<T, V>(po, H, (t0 + u) * kTile + lpos, len, res[u]);
   }
+}
+
+template <typename T, int V, bool BWD>
+__device__ __forceinline__ void row_in_tiles(const T* a, const T* g,
+                                             T* out, int64_t H, int64_t off,
+                                             int64_t len, int lane) {
+  row_in_tiles_of<T, V, BWD>(MemoryLeaves<T, V>{a + off, H}, g, out, H, off, len, lane);
+}
+
+template <typename T, int V, bool BWD, typename Src>
+__device__ __forceinline__ void row_by_wave_of(const Src& src, const T* g, T* out, int64_t H,
+                                               int64_t off, int64_t len, int lane) {
+  if (len <= kTile)
+    row_in_registers_of<T, V, 64, BWD>(src, g, out, H, off, len, lane);
+  else
+    row_in_tiles_of<T, V, BWD>(src, g, out, H, off, len, lane);
 }
 
 template <typename T, int V, bool BWD>

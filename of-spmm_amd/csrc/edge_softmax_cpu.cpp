@@ -21,25 +21,8 @@ namespace {
 
 using namespace esm;
 
-// The contract's sum of x[0 .. len): leaves of kLeaf positions from +0, zero-padded to a power of
-// two, pairwise level by level.  `leaf` is scratch.
-template <typename A>
-A tree_sum(const A* x, int64_t len, std::vector<A>& leaf) {
-#pragma clang fp contract(off)
-  const int64_t leaves = (len + kLeaf - 1) / kLeaf;
-  int64_t padded = 1;
-  while (padded < leaves) padded *= 2;
-  leaf.assign((size_t)padded, A(0));
-  for (int64_t i = 0; i < leaves; ++i) {
-    A s = A(0);
-    const int64_t end = (i + 1) * kLeaf < len ? (i + 1) * kLeaf : len;
-    for (int64_t p = i * kLeaf; p < end; ++p) s = s + x[p];
-    leaf[(size_t)i] = s;
-  }
-  for (int64_t w = 1; w < padded; w *= 2)
-    for (int64_t i = 0; i < padded; i += 2 * w) leaf[(size_t)i] = leaf[(size_t)i] + leaf[(size_t)(i + w)];
-  return leaf[0];
-}
+// The sum's order (tree_sum) and one head's row (softmax_row) are edge_softmax.h's, shared with
+// gat_softmax_cpu.cpp.
 
 template <typename T, typename I>
 void cpu_forward(int nthreads, const I* rp, const T* e, T* y, int64_t heads, int64_t row_begin,
@@ -56,21 +39,8 @@ void cpu_forward(int nthreads, const I* rp, const T* e, T* y, int64_t heads, int
       x.resize((size_t)len);
       for (int64_t h = 0; h < heads; ++h) {
         const T* eh = e + j0 * heads + h;
-        T* yh = y + j0 * heads + h;
-        A best = Num<T>::load(eh[0]);
-        for (int64_t p = 1; p < len; ++p) {
-          const A c = Num<T>::load(eh[p * heads]);
-          best = better(c, best, true) ? c : best;
-        }
-        for (int64_t p = 0; p < len; ++p) {
-          const A t = Num<T>::load(eh[p * heads]) - best;
-          x[(size_t)p] = exp_acc<A>(t);
-        }
-        const A s = tree_sum(x.data(), len, leaf);
-        for (int64_t p = 0; p < len; ++p) {
-          const A q = x[(size_t)p] / s;
-          yh[p * heads] = Num<T>::store(canonical_nan(q));
-        }
+        for (int64_t p = 0; p < len; ++p) x[(size_t)p] = Num<T>::load(eh[p * heads]);
+        softmax_row<T>(x.data(), len, leaf, y + j0 * heads + h, heads);
       }
     }
   }

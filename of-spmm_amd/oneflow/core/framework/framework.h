@@ -16,6 +16,7 @@
 #define OFX_ONEFLOW_SHIM_FRAMEWORK_H_
 
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <memory>
@@ -410,6 +411,30 @@ class Tensor {
 
 using AttrMap = std::map<std::string, int64_t>;
 
+// An AttrMap value as attr type T and back.  The map holds int64 only: an integer or bool attr is
+// its value, a floating-point attr (e.g. negative_slope) travels as the bits of a double.
+template <typename T>
+inline int64_t AttrBits(T v) {
+  if constexpr (std::is_floating_point<T>::value) {
+    const double d = static_cast<double>(v);
+    int64_t bits;
+    std::memcpy(&bits, &d, sizeof(bits));
+    return bits;
+  } else {
+    return static_cast<int64_t>(v);
+  }
+}
+template <typename T>
+inline T AttrFromBits(int64_t bits) {
+  if constexpr (std::is_floating_point<T>::value) {
+    double d;
+    std::memcpy(&d, &bits, sizeof(d));
+    return static_cast<T>(d);
+  } else {
+    return static_cast<T>(bits);
+  }
+}
+
 class InferContext {
  public:
   InferContext(std::map<std::pair<std::string, int32_t>, TensorDesc> in, AttrMap attrs)
@@ -424,7 +449,7 @@ class InferContext {
   void SetOutputDType(const std::string& n, int32_t i, DataType dt) { out_[{n, i}].set_data_type(dt); }
   template <typename T>
   T Attr(const std::string& n) const {
-    return static_cast<T>(attrs_.at(n));
+    return AttrFromBits<T>(attrs_.at(n));
   }
   const TensorDesc& OutputTensorDesc(const std::string& n, int32_t i) const { return out_.at({n, i}); }
 
@@ -595,7 +620,7 @@ class KernelComputeContext {
   DeviceType device_type() const { return dev_; }
   template <typename T>
   T Attr(const std::string& n) const {
-    return static_cast<T>(attrs_.at(n));
+    return AttrFromBits<T>(attrs_.at(n));
   }
   const ParallelContext& parallel_ctx() const { return pc_; }
   void set_parallel_ctx(ParallelContext pc) { pc_ = pc; }
@@ -696,7 +721,7 @@ struct InferSizeContext {
   }
   template <typename T>
   T Attr(const std::string& n) const {
-    return static_cast<T>(attrs.at(n));
+    return AttrFromBits<T>(attrs.at(n));
   }
 };
 
@@ -756,7 +781,7 @@ class OpRegistry {
   }
   template <typename T>
   OpRegistry& Attr(const std::string& n, T dflt = T()) {
-    r_.attrs.emplace_back(n, (int64_t)dflt);
+    r_.attrs.emplace_back(n, AttrBits<T>(dflt));
     return *this;
   }
   OpRegistry& SetLogicalTensorDescInferFn(std::function<Maybe<void>(InferContext*)> f) {

@@ -802,6 +802,63 @@ extern "C" int ofx_functional_edge_softmax_csr_heads_grad(
   });
 }
 
+// ---- functional::GatSoftmaxCsrHeads and its gradient functor ------------------------------------
+// Ops "gat_softmax_csr_heads" and "gat_softmax_csr_heads_grad"
+// (oneflow/user/ops/gat_softmax_heads_op.cpp) through the same op-registry dispatch
+// (INTEGRATION.md §13); negative_slope is the ops' double attr.
+namespace oneflow {
+
+int GatSoftmaxCsrHeads(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+                       const ofx_tensor_desc* s_row, const ofx_tensor_desc* s_col,
+                       const ofx_tensor_desc* y, const ofx_tensor_desc* dy, double negative_slope,
+                       ofx_tensor_desc* out, ofx_tensor_desc* d_row, void* tmp, size_t tmp_bytes,
+                       size_t* tmp_size_out, int num_threads) {
+  // an earlier launch's loud failure comes back here as OFX_EPLAN (as for spmm_csr)
+  if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("gat_softmax_csr_heads");
+  const user_op::AttrMap attrs = {{"negative_slope", user_op::AttrBits<double>(negative_slope)}};
+  if (dy == nullptr)
+    return ToStatus(RunUserOp("gat_softmax_csr_heads",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                               {"s_row", s_row}, {"s_col", s_col}},
+                              {{"out", out}}, attrs, stream, tmp, tmp_bytes, tmp_size_out,
+                              Placement(), -1, num_threads));
+  return ToStatus(RunUserOp("gat_softmax_csr_heads_grad",
+                            {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                             {"s_row", s_row}, {"s_col", s_col}, {"y", y}, {"dy", dy}},
+                            {{"ds", out}, {"d_row", d_row}}, attrs, stream, tmp, tmp_bytes,
+                            tmp_size_out, Placement(), -1, num_threads));
+}
+
+}  // namespace oneflow
+
+extern "C" int ofx_functional_gat_softmax_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                                    const ofx_tensor_desc* col_idx,
+                                                    const ofx_tensor_desc* s_row,
+                                                    const ofx_tensor_desc* s_col,
+                                                    double negative_slope, ofx_tensor_desc* out,
+                                                    void* tmp, size_t tmp_bytes,
+                                                    size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(s_row != nullptr && s_col != nullptr, OFX_EINVAL,
+                "gat_softmax_csr_heads: NULL input s_row or s_col");
+    return GatSoftmaxCsrHeads(stream, row_ptr, col_idx, s_row, s_col, nullptr, nullptr,
+                              negative_slope, out, nullptr, tmp, tmp_bytes, tmp_size_out, 0);
+  });
+}
+
+extern "C" int ofx_functional_gat_softmax_csr_heads_grad(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* s_row, const ofx_tensor_desc* s_col, const ofx_tensor_desc* y,
+    const ofx_tensor_desc* dy, double negative_slope, ofx_tensor_desc* ds, ofx_tensor_desc* d_row,
+    void* tmp, size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(s_row != nullptr && s_col != nullptr && y != nullptr && dy != nullptr, OFX_EINVAL,
+                "gat_softmax_csr_heads_grad: NULL input s_row, s_col, y or dy");
+    return GatSoftmaxCsrHeads(stream, row_ptr, col_idx, s_row, s_col, y, dy, negative_slope, ds,
+                              d_row, tmp, tmp_bytes, tmp_size_out, 0);
+  });
+}
+
 // ---- functional::GraphAttentionCsrHeads ----------------------------------------------------------
 // Op "graph_attention_csr_heads" (oneflow/user/ops/graph_attention_heads_op.cpp) through the same
 // op-registry dispatch; two outputs.

@@ -43,6 +43,15 @@ int EdgeSoftmaxCsrHeads(void* stream, const ofx_tensor_desc* row_ptr,
                         const ofx_tensor_desc* grad, ofx_tensor_desc* out, void* tmp,
                         size_t tmp_bytes, size_t* tmp_size_out, int num_threads);
 
+// functional::GatSoftmaxCsrHeads / GatSoftmaxCsrHeadsGrad: ops "gat_softmax_csr_heads" (dy == NULL:
+// s_row [M, H], s_col [K, H] -> out [nnz, H]) and "gat_softmax_csr_heads_grad" (y, dy [nnz, H] ->
+// out = ds [nnz, H], d_row [M, H]); negative_slope is the ops' attr.
+int GatSoftmaxCsrHeads(void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+                       const ofx_tensor_desc* s_row, const ofx_tensor_desc* s_col,
+                       const ofx_tensor_desc* y, const ofx_tensor_desc* dy, double negative_slope,
+                       ofx_tensor_desc* out, ofx_tensor_desc* d_row, void* tmp, size_t tmp_bytes,
+                       size_t* tmp_size_out, int num_threads);
+
 }  // namespace oneflow
 
 #endif  // OFX_ONEFLOW_CORE_FUNCTIONAL_SPMM_FUNCTOR_H_

@@ -568,6 +568,83 @@ def edge_softmax_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torc
     return dx
 
 
+def _check_gat_inputs(op, rp, ci, s_row, s_col, per_nonzero=()):
+    """The shape and dtype checks of the GAT ops: s_row [M, H], s_col [K, H] and the per-nonzero
+    tensors [nnz, H] of one dtype (s_row's) on one device."""
+    named = [("s_row", s_row), ("s_col", s_col), *per_nonzero]
+    for name, t in named:
+        if t.dim() != 2:
+            raise RuntimeError(f"{op}: {name} should be 2-D [rows, heads], got shape "
+                               f"{tuple(t.shape)}")
+        if t.shape[1] != s_row.shape[1]:
+            raise RuntimeError(f"{op}: {name} should have the number of heads of s_row "
+                               f"({t.shape[1]} vs {s_row.shape[1]})")
+        if t.dtype != s_row.dtype:
+            raise TypeError(f"{op}: {name} datatype should be equal to s_row "
+                            f"({t.dtype} vs {s_row.dtype})")
+        if t.device != s_row.device:
+            raise RuntimeError(f"{op}: expected all tensors on the same device, got {name} on "
+                               f"{t.device} and s_row on {s_row.device}")
+    if s_row.shape[0] != rp.numel() - 1:
+        raise RuntimeError(f"{op}: s_row should have a_num_rows = {rp.numel() - 1} rows, got "
+                           f"{s_row.shape[0]}")
+    for name, t in per_nonzero:
+        if t.shape[0] != ci.numel():
+            raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} rows (as "
+                               f"a_csr_col_idx), got {t.shape[0]}")
+    if rp.dtype != ci.dtype:
+        raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
+                        f"({ci.dtype} vs {rp.dtype})")
+    dtype_code(rp.dtype)
+    if s_row.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {s_row.dtype}")
+
+
+def gat_softmax_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                          s_row: torch.Tensor, s_col: torch.Tensor, negative_slope: float = 0.2, *,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "gat_softmax_csr_heads": out[j, h] = softmax over j's row of
+    LeakyReLU(s_row[row(j), h] + s_col[a_csr_col_idx[j], h]) for s_row [M, H] and s_col [K, H], in
+    one launch: exactly the bits of edge_softmax_csr_heads on the scores rounded to the dtype
+    (contract in include/ofx_spmm.h).  Non-contiguous inputs are copied first.  `out`: a contiguous
+    [nnz, H] tensor, written directly.  negative_slope must be finite and > 0."""
+    op = "gat_softmax_csr_heads"
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    s_row, s_col = _prep(s_row, "s_row"), _prep(s_col, "s_col")
+    _check_gat_inputs(op, rp, ci, s_row, s_col)
+    shape = (ci.numel(), s_row.shape[1])
+    if out is None:
+        out = torch.empty(shape, dtype=s_row.dtype, device=s_row.device)
+    else:
+        _check_out(op, out, shape, s_row, contiguous=True)
+    if out.numel() == 0:
+        return out
+    _run_grad_op(LIB.ofx_functional_gat_softmax_csr_heads, s_row, [rp, ci, s_row, s_col], [out],
+                 [float(negative_slope)])
+    return out
+
+
+def gat_softmax_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                               s_row: torch.Tensor, s_col: torch.Tensor, y: torch.Tensor,
+                               dy: torch.Tensor, negative_slope: float = 0.2):
+    """Op "gat_softmax_csr_heads_grad": (ds [nnz, H], d_row [M, H]) from the forward's stored y and
+    the upstream dy, one launch: ds = edge_softmax_csr_heads_grad(y, dy) times LeakyReLU's
+    derivative at the recomputed sum, d_row[r] = the sum of ds over r's nonzeros in the softmax's
+    order (+0 for an empty row)."""
+    op = "gat_softmax_csr_heads_grad"
+    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    s_row, s_col = _prep(s_row, "s_row"), _prep(s_col, "s_col")
+    y, dy = _prep(y, "y"), _prep(dy, "dy")
+    _check_gat_inputs(op, rp, ci, s_row, s_col, [("y", y), ("dy", dy)])
+    ds = torch.empty_like(y)
+    if ds.numel() == 0:  # nothing is written for nnz == 0 or H == 0: every row is empty
+        return ds, torch.zeros_like(s_row)
+    d_row = torch.empty_like(s_row)
+    _run_grad_op(LIB.ofx_functional_gat_softmax_csr_heads_grad, s_row,
+                 [rp, ci, s_row, s_col, y, dy], [ds, d_row], [float(negative_slope)])
+    return ds, d_row
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

@@ -14,6 +14,9 @@ Multi-head graph attention (q, k, v as [rows, H, D]; scores and weights as [nnz,
 or the three through one op (one fused kernel for the rows below the hub threshold), with the same
 bits and the same gradients:
     out = flow_spmm.graph_attention(row_ptr, col_idx, q, k, v)   # return_attention=True: (out, w)
+The original GAT layer (additive scores s_row [M, H] + s_col [K, H], LeakyReLU, softmax) in one launch:
+    w = flow_spmm.gat_softmax(row_ptr, col_idx, s_row, s_col, negative_slope=0.2)   # [nnz, H]
+    out = flow_spmm.gat_attention(row_ptr, col_idx, s_row, s_col, v)                 # [M, H, D]
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 
@@ -22,10 +25,10 @@ Re-exports mirror python/oneflow/__init__.py:158-160 (`from oneflow._C import ..
 from . import _C, _lib, autograd, build, ops, synth  # noqa: F401
 from ._C import spmm_csr, spmm_csr_reduce
 from ._lib import OfxError
-from .autograd import (csr_transpose, edge_softmax, fused_spmm, graph_attention, sddmm, spmm,
-                       spmm_reduce)
+from .autograd import (csr_transpose, edge_softmax, fused_spmm, gat_attention, gat_softmax,
+                       graph_attention, sddmm, spmm, spmm_reduce)
 from .build import coo_to_csr
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_reduce", "edge_softmax", "graph_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "_C"]
+__all__ = ["spmm", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "_C"]

@@ -465,6 +465,79 @@ def graph_attention(a_csr_row_ptr, a_csr_col_idx, q, k, v, *, return_attention=F
     return (out, attn) if return_attention else out
 
 
+class GatSoftmaxFunction(torch.autograd.Function):
+    """attn [nnz, H] = gat_softmax of s_row [M, H] and s_col [K, H] through op
+    "gat_softmax_csr_heads", differentiable in both.  The weights are saved; the backward is one
+    launch of op "gat_softmax_csr_heads_grad" (ds per nonzero and d(s_row), its row sums) and, only
+    when s_col needs a gradient, the multi-head SpMM of ds on the cached transpose with b = ones
+    (deterministic, no atomics, the same bits on CPU and GPU)."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, s_row, s_col, negative_slope):
+        s_row, s_col = s_row.contiguous(), s_col.contiguous()
+        attn = _C.gat_softmax_csr_heads(row_ptr, col_idx, s_row, s_col, negative_slope)
+        ctx.save_for_backward(row_ptr, col_idx, s_row, s_col, attn)
+        ctx.negative_slope = negative_slope
+        return attn
+
+    @staticmethod
+    def backward(ctx, d_attn):
+        row_ptr, col_idx, s_row, s_col, attn = ctx.saved_tensors
+        ds, d_row = _C.gat_softmax_csr_heads_grad(row_ptr, col_idx, s_row, s_col, attn,
+                                                  d_attn.contiguous(), ctx.negative_slope)
+        d_col = None
+        if ctx.needs_input_grad[3]:
+            d_col = _heads_grad_b(row_ptr, col_idx, ds, s_row.shape[0], s_col.shape[0],
+                                  torch.ones_like(s_row))
+        return None, None, d_row if ctx.needs_input_grad[2] else None, d_col, None
+
+
+def gat_softmax(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, negative_slope=0.2, *, out=None):
+    """The attention weights of a GAT layer over a CSR, in one launch:
+        attn[j, h] = softmax over j's row of LeakyReLU(s_row[row(j), h] + s_col[col[j], h])
+    for s_row [M, H] (a_l . W h_i per destination) and s_col [K, H] (a_r . W h_j per source);
+    1-D s_row [M] and s_col [K] mean H = 1 and return attn [nnz].  The scores are rounded to the
+    dtype before the softmax and never written: attn has exactly the bits of
+    `edge_softmax(rp, ci, e)` on them, on CPU and GPU tensors.  negative_slope must
+    be finite and > 0 (0 would turn a -inf mask into NaN).  Differentiable in s_row and s_col; the
+    gradient in s_col is built only when it is needed.  Non-contiguous inputs are made contiguous
+    first; `out=` (a contiguous [nnz, H] tensor, [nnz] for 1-D inputs) only when no gradient is
+    being recorded."""
+    if s_row.dim() != s_col.dim() or s_row.dim() not in (1, 2):
+        raise RuntimeError("gat_softmax: s_row [M, H] and s_col [K, H] (or s_row [M] and s_col "
+                           f"[K]) are expected, got {tuple(s_row.shape)} and {tuple(s_col.shape)}")
+    flat = s_row.dim() == 1
+    if flat:
+        s_row, s_col = s_row.unsqueeze(1), s_col.unsqueeze(1)
+    negative_slope = float(negative_slope)
+    if torch.is_grad_enabled() and (s_row.requires_grad or s_col.requires_grad):
+        if out is not None:
+            raise RuntimeError("gat_softmax: out= is not supported when gradients are required")
+        attn = GatSoftmaxFunction.apply(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, negative_slope)
+        return attn.squeeze(1) if flat else attn
+    if flat and out is not None:
+        if out.dim() != 1 or not out.is_contiguous():
+            raise RuntimeError("gat_softmax: out must be a contiguous [nnz] tensor for 1-D "
+                               f"inputs, got {tuple(out.shape)}")
+        _C.gat_softmax_csr_heads(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, negative_slope,
+                                 out=out.unsqueeze(1))
+        return out
+    attn = _C.gat_softmax_csr_heads(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, negative_slope,
+                                    out=out)
+    return attn.squeeze(1) if flat else attn
+
+
+def gat_attention(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, v, negative_slope=0.2, *,
+                  return_attention=False):
+    """A GAT layer's aggregation: out = spmm(rp, ci, gat_softmax(rp, ci, s_row, s_col,
+    negative_slope), M, K, v) for s_row [M, H], s_col [K, H] and v [K, H, D] (out [M, H, D]), or
+    1-D s_row, s_col and v [K, D] (out [M, D]).  Plain composition of the two ops: their bits and
+    their gradients.  Returns out, or (out, attn) with return_attention=True."""
+    attn = gat_softmax(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, negative_slope)
+    out = spmm(a_csr_row_ptr, a_csr_col_idx, attn, s_row.shape[0], s_col.shape[0], v)
+    return (out, attn) if return_attention else out
+
+
 class SpmmCsrReduceFunction(torch.autograd.Function):
     """(out, arg) = spmm_csr_reduce(..., reduce) for reduce in {"mean", "max", "min"},
     differentiable in `a_csr_values` and `b`; `arg` is not differentiable.
@@ -600,4 +673,5 @@ def fused_spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_col
 __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm", "TRANSPOSE_CACHE", "ops",
            "FusedSpmmCsrFunction", "fused_spmm", "SpmmCsrReduceFunction", "spmm_reduce",
            "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax", "SpmmCsrHeadsFunction",
-           "SddmmCsrHeadsFunction", "EdgeSoftmaxHeadsFunction"]
+           "SddmmCsrHeadsFunction", "EdgeSoftmaxHeadsFunction", "GatSoftmaxFunction", "gat_softmax",
+           "gat_attention"]
