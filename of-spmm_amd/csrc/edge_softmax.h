@@ -1,13 +1,17 @@
 // edge_softmax.h — what the kCPU kernels (edge_softmax_cpu.cpp) and the HIP kernels
 // (edge_softmax.hip, edge_softmax_heads.hip) of ops "edge_softmax_csr", "edge_softmax_csr_heads"
-// and of their gradients share: the exponential, the constants of the sum's order, the argument
-// checks of their C-ABI entries and, for the HIP units, the device steps of a leaf, the lane-group
-// butterflies and the tile stack (contract in include/ofx_spmm.h).  The
-// multi-head rows take a leaf source, so that gat_softmax_heads.hip runs the same
-// rows on scores it forms from a gather; gat_softmax_cpu.cpp shares the host's row step.
+// and of their gradients share: the exponential, the constants of the sum's order, the host's row
+// steps, the argument checks and the workspace query of their C-ABI entries and, for the HIP units,
+// the host side of a launch (the lane-group rule, the packed-path predicate), the device steps of a
+// leaf, the lane-group butterflies and the tile stack (contract in include/ofx_spmm.h, DESIGN.md
+// §3e and §3f).  The multi-head rows take a leaf source, so that gat_softmax_heads.hip (DESIGN.md
+// §3h) runs the same rows on scores it forms from a gather; gat_softmax_cpu.cpp shares the host's
+// row steps.
 #ifndef OFX_EDGE_SOFTMAX_H_
 #define OFX_EDGE_SOFTMAX_H_
 
+#include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "ofx_internal.h"
@@ -131,6 +135,27 @@ void softmax_row(typename Num<T>::acc* x, int64_t len, std::vector<typename Num<
   }
 }
 
+// One head's row of the gradient: y and g at element stride `stride`; sink(p, de) takes
+// de = y[p] * (g[p] - sum(y * g)) rounded to T, position by position.  q: scratch of len values,
+// not read once the sum is formed, so a sink may reuse it.  len > 0.
+template <typename T, typename Sink>
+void softmax_grad_row(const T* y, const T* g, int64_t stride, int64_t len,
+                      typename Num<T>::acc* q, std::vector<typename Num<T>::acc>& leaf,
+                      Sink&& sink) {
+#pragma clang fp contract(off)
+  using A = typename Num<T>::acc;
+  for (int64_t p = 0; p < len; ++p) {
+    const A prod = Num<T>::load(y[p * stride]) * Num<T>::load(g[p * stride]);
+    q[p] = prod;
+  }
+  const A d = tree_sum(q, len, leaf);
+  for (int64_t p = 0; p < len; ++p) {
+    const A diff = Num<T>::load(g[p * stride]) - d;
+    const A prod = Num<T>::load(y[p * stride]) * diff;
+    sink(p, Num<T>::store(canonical_nan(prod)));
+  }
+}
+
 // ---- argument checks shared by the device and host entries ----------------------------------
 static inline int check_edge_softmax_args(const char* fn, int idx_dtype, int val_dtype, int64_t m,
                                           int64_t nnz, int64_t row_begin, int64_t row_end) {
@@ -148,20 +173,73 @@ static inline int check_edge_softmax_heads_args(const char* fn, int idx_dtype, i
   return check_edge_softmax_args(fn, idx_dtype, val_dtype, m, nnz, row_begin, row_end);
 }
 
+// The body of the family's *_workspace_size entries (the edge softmax: heads = 1 and k = 0 for the
+// single-head op; the GAT weights of gat_softmax_heads.hip, whose columns number k): no op of the
+// family plans or keeps partials, so a valid shape needs 0 bytes.
+static inline int softmax_workspace_size(const char* fn, int idx_dtype, int val_dtype, int64_t m,
+                                         int64_t k, int64_t heads, int64_t nnz,
+                                         const ofx_spmm_options* opts, size_t* bytes) {
+  OFX_READ_OPTIONS(opts, fn);
+  OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "%s: NULL bytes", fn);
+  OFX_REQUIRE(k >= 0, OFX_EINVAL, "%s: negative k=%lld", fn, (long long)k);
+  if (const int rc = check_edge_softmax_heads_args(fn, idx_dtype, val_dtype, m, heads, nnz, 0, m))
+    return rc;
+  *bytes = 0;
+  return OFX_OK;
+}
+
 }  // namespace esm
 }  // namespace ofx
 
 #if defined(__HIP__)
-// ---- what the HIP units (edge_softmax.hip, edge_softmax_heads.hip) share on the device ----------
-// The steps of one row's leaf (kLeaf positions in a lane's registers), the lane-group butterflies
-// and the binary-counter stack of a long row's tiles.  Both units take every arithmetic step from
-// here, so a head's column has the single-head op's bits by construction.
 #include <hip/hip_runtime.h>
 
 #include "spmm_items_dev.h"
 
 namespace ofx {
 namespace esm {
+
+// ---- the host side of a launch, shared by the HIP units of the family ---------------------------
+// The lane group of a launch: the narrowest of 1, 4, 16, 64 lanes whose capacity (kLeaf positions
+// per lane) is at least `want`.  Speed only: the bits do not depend on it, so no test can see it
+// move; its boundaries are pinned here.
+constexpr int group_lanes(int64_t want) {
+  int lg = 1;
+  while (lg < 64 && (int64_t)lg * kLeaf < want) lg *= 4;
+  return lg;
+}
+static_assert(group_lanes(0) == 1 && group_lanes(8) == 1 && group_lanes(9) == 4 &&
+                  group_lanes(32) == 4 && group_lanes(33) == 16 && group_lanes(128) == 16 &&
+                  group_lanes(129) == 64,
+              "the lane-group rule's boundaries");
+
+// `want` of a launch over nrows > 0 of the matrix's m rows: twice the mean degree of its rows, so
+// that most rows fit their group and few wait for the wave.
+inline int launch_group_lanes(int64_t m, int64_t nrows, int64_t nnz, const ofx_spmm_options* opts) {
+  return group_lanes(2 * (launch_nnz(m, nrows, nnz, opts) / nrows));
+}
+
+// f(std::integral_constant<int, LG>) for a run-time lane group: a kernel's instantiation per
+// width (spmm_forward_rules.h with_lanes).
+template <typename F>
+int with_group_lanes(int lg, F&& f) {
+  switch (lg) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
+}
+
+// ---- what the HIP units share on the device -----------------------------------------------------
+// The steps of one row's leaf (kLeaf positions in a lane's registers), the lane-group butterflies
+// and the binary-counter stack of a long row's tiles.  The units take every arithmetic step from
+// here, so a head's column has the single-head op's bits by construction.
+// These kernels' code generation moves with the inlining structure: passing g + off instead of
+// g, off, or building a leaf source at the call site instead of inside a wrapper, changes the
+// registers and instruction counts of every kernel that goes through it.  A change here is checked
+// by per-kernel assembly comparison (`make asm`, scripts/kernel_asm_diff.py); DESIGN.md §3h has
+// the record of what was tried.
 
 // The rounding to T of a quotient or product, as a step of its own: the value passes through a
 // register between the arithmetic and the conversion, so no mixed-precision multiply-convert
@@ -273,7 +351,8 @@ __device__ __forceinline__ A stack_fold(A stk, int64_t tiles) {
   return s;
 }
 
-// ---- the multi-head rows (edge_softmax_heads.hip, phase 2 of graph_attention_heads.hip) ---------
+// ---- the multi-head rows (edge_softmax_heads.hip, gat_softmax_heads.hip, phase 2 of
+// graph_attention_heads.hip) ----------------------------------------------------------------------
 // Pointers are not restrict-qualified: the fused attention kernel normalises its scores in place
 // (a == out; every position is read and written by the same lane, reads first).
 }  // namespace esm
@@ -319,6 +398,28 @@ constexpr int packed_heads() {
   return sizeof(T) == 8 ? 2 : 4;
 }
 
+// Whether a launch takes the packed path (host): whole vectors of V heads, and every base that is
+// loaded or stored as one aligned to V * sizeof(T).  A NULL base (an operand the direction does
+// not have) counts as aligned.
+template <typename T, int V>
+bool heads_packed(int64_t heads, std::initializer_list<const void*> bases) {
+  bool ok = heads % V == 0;
+  for (const void* p : bases) ok = ok && (uintptr_t)p % (V * sizeof(T)) == 0;
+  return ok;
+}
+
+// Item gi = row * G + head group, in 32 bits where both fit.
+__device__ __forceinline__ void split_item(int64_t gi, int64_t G, int64_t* row, int64_t* hg) {
+  if ((((uint64_t)gi | (uint64_t)G) >> 32) == 0) {
+    const uint32_t r = (uint32_t)gi / (uint32_t)G;
+    *row = r;
+    *hg = (uint32_t)gi - r * (uint32_t)G;
+  } else {
+    *row = gi / G;
+    *hg = gi - *row * G;
+  }
+}
+
 // x[v][i] = load(p[(pos + i) * H + v]) for the leaf's positions inside [0, len), `fill` for the
 // others; p points at the row's first position and the lane's first head.  len > 0.
 template <typename T, int V>
@@ -334,22 +435,6 @@ __device__ __forceinline__ void load_leaf_heads(const T* p, int64_t H, int64_t p
     const typename HV::Elems el = __builtin_bit_cast(typename HV::Elems, raw);
 #pragma unroll
     for (int v = 0; v < V; ++v) x[v][i] = in ? Num<T>::load(el.v[v]) : fill;
-  }
-}
-
-// The same for a group that may have no row (len == 0: nothing is loaded).
-template <typename T, int V>
-__device__ __forceinline__ void load_leaf_heads_or_fill(const T* p, int64_t H,
-                                                        int64_t pos, int64_t len,
-                                                        typename Num<T>::acc fill,
-                                                        typename Num<T>::acc (&x)[V][kLeaf]) {
-  if (len > 0) {
-    load_leaf_heads<T, V>(p, H, pos, len, fill, x);
-  } else {
-#pragma unroll
-    for (int v = 0; v < V; ++v)
-#pragma unroll
-      for (int i = 0; i < kLeaf; ++i) x[v][i] = fill;
   }
 }
 
@@ -420,7 +505,7 @@ __device__ __forceinline__ void row_in_registers_of(const Src& src, const T* g, 
   } else {
     A gg[V][kLeaf];
     load_leaf_or_fill<T, V>(src, pos, len, A(0), x);
-    load_leaf_heads_or_fill<T, V>(g + off, H, pos, len, A(0), gg);
+    load_leaf_or_fill<T, V>(MemoryLeaves<T, V>{g + off, H}, pos, len, A(0), gg);
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const A d = group_sum<A, LG>(leaf_dot<A>(x[v], gg[v]));

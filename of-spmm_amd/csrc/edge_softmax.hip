@@ -3,12 +3,13 @@
 // exponential and the constants of the sum's order in edge_softmax.h).
 //
 // One lane group of LG lanes per row of the identity work list (work_item with skip_empty; no
-// plan is read, so no plan can be invalid).  LG is picked per launch from the mean degree.  Lane t
-// of a group holds the row's leaf t (8 consecutive positions) in registers, loaded and stored 16
-// bytes at a time at whatever alignment the row starts (exact on gfx950, probes/unaligned_probe.hip;
-// a vector is taken only where it lies wholly inside the row, so nothing outside the launch's
-// nonzeros is read or written).  The maximum and the tree sum both go through the SDDMM's xor
-// butterfly.  A row that fits its group (at most 8 LG elements) is read once and written once.
+// plan is read, so no plan can be invalid).  LG is picked per launch from the mean degree by the
+// family's rule (edge_softmax.h launch_group_lanes).  Lane t of a group holds the row's leaf t (8
+// consecutive positions) in registers, loaded and stored 16 bytes at a time at whatever alignment
+// the row starts (exact on gfx950, probes/unaligned_probe.hip; a vector is taken only where it
+// lies wholly inside the row, so nothing outside the launch's nonzeros is read or written).  The
+// maximum and the tree sum both go through the SDDMM's xor butterfly.  A row that fits its group
+// (at most 8 LG elements) is read once and written once.
 //
 // Longer rows are taken over by the whole wave, one after another: up to kTile = 512 elements the
 // wave is the lane group (still read once); beyond, the row is swept in tiles of 64 leaves, whose
@@ -277,28 +278,15 @@ int esm_cfg(const EsmArgs& x) {
   });
 }
 
-// The lane group of a launch: the narrowest whose capacity (8 LG) is at least twice the mean
-// degree of the launch's rows, so that most rows fit their group and few wait for the wave.
-// Speed only: the bits do not depend on it.  OFX_ESM_LG forces one width (A/B builds).
-#ifndef OFX_ESM_LG
-#define OFX_ESM_LG 0
-#endif
-template <typename T, typename I, bool BWD>
-int esm_width(const EsmArgs& x) {
-  const int64_t est = launch_nnz(x.m, x.nrows, x.nnz, x.opts);
-  const int64_t want = OFX_ESM_LG > 0 ? (int64_t)OFX_ESM_LG * kLeaf : 2 * (est / x.nrows);
-  if (want <= 1 * kLeaf) return esm_cfg<T, I, 1, BWD>(x);
-  if (want <= 4 * kLeaf) return esm_cfg<T, I, 4, BWD>(x);
-  if (want <= 16 * kLeaf) return esm_cfg<T, I, 16, BWD>(x);
-  return esm_cfg<T, I, 64, BWD>(x);
-}
-
+// The lane group by the family's rule (edge_softmax.h launch_group_lanes).
 template <bool BWD>
 int esm_launch(int idx_dtype, int val_dtype, const EsmArgs& x) {
   return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
     using T = std::remove_pointer_t<decltype(tp)>;
     using I = std::remove_pointer_t<decltype(ip)>;
-    return esm_width<T, I, BWD>(x);
+    return with_group_lanes(launch_group_lanes(x.m, x.nrows, x.nnz, x.opts), [&](auto lanes) {
+      return esm_cfg<T, I, decltype(lanes)::value, BWD>(x);
+    });
   });
 }
 
@@ -324,13 +312,8 @@ extern "C" int ofx_edge_softmax_csr_workspace_size(int idx_dtype, int val_dtype,
                                                    int64_t nnz, const ofx_spmm_options* opts,
                                                    size_t* bytes) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_READ_OPTIONS(opts, "edge_softmax_csr_workspace_size");
-    OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "edge_softmax_csr_workspace_size: NULL bytes");
-    if (const int rc = check_edge_softmax_args("edge_softmax_csr_workspace_size", idx_dtype,
-                                               val_dtype, m, nnz, 0, m))
-      return rc;
-    *bytes = 0;  // no plan, no partials
-    return OFX_OK;
+    return softmax_workspace_size("edge_softmax_csr_workspace_size", idx_dtype, val_dtype, m, 0, 1,
+                                  nnz, opts, bytes);
   });
 }
 
@@ -339,10 +322,7 @@ extern "C" int ofx_edge_softmax_csr(void* stream, int idx_dtype, int val_dtype, 
                                     int64_t row_begin, int64_t row_end, void* workspace,
                                     size_t workspace_bytes, const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_TAKE_DEVICE_ERROR("edge_softmax_csr");  // an earlier launch's loud failure (spmm_plan.h)
-    OFX_READ_OPTIONS(opts, "edge_softmax_csr");
-    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
-                "edge_softmax_csr: NULL workspace of %zu bytes", workspace_bytes);
+    OFX_DEVICE_ENTRY("edge_softmax_csr", opts, workspace, workspace_bytes);
     return esm_entry<false>("edge_softmax_csr", stream, idx_dtype, val_dtype, m, nnz, row_ptr, e,
                             nullptr, y, row_begin, row_end, opts);
   });
@@ -354,10 +334,7 @@ extern "C" int ofx_edge_softmax_csr_grad(void* stream, int idx_dtype, int val_dt
                                          int64_t row_end, void* workspace, size_t workspace_bytes,
                                          const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_TAKE_DEVICE_ERROR("edge_softmax_csr_grad");
-    OFX_READ_OPTIONS(opts, "edge_softmax_csr_grad");
-    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
-                "edge_softmax_csr_grad: NULL workspace of %zu bytes", workspace_bytes);
+    OFX_DEVICE_ENTRY("edge_softmax_csr_grad", opts, workspace, workspace_bytes);
     return esm_entry<true>("edge_softmax_csr_grad", stream, idx_dtype, val_dtype, m, nnz, row_ptr,
                            y, g, de, row_begin, row_end, opts);
   });

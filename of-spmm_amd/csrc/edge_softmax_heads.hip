@@ -40,20 +40,9 @@ using namespace item;
 using namespace esm;
 using namespace esmh;
 
-// The head vectors, the leaf loads and stores at stride H and the rows in registers / in tiles / by
-// the wave are edge_softmax.h's: graph_attention_heads.hip runs the same steps in place.
-
-// gi = row * G + head group, in 32 bits where both fit.
-__device__ __forceinline__ void split_item(int64_t gi, int64_t G, int64_t* row, int64_t* hg) {
-  if ((((uint64_t)gi | (uint64_t)G) >> 32) == 0) {
-    const uint32_t r = (uint32_t)gi / (uint32_t)G;
-    *row = r;
-    *hg = (uint32_t)gi - r * (uint32_t)G;
-  } else {
-    *row = gi / G;
-    *hg = gi - *row * G;
-  }
-}
+// The head vectors, the item's split, the leaf loads and stores at stride H and the rows in
+// registers / in tiles / by the wave are edge_softmax.h's: graph_attention_heads.hip runs the same
+// steps in place.
 
 template <typename T, typename I, int V, int LG, bool BWD>
 __global__ void __launch_bounds__(kBlock)
@@ -109,26 +98,16 @@ int esmh_cfg(const EsmHeadsArgs& x) {
   });
 }
 
-// The lane group of a launch, by the single-head op's rule (edge_softmax.hip esm_width): the
-// narrowest whose capacity (8 LG) is at least twice the mean degree of the launch's rows.  Speed
-// only: the bits do not depend on it.
-template <typename T, typename I, int V, bool BWD>
-int esmh_width(const EsmHeadsArgs& x) {
-  const int64_t est = launch_nnz(x.m, x.nrows, x.nnz, x.opts);
-  const int64_t want = 2 * (est / x.nrows);
-  if (want <= 1 * kLeaf) return esmh_cfg<T, I, V, 1, BWD>(x);
-  if (want <= 4 * kLeaf) return esmh_cfg<T, I, V, 4, BWD>(x);
-  if (want <= 16 * kLeaf) return esmh_cfg<T, I, V, 16, BWD>(x);
-  return esmh_cfg<T, I, V, 64, BWD>(x);
-}
-
+// The path and the lane group by the family's rules (edge_softmax.h heads_packed,
+// launch_group_lanes); the forward has no g.
 template <typename T, typename I, bool BWD>
 int esmh_typed(const EsmHeadsArgs& x) {
   constexpr int V = packed_heads<T>();
-  constexpr uintptr_t kVecBytes = V * sizeof(T);
-  const bool packed = x.heads % V == 0 && (uintptr_t)x.a % kVecBytes == 0 &&
-                      (uintptr_t)x.out % kVecBytes == 0 && (!BWD || (uintptr_t)x.g % kVecBytes == 0);
-  return packed ? esmh_width<T, I, V, BWD>(x) : esmh_width<T, I, 1, BWD>(x);
+  const bool packed = heads_packed<T, V>(x.heads, {x.a, x.g, x.out});
+  return with_group_lanes(launch_group_lanes(x.m, x.nrows, x.nnz, x.opts), [&](auto lanes) {
+    constexpr int LG = decltype(lanes)::value;
+    return packed ? esmh_cfg<T, I, V, LG, BWD>(x) : esmh_cfg<T, I, 1, LG, BWD>(x);
+  });
 }
 
 template <bool BWD>
@@ -166,13 +145,8 @@ extern "C" int ofx_edge_softmax_csr_heads_workspace_size(int idx_dtype, int val_
                                                          const ofx_spmm_options* opts,
                                                          size_t* bytes) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads_workspace_size");
-    OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "edge_softmax_csr_heads_workspace_size: NULL bytes");
-    if (const int rc = check_edge_softmax_heads_args("edge_softmax_csr_heads_workspace_size",
-                                                     idx_dtype, val_dtype, m, heads, nnz, 0, m))
-      return rc;
-    *bytes = 0;  // no plan, no partials
-    return OFX_OK;
+    return softmax_workspace_size("edge_softmax_csr_heads_workspace_size", idx_dtype, val_dtype, m,
+                                  0, heads, nnz, opts, bytes);
   });
 }
 
@@ -182,10 +156,7 @@ extern "C" int ofx_edge_softmax_csr_heads(void* stream, int idx_dtype, int val_d
                                           int64_t row_end, void* workspace, size_t workspace_bytes,
                                           const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_TAKE_DEVICE_ERROR("edge_softmax_csr_heads");  // an earlier launch's loud failure
-    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads");
-    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
-                "edge_softmax_csr_heads: NULL workspace of %zu bytes", workspace_bytes);
+    OFX_DEVICE_ENTRY("edge_softmax_csr_heads", opts, workspace, workspace_bytes);
     return esmh_entry<false>("edge_softmax_csr_heads", stream, idx_dtype, val_dtype, m, heads, nnz,
                              row_ptr, e, nullptr, y, row_begin, row_end, opts);
   });
@@ -198,10 +169,7 @@ extern "C" int ofx_edge_softmax_csr_heads_grad(void* stream, int idx_dtype, int 
                                                void* workspace, size_t workspace_bytes,
                                                const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_TAKE_DEVICE_ERROR("edge_softmax_csr_heads_grad");
-    OFX_READ_OPTIONS(opts, "edge_softmax_csr_heads_grad");
-    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
-                "edge_softmax_csr_heads_grad: NULL workspace of %zu bytes", workspace_bytes);
+    OFX_DEVICE_ENTRY("edge_softmax_csr_heads_grad", opts, workspace, workspace_bytes);
     return esmh_entry<true>("edge_softmax_csr_heads_grad", stream, idx_dtype, val_dtype, m, heads,
                             nnz, row_ptr, y, g, de, row_begin, row_end, opts);
   });

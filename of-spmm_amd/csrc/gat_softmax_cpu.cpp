@@ -3,7 +3,8 @@
 // gat_softmax.h and edge_softmax.h).  Row-parallel over OpenMP like edge_softmax_cpu.cpp; the same
 // bits as the HIP kernels (gat_softmax_heads.hip).  A head's scores are formed, rounded to T and
 // handed to the edge softmax's own row step (esm::softmax_row), so attn has the bits of
-// ofx_edge_softmax_csr_heads on those scores by construction.
+// ofx_edge_softmax_csr_heads on those scores by construction; the gradient takes de from the edge
+// softmax's gradient row (esm::softmax_grad_row) in the same way.
 #pragma clang fp contract(off)
 
 #include <omp.h>
@@ -82,31 +83,21 @@ void cpu_backward(int nthreads, const I* rp, const I* ci, const T* s_row, const 
       }
       q.resize((size_t)len);
       for (int64_t h = 0; h < heads; ++h) {
-        const T* yh = y + j0 * heads + h;
-        const T* gh = g + j0 * heads + h;
         T* dh = ds + j0 * heads + h;
         const A sr = Num<T>::load(s_row[(r - row_begin) * heads + h]);
-        for (int64_t p = 0; p < len; ++p) {
-          const A prod = Num<T>::load(yh[p * heads]) * Num<T>::load(gh[p * heads]);
-          q[(size_t)p] = prod;
-        }
-        const A d = tree_sum(q.data(), len, leaf);
-        for (int64_t p = 0; p < len; ++p) {
-          const A diff = Num<T>::load(gh[p * heads]) - d;
-          const A prod = Num<T>::load(yh[p * heads]) * diff;
-          const T de = Num<T>::store(canonical_nan(prod));
-          const A z = score_sum<T, I>(sr, s_col + h, ci, j0 + p, heads, k);
-          const A scaled = Num<T>::load(de) * leaky_factor<A>(z, slope);
-          dh[p * heads] = Num<T>::store(canonical_nan(scaled));
-          q[(size_t)p] = Num<T>::load(dh[p * heads]);
-        }
+        // the edge softmax's de, scaled by the activation's factor; q collects the second sum
+        softmax_grad_row<T>(y + j0 * heads + h, g + j0 * heads + h, heads, len, q.data(), leaf,
+                            [&](int64_t p, T de) {
+                              const A z = score_sum<T, I>(sr, s_col + h, ci, j0 + p, heads, k);
+                              const A scaled = Num<T>::load(de) * leaky_factor<A>(z, slope);
+                              dh[p * heads] = Num<T>::store(canonical_nan(scaled));
+                              q[(size_t)p] = Num<T>::load(dh[p * heads]);
+                            });
         dr[h] = Num<T>::store(canonical_nan(tree_sum(q.data(), len, leaf)));
       }
     }
   }
 }
-
-int threads_of(int num_threads) { return num_threads > 0 ? num_threads : omp_get_max_threads(); }
 
 }  // namespace
 }  // namespace ofx

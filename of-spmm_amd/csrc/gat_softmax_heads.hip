@@ -172,8 +172,8 @@ __device__ __forceinline__ void grad_row_in_registers(const GatLeaves<T, I, V>& 
   using A = typename Num<T>::acc;
   const int64_t pos = (int64_t)gl * kLeaf;
   A x[V][kLeaf], gg[V][kLeaf], d[V];
-  load_leaf_heads_or_fill<T, V>(y, H, pos, len, A(0), x);
-  load_leaf_heads_or_fill<T, V>(g, H, pos, len, A(0), gg);
+  load_leaf_or_fill<T, V>(MemoryLeaves<T, V>{y, H}, pos, len, A(0), x);
+  load_leaf_or_fill<T, V>(MemoryLeaves<T, V>{g, H}, pos, len, A(0), gg);
 #pragma unroll
   for (int v = 0; v < V; ++v) d[v] = group_sum<A, LG>(leaf_dot<A>(x[v], gg[v]));
   grad_leaf<T, I, V>(src, x, gg, d, ds, H, pos, len, dr);
@@ -224,18 +224,6 @@ __device__ __forceinline__ void store_row_sum(T* p, const typename Num<T>::acc (
 #pragma unroll
   for (int v = 0; v < V; ++v) el.v[v] = store_rounded<T>(dr[v]);
   *reinterpret_cast<typename HV::Raw*>(p) = __builtin_bit_cast(typename HV::Raw, el);
-}
-
-// gi = row * G + head group, in 32 bits where both fit.
-__device__ __forceinline__ void split_item(int64_t gi, int64_t G, int64_t* row, int64_t* hg) {
-  if ((((uint64_t)gi | (uint64_t)G) >> 32) == 0) {
-    const uint32_t r = (uint32_t)gi / (uint32_t)G;
-    *row = r;
-    *hg = (uint32_t)gi - r * (uint32_t)G;
-  } else {
-    *row = gi / G;
-    *hg = gi - *row * G;
-  }
 }
 
 struct Geometry {
@@ -341,26 +329,17 @@ int gat_cfg(const GatArgs& x) {
   });
 }
 
-// The lane group of a launch, by the edge softmax's rule (edge_softmax_heads.hip esmh_width).
-// Speed only: the bits do not depend on it.
-template <typename T, typename I, int V, bool BWD>
-int gat_width(const GatArgs& x) {
-  const int64_t est = launch_nnz(x.m, x.nrows, x.nnz, x.opts);
-  const int64_t want = 2 * (est / x.nrows);
-  if (want <= 1 * kLeaf) return gat_cfg<T, I, V, 1, BWD>(x);
-  if (want <= 4 * kLeaf) return gat_cfg<T, I, V, 4, BWD>(x);
-  if (want <= 16 * kLeaf) return gat_cfg<T, I, V, 16, BWD>(x);
-  return gat_cfg<T, I, V, 64, BWD>(x);
-}
-
+// The path and the lane group by the edge softmax's rules (edge_softmax.h heads_packed,
+// launch_group_lanes); the forward has no y, g and d_row.
 template <typename T, typename I, bool BWD>
 int gat_typed(const GatArgs& x) {
   constexpr int V = packed_heads<T>();
-  constexpr uintptr_t kVecBytes = V * sizeof(T);
-  const auto aligned = [](const void* p) { return (uintptr_t)p % kVecBytes == 0; };
-  const bool packed = x.heads % V == 0 && aligned(x.s_row) && aligned(x.s_col) && aligned(x.out) &&
-                      (!BWD || (aligned(x.y) && aligned(x.g) && aligned(x.d_row)));
-  return packed ? gat_width<T, I, V, BWD>(x) : gat_width<T, I, 1, BWD>(x);
+  const bool packed =
+      heads_packed<T, V>(x.heads, {x.s_row, x.s_col, x.out, x.y, x.g, x.d_row});
+  return with_group_lanes(launch_group_lanes(x.m, x.nrows, x.nnz, x.opts), [&](auto lanes) {
+    constexpr int LG = decltype(lanes)::value;
+    return packed ? gat_cfg<T, I, V, LG, BWD>(x) : gat_cfg<T, I, 1, LG, BWD>(x);
+  });
 }
 
 template <bool BWD>
@@ -393,15 +372,8 @@ extern "C" int ofx_gat_softmax_csr_heads_workspace_size(int idx_dtype, int val_d
                                                         const ofx_spmm_options* opts,
                                                         size_t* bytes) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_READ_OPTIONS(opts, "gat_softmax_csr_heads_workspace_size");
-    OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "gat_softmax_csr_heads_workspace_size: NULL bytes");
-    OFX_REQUIRE(k >= 0, OFX_EINVAL, "gat_softmax_csr_heads_workspace_size: negative k=%lld",
-                (long long)k);
-    if (const int rc = check_edge_softmax_heads_args("gat_softmax_csr_heads_workspace_size",
-                                                     idx_dtype, val_dtype, m, heads, nnz, 0, m))
-      return rc;
-    *bytes = 0;  // no plan, no partials
-    return OFX_OK;
+    return softmax_workspace_size("gat_softmax_csr_heads_workspace_size", idx_dtype, val_dtype, m,
+                                  k, heads, nnz, opts, bytes);
   });
 }
 
@@ -413,10 +385,7 @@ extern "C" int ofx_gat_softmax_csr_heads(void* stream, int idx_dtype, int val_dt
                                          int64_t row_end, void* workspace, size_t workspace_bytes,
                                          const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_TAKE_DEVICE_ERROR("gat_softmax_csr_heads");  // an earlier launch's loud failure
-    OFX_READ_OPTIONS(opts, "gat_softmax_csr_heads");
-    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
-                "gat_softmax_csr_heads: NULL workspace of %zu bytes", workspace_bytes);
+    OFX_DEVICE_ENTRY("gat_softmax_csr_heads", opts, workspace, workspace_bytes);
     return gat_entry<false>("gat_softmax_csr_heads", stream, idx_dtype, val_dtype, m, k, heads,
                             nnz, row_ptr, col_idx, s_row, s_col, negative_slope, nullptr, nullptr,
                             attn, nullptr, row_begin, row_end, opts);
@@ -433,10 +402,7 @@ extern "C" int ofx_gat_softmax_csr_heads_grad(void* stream, int idx_dtype, int v
                                               size_t workspace_bytes,
                                               const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_TAKE_DEVICE_ERROR("gat_softmax_csr_heads_grad");
-    OFX_READ_OPTIONS(opts, "gat_softmax_csr_heads_grad");
-    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
-                "gat_softmax_csr_heads_grad: NULL workspace of %zu bytes", workspace_bytes);
+    OFX_DEVICE_ENTRY("gat_softmax_csr_heads_grad", opts, workspace, workspace_bytes);
     return gat_entry<true>("gat_softmax_csr_heads_grad", stream, idx_dtype, val_dtype, m, k, heads,
                            nnz, row_ptr, col_idx, s_row, s_col, negative_slope, attn, g, ds, d_row,
                            row_begin, row_end, opts);

@@ -343,10 +343,7 @@ extern "C" int ofx_graph_attention_csr_heads(void* stream, int idx_dtype, int va
                                              size_t workspace_bytes,
                                              const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    OFX_TAKE_DEVICE_ERROR("graph_attention_csr_heads");  // an earlier launch's loud failure
-    OFX_READ_OPTIONS(opts, "graph_attention_csr_heads");
-    OFX_REQUIRE(workspace != nullptr || workspace_bytes == 0, OFX_EWORKSPACE,
-                "graph_attention_csr_heads: NULL workspace of %zu bytes", workspace_bytes);
+    OFX_DEVICE_ENTRY("graph_attention_csr_heads", opts, workspace, workspace_bytes);
     gat::Shape sh;
     if (const int rc = gat::check_graph_attention_args(
             "graph_attention_csr_heads", idx_dtype, val_dtype, m, k, heads, d, nnz, row_ptr,

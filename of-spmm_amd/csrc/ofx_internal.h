@@ -65,6 +65,15 @@ int read_options(const ofx_spmm_options* in, ofx_spmm_options* out, const char* 
     if (const int ofx_de_ = ::ofx::take_device_error(where)) return ofx_de_; \
   } while (0)
 
+// What opens a launching entry `fn` that takes (workspace, workspace_bytes, opts), in this order:
+// an earlier launch's loud failure, the caller's options, a NULL workspace of some bytes.
+// (Statements, not a block: OFX_READ_OPTIONS declares the copy `opts` then points to.)
+#define OFX_DEVICE_ENTRY(fn, opts, workspace, workspace_bytes)                            \
+  OFX_TAKE_DEVICE_ERROR(fn);                                                              \
+  OFX_READ_OPTIONS(opts, fn);                                                             \
+  OFX_REQUIRE((workspace) != nullptr || (workspace_bytes) == 0, OFX_EWORKSPACE,           \
+              "%s: NULL workspace of %zu bytes", (fn), (size_t)(workspace_bytes))
+
 #define OFX_HIP_CHECK(expr)                                                                 \
   do {                                                                                      \
     hipError_t ofx_e_ = (expr);                                                             \

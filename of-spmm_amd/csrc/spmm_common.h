@@ -11,6 +11,7 @@
 #ifndef OFX_SPMM_COMMON_H_
 #define OFX_SPMM_COMMON_H_
 
+#include <omp.h>  // threads_of; declarations only: a unit that calls it is built with -fopenmp
 #include <stdint.h>
 #include <string.h>
 
@@ -165,6 +166,12 @@ int by_types(int idx_dtype, int val_dtype, F&& f) {
       default: return f((f16*)nullptr, ip);
     }
   });
+}
+
+// The threads of a kCPU entry (host): its num_threads argument, or OpenMP's own count when that is
+// <= 0.
+static inline int threads_of(int num_threads) {
+  return num_threads > 0 ? num_threads : omp_get_max_threads();
 }
 
 // ---- schedule ---------------------------------------------------------------------------

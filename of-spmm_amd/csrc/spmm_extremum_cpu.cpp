@@ -130,8 +130,6 @@ void cpu_row_scale(int nthreads, int64_t n, const I* rp, const T* src, int64_t l
   }
 }
 
-int threads_of(int num_threads) { return num_threads > 0 ? num_threads : omp_get_max_threads(); }
-
 }  // namespace
 }  // namespace ofx
 

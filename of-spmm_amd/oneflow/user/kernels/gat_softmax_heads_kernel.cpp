@@ -1,7 +1,7 @@
 /*
  * gat_softmax_heads_kernel.cpp — kernels of ops "gat_softmax_csr_heads" and
  * "gat_softmax_csr_heads_grad" for DeviceType::kCPU and DeviceType::kHIP (same registration
- * pattern as edge_softmax_heads_kernel.cpp; device work through the C-ABI of include/ofx_spmm.h).
+ * pattern as edge_softmax_kernel.cpp; device work through the C-ABI of include/ofx_spmm.h).
  */
 #include "oneflow/core/framework/framework.h"
 #include "oneflow/user/kernels/csr_kernel_util.h"
