@@ -52,6 +52,11 @@ def _prep(t: torch.Tensor, name: str, matrix: bool = False) -> torch.Tensor:
     return t.contiguous()
 
 
+def _csr_pair(row_ptr: torch.Tensor, col_idx: torch.Tensor):
+    """The two index tensors of a CSR, prepared."""
+    return _prep(row_ptr, "a_csr_row_ptr"), _prep(col_idx, "a_csr_col_idx")
+
+
 def desc(t: torch.Tensor) -> TensorDesc:
     d = TensorDesc()
     d.dtype = dtype_code(t.dtype)
@@ -70,6 +75,39 @@ def current_stream_handle(t: torch.Tensor):
     if t.device.type == "cpu":
         return None
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _refs(*tensors):
+    """Pointers to the descriptors of `tensors`, as the functional entries take them."""
+    return tuple([ctypes.byref(desc(t)) for t in tensors])
+
+
+def _two_phase(fn, stream_of, before, outs, after=(), attrs=(), *, what=None, query_fn=None,
+               size=None, host_tmp=True):
+    """The two-phase call of a functional entry
+        fn(stream, *before, *outs, tmp, tmp_bytes, *after, size_out, *attrs):
+    the tmp size query (no stream, NULL outputs, no tmp), then the run on `stream_of`'s current
+    stream with the op's tmp_buffer on its device (host memory for kCPU kernels; none at all with
+    host_tmp=False).  `attrs`: trailing arguments of an `_attrs` entry; `query_fn`: the entry
+    without them that answers the size query instead; `size`: a size already known (no query is
+    made).  `what` names the call in an error (default: the entry's name).  Returns the size."""
+    what = what or fn.__name__
+    if size is None:
+        got = ctypes.c_size_t(0)
+        null_outs = (None,) * len(outs)
+        if query_fn is None:
+            rc = fn(None, *before, *null_outs, None, 0, *after, ctypes.byref(got), *attrs)
+        else:
+            rc = query_fn(None, *before, *null_outs, None, 0, *after, ctypes.byref(got))
+        check(rc, what)
+        size = got.value
+    tmp = None
+    if size and (host_tmp or stream_of.device.type != "cpu"):
+        tmp = torch.empty(size, dtype=torch.uint8, device=stream_of.device)
+    check(fn(current_stream_handle(stream_of), *before, *outs,
+             tmp.data_ptr() if tmp is not None else None, size if tmp is not None else 0,
+             *after, None, *attrs), what)
+    return size
 
 
 def _placement(_parallel, _placement_nd):
@@ -117,8 +155,7 @@ def spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
       for an N-D one.  The op's physical inference shapes `out`; the kernel's cache takes the row
       range from out's NdSbp (GetTensorSliceView4ParallelId) and the hub schedule from logical N.
     """
-    rp = _prep(a_csr_row_ptr, "a_csr_row_ptr")
-    ci = _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     vals = _prep(a_csr_values, "a_csr_values")
     bb = _prep(b, "b", matrix=True)
     d_rp, d_ci, d_v, d_b = desc(rp), desc(ci), desc(vals), desc(bb)
@@ -131,9 +168,9 @@ def spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     # Out shape and tmp size depend only on the signature (shapes, dtypes, strides, device,
     # attrs, placement): memoised after the first successful call, as OneFlow's eager path keeps
     # its inferred descs per op signature.  The launch below still runs the full inference.
-    key = (tuple(d.shape[i] for d in (d_rp, d_ci, d_v, d_b) for i in range(2)), d_rp.dtype,
-           d_ci.dtype, d_v.dtype, d_b.dtype, d_b.stride[0], d_b.device, int(a_num_rows),
-           int(a_num_cols), hier, axes, pid, logical_n, int(num_threads))
+    key = (rp.shape, ci.shape, vals.shape, bb.shape, d_rp.dtype, d_ci.dtype, d_v.dtype, d_b.dtype,
+           d_b.stride[0], d_b.device, int(a_num_rows), int(a_num_cols), hier, axes, pid, logical_n,
+           int(num_threads))
     memo = _SIG_MEMO.get(key)
     if out is None and memo is not None:
         out = torch.empty(memo[0], dtype=memo[1], device=bb.device)
@@ -142,9 +179,7 @@ def spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
         # empty descriptor (tmp size query) would not return the shape, so ask the infer entry
         # for the logical shape and apply the placement like GetPhysicalShape
         od = TensorDesc()
-        check(LIB.ofx_functional_spmm_csr_infer(ctypes.byref(d_rp), ctypes.byref(d_ci),
-                                                ctypes.byref(d_v), int(a_num_rows), int(a_num_cols),
-                                                ctypes.byref(d_b), ctypes.byref(od)), "spmm_csr")
+        check(LIB.ofx_functional_spmm_csr_infer(*common[:6], ctypes.byref(od)), "spmm_csr")
         rows, n = od.shape[0], od.shape[1]
         for i, (h, a) in enumerate(zip(hier, axes)):
             if a == 0 and h > 1 and rows > 0:
@@ -154,22 +189,12 @@ def spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
                 lo, hi = balanced_range(rows, h, idx % h)
                 rows = hi - lo
         out = torch.empty((rows, n), dtype=_DT_TO_TORCH[od.dtype], device=bb.device)
-    d_o = desc(out)
-    tmp_bytes = ctypes.c_size_t(0)
-    if memo is not None:
-        tmp_bytes.value = memo[2]
-    else:
-        check(LIB.ofx_functional_spmm_csr_global(None, *common, None, None, 0, *tail,
-                                                 ctypes.byref(tmp_bytes)), "spmm_csr")
-    tmp = None
-    if tmp_bytes.value:
-        tmp = torch.empty(tmp_bytes.value, dtype=torch.uint8, device=bb.device)
-    check(LIB.ofx_functional_spmm_csr_global_attrs(
-        current_stream_handle(bb), *common, ctypes.byref(d_o),
-        tmp.data_ptr() if tmp is not None else None, tmp_bytes.value, *tail, None,
-        _attrs_arg(static_csr)), "spmm_csr")
+    tmp_bytes = _two_phase(LIB.ofx_functional_spmm_csr_global_attrs, bb, common, _refs(out), tail,
+                           (_attrs_arg(static_csr),), what="spmm_csr",
+                           query_fn=LIB.ofx_functional_spmm_csr_global,
+                           size=memo[2] if memo is not None else None)
     if memo is None and len(_SIG_MEMO) < 4096:
-        _SIG_MEMO[key] = (tuple(out.shape), out.dtype, tmp_bytes.value)
+        _SIG_MEMO[key] = (tuple(out.shape), out.dtype, tmp_bytes)
     return out
 
 
@@ -193,49 +218,23 @@ def fused_spmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     """Op "fused_spmm_csr": relu?(A @ b + bias?) in one kernel, the same bits as
     spmm_csr -> bias_add -> relu run separately.  `static_csr` as for
     spmm_csr: the plan of an unchanged CSR is kept in the op's kernel state."""
-    rp = _prep(a_csr_row_ptr, "a_csr_row_ptr")
-    ci = _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     vals = _prep(a_csr_values, "a_csr_values")
     bb = _prep(b, "b", matrix=True)
     bs = _prep(bias, "bias") if bias is not None else None
-    d_rp, d_ci, d_v, d_b = desc(rp), desc(ci), desc(vals), desc(bb)
-    d_bias = ctypes.byref(desc(bs)) if bs is not None else None
+    m, k = int(a_num_rows), int(a_num_cols)
+    r_rp, r_ci, r_v, r_b = _refs(rp, ci, vals, bb)
+    r_bias = _refs(bs)[0] if bs is not None else None
     od = TensorDesc()
-    check(LIB.ofx_functional_spmm_csr_infer(ctypes.byref(d_rp), ctypes.byref(d_ci), ctypes.byref(d_v),
-                                            int(a_num_rows), int(a_num_cols), ctypes.byref(d_b),
-                                            ctypes.byref(od)), "fused_spmm_csr")
+    check(LIB.ofx_functional_spmm_csr_infer(r_rp, r_ci, r_v, m, k, r_b, ctypes.byref(od)),
+          "fused_spmm_csr")
     if out is None:
         out = torch.empty((od.shape[0], od.shape[1]), dtype=_DT_TO_TORCH[od.dtype], device=bb.device)
-    d_o = desc(out)
-    args = (ctypes.byref(d_rp), ctypes.byref(d_ci), ctypes.byref(d_v), ctypes.byref(d_b), d_bias,
-            int(a_num_rows), int(a_num_cols), 1 if relu else 0, ctypes.byref(d_o))
-    size = ctypes.c_size_t(0)
-    check(LIB.ofx_functional_fused_spmm_csr(None, *args, None, 0, ctypes.byref(size)), "fused_spmm_csr")
-    tmp = None
-    if size.value and bb.device.type != "cpu":
-        tmp = torch.empty(size.value, dtype=torch.uint8, device=bb.device)
-    check(LIB.ofx_functional_fused_spmm_csr_attrs(current_stream_handle(bb), *args,
-                                                  tmp.data_ptr() if tmp is not None else None,
-                                                  size.value if tmp is not None else 0, None,
-                                                  _attrs_arg(static_csr)),
-          "fused_spmm_csr")
+    _two_phase(LIB.ofx_functional_fused_spmm_csr_attrs, bb,
+               (r_rp, r_ci, r_v, r_b, r_bias, m, k, 1 if relu else 0), _refs(out),
+               attrs=(_attrs_arg(static_csr),), what="fused_spmm_csr",
+               query_fn=LIB.ofx_functional_fused_spmm_csr, host_tmp=False)
     return out
-
-
-def _run_grad_op(fn, stream_of, ins, outs, extra, attrs=()):
-    """Two-phase call of a functional gradient entry: tmp size, then the run.  `attrs`: trailing
-    arguments of an `_attrs` entry (an ofx_spmm_attrs pointer)."""
-    size = ctypes.c_size_t(0)
-    descs_in = [ctypes.byref(desc(t)) for t in ins]
-    descs_out = [ctypes.byref(desc(t)) for t in outs]
-    check(fn(None, *descs_in, *extra, *descs_out, None, 0, ctypes.byref(size), *attrs),
-          fn.__name__)
-    tmp = None
-    if size.value:  # the op's tmp_buffer, on the op's device (host memory for kCPU kernels)
-        tmp = torch.empty(size.value, dtype=torch.uint8, device=stream_of.device)
-    check(fn(current_stream_handle(stream_of), *descs_in, *extra, *descs_out,
-             tmp.data_ptr() if tmp is not None else None, size.value if tmp is not None else 0,
-             None, *attrs), fn.__name__)
 
 
 def sddmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a: torch.Tensor,
@@ -243,7 +242,7 @@ def sddmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a: torch
               static_csr: int = 0) -> torch.Tensor:
     """out[j] = <a[row(j), :], b[col(j), :]> (op "sddmm_csr": the values-gradient of spmm_csr).
     `static_csr` as for spmm_csr: the SDDMM's plan of an unchanged CSR is kept."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     a, b = _prep(a, "a", matrix=True), _prep(b, "b", matrix=True)
     if b.dim() == 2 and b.shape[1] == 0:  # empty inner dimension: every dot product is 0
         out = torch.zeros(ci.numel(), dtype=b.dtype, device=b.device)
@@ -251,8 +250,9 @@ def sddmm_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a: torch
         out = torch.empty(ci.numel(), dtype=b.dtype, device=b.device)
     if b.dim() == 2 and b.shape[1] == 0 and a.dim() == 2 and a.shape[1] == 0:
         return out
-    _run_grad_op(LIB.ofx_functional_sddmm_csr_attrs, b, [rp, ci, a, b], [out],
-                 [int(a_num_rows), int(a_num_cols)], (_attrs_arg(static_csr),))
+    _two_phase(LIB.ofx_functional_sddmm_csr_attrs, b,
+               _refs(rp, ci, a, b) + (int(a_num_rows), int(a_num_cols)), _refs(out),
+               attrs=(_attrs_arg(static_csr),))
     return out
 
 
@@ -263,7 +263,7 @@ def spmm_csr_gathered(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     """Op "spmm_csr_gathered": A @ b with nonzero j's value a_csr_values[values_perm[j]] (the
     d(b) gradient of spmm_csr with learnable values: A^T's structure, A's values, A^T's perm).
     `static_csr` as for spmm_csr (the autograd's cached A^T passes its entry's value)."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     vals, perm = _prep(a_csr_values, "a_csr_values"), _prep(values_perm, "values_perm")
     bb = _prep(b, "b", matrix=True)
     if out is None:
@@ -271,8 +271,9 @@ def spmm_csr_gathered(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
                           device=bb.device)
     if out.numel() == 0:
         return out
-    _run_grad_op(LIB.ofx_functional_spmm_csr_gathered_attrs, bb, [rp, ci, vals, perm, bb], [out],
-                 [int(a_num_rows), int(a_num_cols)], (_attrs_arg(static_csr),))
+    _two_phase(LIB.ofx_functional_spmm_csr_gathered_attrs, bb,
+               _refs(rp, ci, vals, perm, bb) + (int(a_num_rows), int(a_num_cols)), _refs(out),
+               attrs=(_attrs_arg(static_csr),))
     return out
 
 
@@ -299,8 +300,7 @@ def spmm_csr_reduce(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     out_split_axis[, logical_n])` as for spmm_csr: this rank's rows (axis 0) or columns (axis 1)
     of out and arg; arg keeps global nonzero indices under a row split."""
     code = reduce_code(reduce)
-    rp = _prep(a_csr_row_ptr, "a_csr_row_ptr")
-    ci = _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     vals = _prep(a_csr_values, "a_csr_values")
     bb = _prep(b, "b", matrix=True)
     pid, pnum, axis, logical_n = 0, 1, -1, -1
@@ -316,22 +316,9 @@ def spmm_csr_reduce(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
         out = torch.empty((rows, n), dtype=bb.dtype, device=bb.device)
     has_arg = code in (_lib.REDUCE_MAX, _lib.REDUCE_MIN)
     arg = torch.empty((rows if has_arg else 0, n), dtype=rp.dtype, device=bb.device)
-    d_in = [desc(t) for t in (rp, ci, vals)]
-    d_b, d_o, d_a = desc(bb), desc(out), desc(arg)
-    head = (*(ctypes.byref(d) for d in d_in), int(a_num_rows), int(a_num_cols), ctypes.byref(d_b),
-            code)
-    tail = (pid, pnum, axis, logical_n, int(num_threads))
-    size = ctypes.c_size_t(0)
-    check(LIB.ofx_functional_spmm_csr_reduce(None, *head, None, None, None, 0, *tail,
-                                             ctypes.byref(size)), "spmm_csr_reduce")
-    tmp = None
-    if size.value:
-        tmp = torch.empty(size.value, dtype=torch.uint8, device=bb.device)
-    check(LIB.ofx_functional_spmm_csr_reduce(current_stream_handle(bb), *head, ctypes.byref(d_o),
-                                             ctypes.byref(d_a),
-                                             tmp.data_ptr() if tmp is not None else None,
-                                             size.value if tmp is not None else 0, *tail, None),
-          "spmm_csr_reduce")
+    head = (*_refs(rp, ci, vals), int(a_num_rows), int(a_num_cols), *_refs(bb), code)
+    _two_phase(LIB.ofx_functional_spmm_csr_reduce, bb, head, _refs(out, arg),
+               (pid, pnum, axis, logical_n, int(num_threads)), what="spmm_csr_reduce")
     return out, arg
 
 
@@ -346,8 +333,8 @@ def spmm_csr_reduce_grad_b(at_row_ptr: torch.Tensor, at_col_idx: torch.Tensor,
     vals = _prep(a_csr_values, "a_csr_values")
     arg, dy = _prep(arg, "arg", matrix=True), _prep(dy, "dy", matrix=True)
     out = torch.empty((int(a_num_cols), dy.shape[1]), dtype=dy.dtype, device=dy.device)
-    _run_grad_op(LIB.ofx_functional_spmm_csr_reduce_grad_b, dy, [rp, ci, perm, vals, arg, dy],
-                 [out], [int(a_num_rows), int(a_num_cols)])
+    _two_phase(LIB.ofx_functional_spmm_csr_reduce_grad_b, dy,
+               _refs(rp, ci, perm, vals, arg, dy) + (int(a_num_rows), int(a_num_cols)), _refs(out))
     return out
 
 
@@ -356,37 +343,46 @@ def spmm_csr_reduce_grad_values(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torc
                                 a_num_rows: int, a_num_cols: int) -> torch.Tensor:
     """Op "spmm_csr_reduce_grad_values": d(values) [nnz] of reduce = max / min, the SDDMM of dy
     and b restricted to the columns each nonzero won (ofx_sddmm_csr_select)."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     arg, dy = _prep(arg, "arg", matrix=True), _prep(dy, "dy", matrix=True)
     bb = _prep(b, "b", matrix=True)
     if bb.dim() == 2 and bb.shape[1] == 0:  # empty inner dimension: every dot product is +0
         return torch.zeros(ci.numel(), dtype=bb.dtype, device=bb.device)
     out = torch.empty(ci.numel(), dtype=bb.dtype, device=bb.device)
-    _run_grad_op(LIB.ofx_functional_spmm_csr_reduce_grad_values, bb, [rp, ci, arg, dy, bb], [out],
-                 [int(a_num_rows), int(a_num_cols)])
+    _two_phase(LIB.ofx_functional_spmm_csr_reduce_grad_values, bb,
+               _refs(rp, ci, arg, dy, bb) + (int(a_num_rows), int(a_num_cols)), _refs(out))
     return out
 
 
-def _check_inputs(op, rp, ci, named, rank, ref, per_nonzero):
-    """The shape and dtype checks the edge-softmax and multi-head ops share, ahead of the op
+def _check_inputs(op, rp, ci, named, rank, ref, per_nonzero, gat=False):
+    """The shape and dtype checks the edge-softmax, multi-head and GAT ops share, ahead of the op
     layer's own (its messages name the C-ABI).  `named`: [(name, tensor)], each of `rank`
-    dimensions; `ref`: the name of the one whose dtype the others must have; per_nonzero: each
-    has nnz elements (rank 1) or nnz rows of one number of heads (rank 2)."""
+    dimensions; `ref`: the name of the one whose dtype the others must have; per_nonzero: True
+    (every tensor), False (none) or the names of those that have nnz elements (rank 1) or nnz
+    rows (rank 2) of `ref`'s number of heads.  gat: the GAT ops' form, every tensor [rows, heads]
+    with `ref`'s heads on `ref`'s device, `ref` with a_num_rows rows."""
     ref_t = dict(named)[ref]
     for name, t in named:
-        layout = " [nnz, heads]" if per_nonzero and rank == 2 else ""
-        if name == ref and not per_nonzero:
+        nnz_rows = per_nonzero if isinstance(per_nonzero, bool) else name in per_nonzero
+        layout = " [rows, heads]" if gat else " [nnz, heads]" if nnz_rows and rank == 2 else ""
+        if name == ref and not per_nonzero and not gat:
             layout = " [K, heads * D]"
         if t.dim() != rank:
             raise RuntimeError(f"{op}: {name} should be {rank}-D{layout}, got shape "
                                f"{tuple(t.shape)}")
-        if per_nonzero and t.shape[0] != ci.numel():
+        if nnz_rows and t.shape[0] != ci.numel():
             raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} "
                                f"{'elements' if rank == 1 else 'rows'} (as a_csr_col_idx), got "
                                f"{t.shape[0]}")
-        if per_nonzero and rank == 2 and t.shape[1] != ref_t.shape[1]:
+        if (nnz_rows or gat) and rank == 2 and t.shape[1] != ref_t.shape[1]:
             raise RuntimeError(f"{op}: {name} should have the number of heads of {ref} "
                                f"({t.shape[1]} vs {ref_t.shape[1]})")
+        if gat and t.device != ref_t.device:
+            raise RuntimeError(f"{op}: expected all tensors on the same device, got {name} on "
+                               f"{t.device} and {ref} on {ref_t.device}")
+    if gat and ref_t.shape[0] != rp.numel() - 1:
+        raise RuntimeError(f"{op}: {ref} should have a_num_rows = {rp.numel() - 1} rows, got "
+                           f"{ref_t.shape[0]}")
     if rp.dtype != ci.dtype:
         raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
                         f"({ci.dtype} vs {rp.dtype})")
@@ -395,7 +391,7 @@ def _check_inputs(op, rp, ci, named, rank, ref, per_nonzero):
         raise TypeError(f"{op} supports float, double, float16, bfloat16; got {ref_t.dtype}")
     for name, t in named:
         if t.dtype != ref_t.dtype:
-            detail = "" if per_nonzero else f" ({t.dtype} vs {ref_t.dtype})"
+            detail = f" ({t.dtype} vs {ref_t.dtype})" if gat or not per_nonzero else ""
             raise TypeError(f"{op}: {name} datatype should be equal to {ref}{detail}")
 
 
@@ -404,12 +400,12 @@ def edge_softmax_csr(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, e
     """Op "edge_softmax_csr": out[j] = softmax of the scores e over the nonzeros of j's row (DGL's
     edge_softmax, PyG's softmax(src, ptr=row_ptr)); contract in include/ofx_spmm.h.  One HIP
     launch on GPU tensors, the kCPU kernel on CPU tensors: the same bits."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     e = _prep(e, "e")
     _check_inputs("edge_softmax_csr", rp, ci, [("e", e)], 1, "e", True)
     if out is None:
         out = torch.empty_like(e)
-    _run_grad_op(LIB.ofx_functional_edge_softmax_csr, e, [rp, ci, e], [out], [])
+    _two_phase(LIB.ofx_functional_edge_softmax_csr, e, _refs(rp, ci, e), _refs(out))
     return out
 
 
@@ -417,20 +413,25 @@ def edge_softmax_csr_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tens
                           y: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     """Op "edge_softmax_csr_grad": dx[j] = y[j] * (dy[j] - sum over j's row of y * dy), from the
     forward's stored y."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     y, dy = _prep(y, "y"), _prep(dy, "dy")
     _check_inputs("edge_softmax_csr_grad", rp, ci, [("y", y), ("dy", dy)], 1, "y", True)
     dx = torch.empty_like(y)
-    _run_grad_op(LIB.ofx_functional_edge_softmax_csr_grad, y, [rp, ci, y, dy], [dx], [])
+    _two_phase(LIB.ofx_functional_edge_softmax_csr_grad, y, _refs(rp, ci, y, dy), _refs(dx))
     return dx
 
 
 def _check_out(op, out, shape, like, contiguous=False):
+    """The op's output: a new `shape` tensor of `like`'s dtype and device, or the caller's `out`
+    once it is found to be one."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=like.dtype, device=like.device)
     if contiguous and not out.is_contiguous():
         raise RuntimeError(f"{op}: out must be contiguous")
     if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device:
         raise RuntimeError(f"{op}: out must be a {tuple(shape)} tensor of dtype {like.dtype} on "
                            f"{like.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    return out
 
 
 def spmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
@@ -440,7 +441,7 @@ def spmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     a_csr_values[j, h] * b[a_csr_col_idx[j], h*D + c]; a_csr_values is [nnz, H], b is [K, H*D] with
     head h in columns [h*D, (h+1)*D).  One launch for all heads; every head's slice has the bits
     of spmm_csr on that slice (contract in include/ofx_spmm.h)."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     vals = _prep(a_csr_values, "a_csr_values")
     bb = _prep(b, "b", matrix=True)
     _check_inputs("spmm_csr_heads", rp, ci, [("a_csr_values", vals), ("b", bb)], 2, "b", False)
@@ -450,15 +451,11 @@ def spmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     if vals.shape[1] < 1 or bb.shape[1] % vals.shape[1] != 0:
         raise RuntimeError(f"spmm_csr_heads: b's columns ({bb.shape[1]}) should be a multiple of "
                            f"the number of heads ({vals.shape[1]})")
-    shape = (int(a_num_rows), bb.shape[1])
-    if out is None:
-        out = torch.empty(shape, dtype=bb.dtype, device=bb.device)
-    else:
-        _check_out("spmm_csr_heads", out, shape, bb)
+    out = _check_out("spmm_csr_heads", out, (int(a_num_rows), bb.shape[1]), bb)
     if out.numel() == 0:
         return out
-    _run_grad_op(LIB.ofx_functional_spmm_csr_heads, bb, [rp, ci, vals, bb], [out],
-                 [int(a_num_rows), int(a_num_cols)])
+    _two_phase(LIB.ofx_functional_spmm_csr_heads, bb,
+               _refs(rp, ci, vals, bb) + (int(a_num_rows), int(a_num_cols)), _refs(out))
     return out
 
 
@@ -469,7 +466,7 @@ def sddmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a:
     b[col(j), h*D:(h+1)*D]> for a [M, H*D], b [K, H*D], H = num_heads: the scores of multi-head
     graph attention and the values-gradient of spmm_csr_heads; every head has the bits of
     sddmm_csr on its slice."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     a, bb = _prep(a, "a", matrix=True), _prep(b, "b", matrix=True)
     _check_inputs("sddmm_csr_heads", rp, ci, [("a", a), ("b", bb)], 2, "b", False)
     heads = int(num_heads)
@@ -479,16 +476,12 @@ def sddmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a:
     if a.shape[1] != bb.shape[1]:
         raise RuntimeError("sddmm_csr_heads: a and b should have the same number of columns "
                            f"({a.shape[1]} vs {bb.shape[1]})")
-    shape = (ci.numel(), heads)
-    if out is None:
-        out = torch.empty(shape, dtype=bb.dtype, device=bb.device)
-    else:
-        _check_out("sddmm_csr_heads", out, shape, bb, contiguous=True)
+    out = _check_out("sddmm_csr_heads", out, (ci.numel(), heads), bb, contiguous=True)
     if out.numel() == 0:
         return out
     if bb.shape[1] == 0:  # empty inner dimension: every dot product is +0
         return out.zero_()
-    _run_grad_op(LIB.ofx_functional_sddmm_csr_heads, bb, [rp, ci, a, bb], [out], [heads])
+    _two_phase(LIB.ofx_functional_sddmm_csr_heads, bb, _refs(rp, ci, a, bb) + (heads,), _refs(out))
     return out
 
 
@@ -503,7 +496,7 @@ def graph_attention_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.
     with exactly the bits of that composition (contract in include/ofx_spmm.h).  `out`: a [M, H*D]
     tensor; `attn_out`: a contiguous [nnz, H] tensor; both written directly."""
     op = "graph_attention_csr_heads"
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     q = _prep(q, "q", matrix=True)
     kk, vv = _prep(k, "k", matrix=True), _prep(v, "v", matrix=True)
     _check_inputs(op, rp, ci, [("q", q), ("v", vv), ("k", kk)], 2, "k", False)
@@ -520,18 +513,12 @@ def graph_attention_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.
     m = rp.numel() - 1
     if q.shape[0] != m:
         raise RuntimeError(f"{op}: q should have a_num_rows = {m} rows, got {q.shape[0]}")
-    if out is None:
-        out = torch.empty((m, kk.shape[1]), dtype=kk.dtype, device=kk.device)
-    else:
-        _check_out(op, out, (m, kk.shape[1]), kk)
-    if attn_out is None:
-        attn_out = torch.empty((ci.numel(), heads), dtype=kk.dtype, device=kk.device)
-    else:
-        _check_out(op, attn_out, (ci.numel(), heads), kk, contiguous=True)
+    out = _check_out(op, out, (m, kk.shape[1]), kk)
+    attn_out = _check_out(op, attn_out, (ci.numel(), heads), kk, contiguous=True)
     if out.numel() == 0:
         return out, attn_out
-    _run_grad_op(LIB.ofx_functional_graph_attention_csr_heads, kk, [rp, ci, q, kk, vv],
-                 [out, attn_out], [heads])
+    _two_phase(LIB.ofx_functional_graph_attention_csr_heads, kk,
+               _refs(rp, ci, q, kk, vv) + (heads,), _refs(out, attn_out))
     return out, attn_out
 
 
@@ -541,16 +528,13 @@ def edge_softmax_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Ten
     j's row, for e [nnz, H] (sddmm_csr_heads's output; a non-contiguous e is copied first).  One
     launch for all heads; every head has the bits of edge_softmax_csr on its column (contract in
     include/ofx_spmm.h).  `out`: a contiguous [nnz, H] tensor, written directly."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     e = _prep(e, "e")
     _check_inputs("edge_softmax_csr_heads", rp, ci, [("e", e)], 2, "e", True)
-    if out is None:
-        out = torch.empty_like(e)
-    else:
-        _check_out("edge_softmax_csr_heads", out, e.shape, e, contiguous=True)
+    out = _check_out("edge_softmax_csr_heads", out, e.shape, e, contiguous=True)
     if out.numel() == 0:
         return out
-    _run_grad_op(LIB.ofx_functional_edge_softmax_csr_heads, e, [rp, ci, e], [out], [])
+    _two_phase(LIB.ofx_functional_edge_softmax_csr_heads, e, _refs(rp, ci, e), _refs(out))
     return out
 
 
@@ -558,46 +542,14 @@ def edge_softmax_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torc
                                 y: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     """Op "edge_softmax_csr_heads_grad": dx[j, h] = y[j, h] * (dy[j, h] - sum over j's row of
     y[:, h] * dy[:, h]) for y, dy [nnz, H], from the forward's stored y; one launch."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     y, dy = _prep(y, "y"), _prep(dy, "dy")
     _check_inputs("edge_softmax_csr_heads_grad", rp, ci, [("y", y), ("dy", dy)], 2, "y", True)
     dx = torch.empty_like(y)
     if dx.numel() == 0:
         return dx
-    _run_grad_op(LIB.ofx_functional_edge_softmax_csr_heads_grad, y, [rp, ci, y, dy], [dx], [])
+    _two_phase(LIB.ofx_functional_edge_softmax_csr_heads_grad, y, _refs(rp, ci, y, dy), _refs(dx))
     return dx
-
-
-def _check_gat_inputs(op, rp, ci, s_row, s_col, per_nonzero=()):
-    """The shape and dtype checks of the GAT ops: s_row [M, H], s_col [K, H] and the per-nonzero
-    tensors [nnz, H] of one dtype (s_row's) on one device."""
-    named = [("s_row", s_row), ("s_col", s_col), *per_nonzero]
-    for name, t in named:
-        if t.dim() != 2:
-            raise RuntimeError(f"{op}: {name} should be 2-D [rows, heads], got shape "
-                               f"{tuple(t.shape)}")
-        if t.shape[1] != s_row.shape[1]:
-            raise RuntimeError(f"{op}: {name} should have the number of heads of s_row "
-                               f"({t.shape[1]} vs {s_row.shape[1]})")
-        if t.dtype != s_row.dtype:
-            raise TypeError(f"{op}: {name} datatype should be equal to s_row "
-                            f"({t.dtype} vs {s_row.dtype})")
-        if t.device != s_row.device:
-            raise RuntimeError(f"{op}: expected all tensors on the same device, got {name} on "
-                               f"{t.device} and s_row on {s_row.device}")
-    if s_row.shape[0] != rp.numel() - 1:
-        raise RuntimeError(f"{op}: s_row should have a_num_rows = {rp.numel() - 1} rows, got "
-                           f"{s_row.shape[0]}")
-    for name, t in per_nonzero:
-        if t.shape[0] != ci.numel():
-            raise RuntimeError(f"{op}: {name} should have nnz = {ci.numel()} rows (as "
-                               f"a_csr_col_idx), got {t.shape[0]}")
-    if rp.dtype != ci.dtype:
-        raise TypeError(f"{op}: a_csr_col_idx should have the dtype of a_csr_row_ptr "
-                        f"({ci.dtype} vs {rp.dtype})")
-    dtype_code(rp.dtype)
-    if s_row.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
-        raise TypeError(f"{op} supports float, double, float16, bfloat16; got {s_row.dtype}")
 
 
 def gat_softmax_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
@@ -609,18 +561,14 @@ def gat_softmax_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tens
     (contract in include/ofx_spmm.h).  Non-contiguous inputs are copied first.  `out`: a contiguous
     [nnz, H] tensor, written directly.  negative_slope must be finite and > 0."""
     op = "gat_softmax_csr_heads"
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     s_row, s_col = _prep(s_row, "s_row"), _prep(s_col, "s_col")
-    _check_gat_inputs(op, rp, ci, s_row, s_col)
-    shape = (ci.numel(), s_row.shape[1])
-    if out is None:
-        out = torch.empty(shape, dtype=s_row.dtype, device=s_row.device)
-    else:
-        _check_out(op, out, shape, s_row, contiguous=True)
+    _check_inputs(op, rp, ci, [("s_row", s_row), ("s_col", s_col)], 2, "s_row", (), gat=True)
+    out = _check_out(op, out, (ci.numel(), s_row.shape[1]), s_row, contiguous=True)
     if out.numel() == 0:
         return out
-    _run_grad_op(LIB.ofx_functional_gat_softmax_csr_heads, s_row, [rp, ci, s_row, s_col], [out],
-                 [float(negative_slope)])
+    _two_phase(LIB.ofx_functional_gat_softmax_csr_heads, s_row,
+               _refs(rp, ci, s_row, s_col) + (float(negative_slope),), _refs(out))
     return out
 
 
@@ -632,16 +580,17 @@ def gat_softmax_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch
     derivative at the recomputed sum, d_row[r] = the sum of ds over r's nonzeros in the softmax's
     order (+0 for an empty row)."""
     op = "gat_softmax_csr_heads_grad"
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     s_row, s_col = _prep(s_row, "s_row"), _prep(s_col, "s_col")
     y, dy = _prep(y, "y"), _prep(dy, "dy")
-    _check_gat_inputs(op, rp, ci, s_row, s_col, [("y", y), ("dy", dy)])
+    _check_inputs(op, rp, ci, [("s_row", s_row), ("s_col", s_col), ("y", y), ("dy", dy)], 2,
+                  "s_row", ("y", "dy"), gat=True)
     ds = torch.empty_like(y)
     if ds.numel() == 0:  # nothing is written for nnz == 0 or H == 0: every row is empty
         return ds, torch.zeros_like(s_row)
     d_row = torch.empty_like(s_row)
-    _run_grad_op(LIB.ofx_functional_gat_softmax_csr_heads_grad, s_row,
-                 [rp, ci, s_row, s_col, y, dy], [ds, d_row], [float(negative_slope)])
+    _two_phase(LIB.ofx_functional_gat_softmax_csr_heads_grad, s_row,
+               _refs(rp, ci, s_row, s_col, y, dy) + (float(negative_slope),), _refs(ds, d_row))
     return ds, d_row
 
 
@@ -668,13 +617,13 @@ def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
 def csr_transpose(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a_num_rows: int,
                   a_num_cols: int):
     """Structure of A^T (op "csr_transpose"): (row_ptr [K+1], col_idx [nnz], perm [nnz])."""
-    rp, ci = _prep(a_csr_row_ptr, "a_csr_row_ptr"), _prep(a_csr_col_idx, "a_csr_col_idx")
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
     it, dev = rp.dtype, rp.device
     rp_t = torch.empty(int(a_num_cols) + 1, dtype=it, device=dev)
     ci_t = torch.empty(ci.numel(), dtype=it, device=dev)
     perm = torch.empty(ci.numel(), dtype=it, device=dev)
-    _run_grad_op(LIB.ofx_functional_csr_transpose, rp, [rp, ci], [rp_t, ci_t, perm],
-                 [int(a_num_rows), int(a_num_cols)])
+    _two_phase(LIB.ofx_functional_csr_transpose, rp,
+               _refs(rp, ci) + (int(a_num_rows), int(a_num_cols)), _refs(rp_t, ci_t, perm))
     return rp_t, ci_t, perm
 
 

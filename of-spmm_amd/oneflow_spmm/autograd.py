@@ -43,6 +43,32 @@ def gather_values(perm: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _gather_rows(perm: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+    """The rows values[perm] of a contiguous [nnz, H] tensor (ofx_gather_rows on the device, a
+    torch index on the host: plumbing, not hot path)."""
+    if values.device.type == "cpu" or values.numel() == 0:
+        return values.index_select(0, perm.long())
+    out = torch.empty_like(values)
+    row_bytes = values.shape[1] * values.element_size()
+    check(LIB.ofx_gather_rows(current_stream_handle(values), dtype_code(perm.dtype),
+                              values.shape[0], row_bytes, perm.data_ptr(), values.data_ptr(),
+                              row_bytes, out.data_ptr(), row_bytes), "gather_rows")
+    return out
+
+
+def _recording(op: str, out, *tensors) -> bool:
+    """Whether gradients are being recorded for any of `tensors` (None: an absent input), the
+    dispatch decision of every public op; `out=` is refused then."""
+    if not torch.is_grad_enabled():
+        return False
+    for t in tensors:
+        if t is not None and t.requires_grad:
+            if out is not None:
+                raise RuntimeError(f"{op}: out= is not supported when gradients are required")
+            return True
+    return False
+
+
 def _heads_2d(t: torch.Tensor, name: str) -> torch.Tensor:
     """A [rows, H, D] tensor made contiguous and viewed as [rows, H*D]."""
     if t.dim() != 3:
@@ -65,10 +91,10 @@ def sddmm(row_ptr: torch.Tensor, col_idx: torch.Tensor, a: torch.Tensor, b: torc
             raise RuntimeError("sddmm: a [M, H, D] needs b [K, H, D] with the same heads and D, "
                                f"got {tuple(a.shape)} and {tuple(b.shape)}")
         heads = a.shape[1]
-        if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        if _recording("sddmm", None, a, b):
             return SddmmCsrHeadsFunction.apply(row_ptr, col_idx, a, b)
         return _C.sddmm_csr_heads(row_ptr, col_idx, _heads_2d(a, "a"), _heads_2d(b, "b"), heads)
-    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+    if _recording("sddmm", None, a, b):
         return SddmmCsrFunction.apply(row_ptr, col_idx, a, b, int(static_csr))
     return _C.sddmm_csr(row_ptr, col_idx, a, b, row_ptr.numel() - 1, b.shape[0],
                         static_csr=static_csr)
@@ -84,6 +110,11 @@ class _TransposeCache:
         self.value_entries: OrderedDict = OrderedDict()
         self.seen: OrderedDict = OrderedDict()  # value keys met once (not yet worth a copy)
 
+    def _insert(self, d: OrderedDict, key, item) -> list:
+        """d[key] = item, bounded: the oldest entries beyond `capacity` leave and are returned."""
+        d[key] = item
+        return [d.popitem(last=False)[1] for _ in range(len(d) - self.capacity)]
+
     def get(self, row_ptr, col_idx, k):
         key = (row_ptr.data_ptr(), col_idx.data_ptr(), row_ptr._version, col_idx._version,
                row_ptr.numel(), col_idx.numel(), k, str(row_ptr.device))
@@ -97,9 +128,7 @@ class _TransposeCache:
         # other entry ever had (a later transpose at recycled addresses gets a new one)
         self._next_id += 1
         self.static_ids[id(t[0])] = self._next_id
-        self.entries[key] = (row_ptr, col_idx, t)
-        while len(self.entries) > self.capacity:
-            _, (_, _, old) = self.entries.popitem(last=False)
+        for _, _, old in self._insert(self.entries, key, (row_ptr, col_idx, t)):
             self.static_ids.pop(id(old[0]), None)
         return t
 
@@ -107,47 +136,67 @@ class _TransposeCache:
         """The static_csr value of a cached A^T (0 if it is not cached any more)."""
         return self.static_ids.get(id(rp_t), 0)
 
+    @staticmethod
+    def _values_key(row_ptr, col_idx, k, values):
+        return (row_ptr.data_ptr(), col_idx.data_ptr(), row_ptr._version, col_idx._version, k,
+                values.data_ptr(), values._version, values.dtype, tuple(values.shape),
+                str(values.device))
 
-    def values_t(self, row_ptr, col_idx, values, k):
-        """A^T's values = values[perm].  Edge weights of a GNN (e.g. GCN normalisation) are
-        usually constant across steps, so the gathered copy is kept too, keyed on the values
-        tensor's storage and version (an in-place update invalidates it)."""
+    def transposed_values(self, row_ptr, col_idx, values, k, first_sight):
+        """(row_ptr_T, col_idx_T, perm, A^T's values = values[perm]) for values [nnz] or a
+        contiguous [nnz, H].  Edge weights of a GNN (GCN normalisation, constant attention
+        weights) are usually constant across steps, so values met again unchanged keep their
+        gathered copy, keyed on the values tensor's storage and version (an in-place update
+        invalidates it); values new every step (learnable weights, upstream gradients) are not
+        worth one.  `first_sight` is what values met for the first time get:
+          "fused":  no copy at all, None is returned (the caller reads them through perm);
+          "gather": a copy that is not kept;
+          "cache":  a copy kept at once.
+        A copy gathered while the current stream is capturing is used but never stored, nor is
+        its sighting: it lives in the graph's pool."""
         rp_t, ci_t, perm = self.get(row_ptr, col_idx, k)
-        key = (row_ptr.data_ptr(), col_idx.data_ptr(), row_ptr._version, col_idx._version, k,
-               values.data_ptr(), values._version, values.dtype, values.numel(), str(values.device))
+        key = self._values_key(row_ptr, col_idx, k, values)
         hit = self.value_entries.get(key)
         if hit is not None:
             self.value_entries.move_to_end(key)
-            return rp_t, ci_t, hit[1]
-        vals_t = gather_values(perm, values)
-        self.value_entries[key] = (values, vals_t)  # holds values: its storage cannot be reused
-        while len(self.value_entries) > self.capacity:
-            self.value_entries.popitem(last=False)
-        return rp_t, ci_t, vals_t
-
+            return rp_t, ci_t, perm, hit[1]
+        again = first_sight == "cache" or key in self.seen
+        if first_sight == "fused" and not again:
+            self._insert(self.seen, key, values)  # holds values: its storage cannot be reused
+            return rp_t, ci_t, perm, None
+        vals_t = gather_values(perm, values) if values.dim() == 1 else _gather_rows(perm, values)
+        if not (values.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            if again:
+                self._insert(self.value_entries, key, (values, vals_t))  # holds values, as seen
+            else:
+                self._insert(self.seen, key, values)
+        return rp_t, ci_t, perm, vals_t
 
     def grad_b(self, row_ptr, col_idx, values, m, k, d_out):
-        """d(b) = A^T @ d(out).  Values met for the first time (e.g. learnable edge weights,
-        new every step) are read through the transpose's perm inside the SpMM
-        (ofx_spmm_csr_gathered: no values[perm] copy written); values met again unchanged
-        (constant GCN weights) are gathered once and cached, then the plain SpMM runs on them.
-        Every route gives the same bits."""
-        rp_t, ci_t, perm = self.get(row_ptr, col_idx, k)
-        key = (row_ptr.data_ptr(), col_idx.data_ptr(), row_ptr._version, col_idx._version, k,
-               values.data_ptr(), values._version, values.dtype, values.numel(), str(values.device))
-        if key not in self.value_entries and values.device.type == "cuda" and key not in self.seen:
-            self.seen[key] = values  # holds values: its storage cannot be reused under the key
-            while len(self.seen) > self.capacity:
-                self.seen.popitem(last=False)
-            # the cached A^T's structure is static while its entry lives: its plan is kept too
+        """d(b) = A^T @ d(out) for values [nnz].  On the GPU, values met for the first time are
+        read through the transpose's perm inside the SpMM (ofx_spmm_csr_gathered: no
+        values[perm] copy written); values met again are gathered once and cached, then the
+        plain SpMM runs on them.  On the CPU the copy is cached at once.  Every route gives the
+        same bits.  The cached A^T's structure is static while its entry lives: its plan is kept
+        across steps (static_csr, a value unique to the entry)."""
+        rp_t, ci_t, perm, vals_t = self.transposed_values(
+            row_ptr, col_idx, values, k, "fused" if values.device.type == "cuda" else "cache")
+        if vals_t is None:
             return _C.spmm_csr_gathered(rp_t, ci_t, values, perm, k, m, d_out,
                                         static_csr=self.static_id(rp_t))
-        _, _, vals_t = self.values_t(row_ptr, col_idx, values, k)
-        # the cached A^T: its plan is kept across steps (static_csr, a value unique to the entry)
         return spmm_csr(rp_t, ci_t, vals_t, k, m, d_out, static_csr=self.static_id(rp_t))
+
+    def grad_b_heads(self, row_ptr, col_idx, values, m, k, x):
+        """A(values)^T @ x per head for values [nnz, H]: op "spmm_csr_heads" on the cached
+        transpose with the rows values[perm], gathered every time until the values are met again
+        unchanged."""
+        rp_t, ci_t, _, vals_t = self.transposed_values(row_ptr, col_idx, values.contiguous(), k,
+                                                       "gather")
+        return _C.spmm_csr_heads(rp_t, ci_t, vals_t, k, m, x)
 
 
 TRANSPOSE_CACHE = _TransposeCache()
+_heads_grad_b = TRANSPOSE_CACHE.grad_b_heads  # the former name, for callers that still use it
 
 
 class SpmmCsrFunction(torch.autograd.Function):
@@ -195,43 +244,6 @@ class SddmmCsrFunction(torch.autograd.Function):
         return None, None, d_a, d_b, None
 
 
-def _heads_grad_b(row_ptr, col_idx, values, m, k, x):
-    """A(values)^T @ x per head: op "spmm_csr_heads" on the cached transpose, with A^T's values =
-    the rows values[perm] of H (ofx_gather_rows on the device, a torch index on the host:
-    plumbing, not hot path)."""
-    rp_t, ci_t, perm = TRANSPOSE_CACHE.get(row_ptr, col_idx, k)
-    values = values.contiguous()
-    # the policy of _TransposeCache.grad_b: values met again unchanged (constant attention
-    # weights) keep their gathered copy; values new every step are gathered every step
-    cache = TRANSPOSE_CACHE
-    key = (row_ptr.data_ptr(), col_idx.data_ptr(), row_ptr._version, col_idx._version, k,
-           values.data_ptr(), values._version, values.dtype, tuple(values.shape),
-           str(values.device))
-    hit = cache.value_entries.get(key)
-    if hit is not None:
-        cache.value_entries.move_to_end(key)
-        return _C.spmm_csr_heads(rp_t, ci_t, hit[1], k, m, x)
-    if values.device.type == "cpu" or values.numel() == 0:
-        vals_t = values.index_select(0, perm.long())
-    else:
-        vals_t = torch.empty_like(values)
-        row_bytes = values.shape[1] * values.element_size()
-        check(LIB.ofx_gather_rows(current_stream_handle(values), dtype_code(perm.dtype),
-                                  values.shape[0], row_bytes, perm.data_ptr(), values.data_ptr(),
-                                  row_bytes, vals_t.data_ptr(), row_bytes), "gather_rows")
-    if values.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-        pass  # a copy made inside a graph capture lives in the graph's pool: never cached
-    elif key in cache.seen:
-        cache.value_entries[key] = (values, vals_t)  # holds values: its storage cannot be reused
-        while len(cache.value_entries) > cache.capacity:
-            cache.value_entries.popitem(last=False)
-    else:
-        cache.seen[key] = values
-        while len(cache.seen) > cache.capacity:
-            cache.seen.popitem(last=False)
-    return _C.spmm_csr_heads(rp_t, ci_t, vals_t, k, m, x)
-
-
 class SpmmCsrHeadsFunction(torch.autograd.Function):
     """out [M, H, D] = per head h, A(values[:, h]) @ b[:, h, :], differentiable in values [nnz, H]
     and b [K, H, D]: d(values) is the multi-head SDDMM of d(out) and b, d(b) the multi-head SpMM
@@ -255,7 +267,7 @@ class SpmmCsrHeadsFunction(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             d_values = _C.sddmm_csr_heads(row_ptr, col_idx, g, b2, ctx.heads)
         if ctx.needs_input_grad[5]:
-            d_b = _heads_grad_b(row_ptr, col_idx, values.detach().contiguous(), ctx.m, ctx.k, g)
+            d_b = TRANSPOSE_CACHE.grad_b_heads(row_ptr, col_idx, values.detach(), ctx.m, ctx.k, g)
             d_b = d_b.view(ctx.k, ctx.heads, ctx.d)
         return None, None, d_values, None, None, d_b
 
@@ -282,7 +294,8 @@ class SddmmCsrHeadsFunction(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             d_a = _C.spmm_csr_heads(row_ptr, col_idx, g, m, k, b2).view(m, ctx.heads, ctx.d)
         if ctx.needs_input_grad[3]:
-            d_b = _heads_grad_b(row_ptr, col_idx, g, m, k, a2).view(k, ctx.heads, ctx.d)
+            d_b = TRANSPOSE_CACHE.grad_b_heads(row_ptr, col_idx, g, m, k, a2)
+            d_b = d_b.view(k, ctx.heads, ctx.d)
         return None, None, d_a, d_b
 
 
@@ -295,9 +308,7 @@ def _spmm_heads(row_ptr, col_idx, values, m, k, b, out, reduce):
                            f"{tuple(values.shape)} for b {tuple(b.shape)}")
     m, k = int(m), int(k)
     heads, d = b.shape[1], b.shape[2]
-    if torch.is_grad_enabled() and (values.requires_grad or b.requires_grad):
-        if out is not None:
-            raise RuntimeError("spmm: out= is not supported when gradients are required")
+    if _recording("spmm", out, values, b):
         return SpmmCsrHeadsFunction.apply(row_ptr, col_idx, values, m, k, b)
     out2 = None
     if out is not None:
@@ -310,35 +321,25 @@ def _spmm_heads(row_ptr, col_idx, values, m, k, b, out, reduce):
 
 
 class EdgeSoftmaxFunction(torch.autograd.Function):
-    """y = edge_softmax(row_ptr, e), differentiable in e.  The output is saved and the backward is
-    op "edge_softmax_csr_grad" on it (nothing is recomputed)."""
+    """y = edge_softmax(row_ptr, e) for e [nnz] or [nnz, H], differentiable in e.  The output is
+    saved and the backward is one launch of op "edge_softmax_csr_grad" (for [nnz, H]:
+    "edge_softmax_csr_heads_grad") on it (nothing is recomputed)."""
 
     @staticmethod
     def forward(ctx, row_ptr, col_idx, e):
-        y = _C.edge_softmax_csr(row_ptr, col_idx, e)
+        op = _C.edge_softmax_csr_heads if e.dim() == 2 else _C.edge_softmax_csr
+        y = op(row_ptr, col_idx, e)
         ctx.save_for_backward(row_ptr, col_idx, y)
         return y
 
     @staticmethod
     def backward(ctx, d_y):
         row_ptr, col_idx, y = ctx.saved_tensors
-        return None, None, _C.edge_softmax_csr_grad(row_ptr, col_idx, y, d_y.contiguous())
+        op = _C.edge_softmax_csr_heads_grad if y.dim() == 2 else _C.edge_softmax_csr_grad
+        return None, None, op(row_ptr, col_idx, y, d_y.contiguous())
 
 
-class EdgeSoftmaxHeadsFunction(torch.autograd.Function):
-    """y = edge_softmax(row_ptr, e) for e [nnz, H], differentiable in e.  The output is saved and
-    the backward is one launch of op "edge_softmax_csr_heads_grad" on it."""
-
-    @staticmethod
-    def forward(ctx, row_ptr, col_idx, e):
-        y = _C.edge_softmax_csr_heads(row_ptr, col_idx, e)
-        ctx.save_for_backward(row_ptr, col_idx, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, d_y):
-        row_ptr, col_idx, y = ctx.saved_tensors
-        return None, None, _C.edge_softmax_csr_heads_grad(row_ptr, col_idx, y, d_y.contiguous())
+EdgeSoftmaxHeadsFunction = EdgeSoftmaxFunction  # one class serves both ranks
 
 
 def _edge_softmax_heads_composed(a_csr_row_ptr, a_csr_col_idx, e):
@@ -365,18 +366,10 @@ def edge_softmax(a_csr_row_ptr, a_csr_col_idx, e, *, out=None):
     a non-contiguous e or upstream gradient is made contiguous first, `out=` (a contiguous
     [nnz, H] tensor) is written directly.  Every head has the bits of the 1-D call on its
     column."""
-    if e.dim() == 2:
-        if torch.is_grad_enabled() and e.requires_grad:
-            if out is not None:
-                raise RuntimeError(
-                    "edge_softmax: out= is not supported when gradients are required")
-            return EdgeSoftmaxHeadsFunction.apply(a_csr_row_ptr, a_csr_col_idx, e)
-        return _C.edge_softmax_csr_heads(a_csr_row_ptr, a_csr_col_idx, e, out=out)
-    if torch.is_grad_enabled() and e.requires_grad:
-        if out is not None:
-            raise RuntimeError("edge_softmax: out= is not supported when gradients are required")
+    if _recording("edge_softmax", out, e):
         return EdgeSoftmaxFunction.apply(a_csr_row_ptr, a_csr_col_idx, e)
-    return _C.edge_softmax_csr(a_csr_row_ptr, a_csr_col_idx, e, out=out)
+    op = _C.edge_softmax_csr_heads if e.dim() == 2 else _C.edge_softmax_csr
+    return op(a_csr_row_ptr, a_csr_col_idx, e, out=out)
 
 
 class GraphAttentionFunction(torch.autograd.Function):
@@ -407,7 +400,7 @@ class GraphAttentionFunction(torch.autograd.Function):
         if g is None and d_attn_up is None:
             return None, None, None, None, None
         if ctx.needs_input_grad[4] and g is not None:
-            d_v = _heads_grad_b(row_ptr, col_idx, attn, m, k, g).view(k, heads, d)
+            d_v = TRANSPOSE_CACHE.grad_b_heads(row_ptr, col_idx, attn, m, k, g).view(k, heads, d)
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             if g is None:  # only the returned weights entered the loss
                 d_attn = d_attn_up
@@ -419,7 +412,8 @@ class GraphAttentionFunction(torch.autograd.Function):
             if ctx.needs_input_grad[2]:
                 d_q = _C.spmm_csr_heads(row_ptr, col_idx, d_e, m, k, k2).view(m, heads, d)
             if ctx.needs_input_grad[3]:
-                d_k = _heads_grad_b(row_ptr, col_idx, d_e, m, k, q2).view(k, heads, d)
+                d_k = TRANSPOSE_CACHE.grad_b_heads(row_ptr, col_idx, d_e, m, k, q2)
+                d_k = d_k.view(k, heads, d)
         return None, None, d_q, d_k, d_v
 
 
@@ -454,7 +448,7 @@ def graph_attention(a_csr_row_ptr, a_csr_col_idx, q, k, v, *, return_attention=F
         raise RuntimeError("graph_attention: expected all tensors on the same device, got "
                            f"{q.device}, {k.device}, {v.device}")
     heads, d = k.shape[1], k.shape[2]
-    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+    if _recording("graph_attention", None, q, k, v):
         out, attn = GraphAttentionFunction.apply(a_csr_row_ptr, a_csr_col_idx, q, k, v)
     else:
         out, attn = _C.graph_attention_csr_heads(a_csr_row_ptr, a_csr_col_idx, _heads_2d(q, "q"),
@@ -487,8 +481,8 @@ class GatSoftmaxFunction(torch.autograd.Function):
                                                   d_attn.contiguous(), ctx.negative_slope)
         d_col = None
         if ctx.needs_input_grad[3]:
-            d_col = _heads_grad_b(row_ptr, col_idx, ds, s_row.shape[0], s_col.shape[0],
-                                  torch.ones_like(s_row))
+            d_col = TRANSPOSE_CACHE.grad_b_heads(row_ptr, col_idx, ds, s_row.shape[0],
+                                                 s_col.shape[0], torch.ones_like(s_row))
         return None, None, d_row if ctx.needs_input_grad[2] else None, d_col, None
 
 
@@ -510,9 +504,7 @@ def gat_softmax(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, negative_slope=0.2, 
     if flat:
         s_row, s_col = s_row.unsqueeze(1), s_col.unsqueeze(1)
     negative_slope = float(negative_slope)
-    if torch.is_grad_enabled() and (s_row.requires_grad or s_col.requires_grad):
-        if out is not None:
-            raise RuntimeError("gat_softmax: out= is not supported when gradients are required")
+    if _recording("gat_softmax", out, s_row, s_col):
         attn = GatSoftmaxFunction.apply(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, negative_slope)
         return attn.squeeze(1) if flat else attn
     if flat and out is not None:
@@ -582,9 +574,7 @@ def spmm_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_co
     column c of row r for "max" / "min" (-1 for an empty row), an empty [0, N] tensor for "sum" /
     "mean".  With autograd, as `spmm`; `out=` only when no gradient is being recorded."""
     _C.reduce_code(reduce)  # ValueError for an unknown name, before anything runs
-    if torch.is_grad_enabled() and (a_csr_values.requires_grad or b.requires_grad):
-        if out is not None:
-            raise RuntimeError("spmm_reduce: out= is not supported when gradients are required")
+    if _recording("spmm_reduce", out, a_csr_values, b):
         if reduce == "sum":
             res = SpmmCsrFunction.apply(a_csr_row_ptr, a_csr_col_idx, a_csr_values,
                                         int(a_num_rows), int(a_num_cols), b, 0)
@@ -616,9 +606,7 @@ def spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b, 
     if reduce != "sum":
         return spmm_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b,
                            reduce, out=out)[0]
-    if torch.is_grad_enabled() and (a_csr_values.requires_grad or b.requires_grad):
-        if out is not None:
-            raise RuntimeError("spmm: out= is not supported when gradients are required")
+    if _recording("spmm", out, a_csr_values, b):
         return SpmmCsrFunction.apply(a_csr_row_ptr, a_csr_col_idx, a_csr_values, int(a_num_rows),
                                      int(a_num_cols), b, int(static_csr))
     return spmm_csr(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b, out=out,
@@ -658,11 +646,7 @@ def fused_spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_col
                *, relu=False, out=None, static_csr=0):
     """A GCN layer's aggregation + bias + activation: relu?(A @ b + bias?) with autograd.
     `static_csr` as for `spmm`: the forward plans an unchanged CSR once."""
-    needs = (a_csr_values.requires_grad or b.requires_grad or
-             (bias is not None and bias.requires_grad))
-    if torch.is_grad_enabled() and needs:
-        if out is not None:
-            raise RuntimeError("fused_spmm: out= is not supported when gradients are required")
+    if _recording("fused_spmm", out, a_csr_values, b, bias):
         return FusedSpmmCsrFunction.apply(a_csr_row_ptr, a_csr_col_idx, a_csr_values,
                                           int(a_num_rows), int(a_num_cols), b, bias, bool(relu),
                                           int(static_csr))

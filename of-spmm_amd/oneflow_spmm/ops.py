@@ -35,6 +35,20 @@ def _with(o: Options | None, **fields) -> Options:
     return c
 
 
+def _nz(t):
+    """The data pointer of a tensor, NULL for None or an empty one."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _workspace(device, what, query, *args, workspace_bytes: int | None = None):
+    """(buffer, bytes) of one device launch: the size `query(*args, &size)` answers, or
+    workspace_bytes if given (the query is still made), in a buffer of max(bytes, 1) bytes."""
+    size = ctypes.c_size_t(0)
+    check(query(*args, ctypes.byref(size)), what)
+    ws = size.value if workspace_bytes is None else int(workspace_bytes)
+    return torch.empty(max(ws, 1), dtype=torch.uint8, device=device), ws
+
+
 def default_split(n: int) -> int:
     return int(LIB.ofx_spmm_default_split(int(n)))
 
@@ -155,14 +169,14 @@ def spmm_csr_gathered(row_ptr, col_idx, values, values_perm, b, m, k, *, out=Non
     if out is None:
         out = torch.empty((m, b.shape[1]), dtype=b.dtype, device=b.device)
     n, nnz = b.shape[1], col_idx.numel()
-    ws = workspace_size(row_ptr.dtype, b.dtype, m, k, n, nnz, options)
-    wbuf = torch.empty(max(ws, 1), dtype=torch.uint8, device=b.device)
-    nz = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
-    check(LIB.ofx_spmm_csr_gathered(current_stream_handle(b), dtype_code(row_ptr.dtype),
-                                    dtype_code(b.dtype), m, k, n, nnz, row_ptr.data_ptr(),
-                                    nz(col_idx), nz(values), nz(values_perm), nz(b), b.stride(0),
-                                    out.data_ptr(), out.stride(0), 0, m, wbuf.data_ptr(), ws,
-                                    ctypes.byref(options) if options else None),
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(b.dtype)
+    popt = ctypes.byref(options) if options else None
+    wbuf, ws = _workspace(b.device, "workspace_size", LIB.ofx_spmm_csr_workspace_size, idt, vdt,
+                          m, k, n, nnz, popt)
+    check(LIB.ofx_spmm_csr_gathered(current_stream_handle(b), idt, vdt, m, k, n, nnz,
+                                    row_ptr.data_ptr(), _nz(col_idx), _nz(values),
+                                    _nz(values_perm), _nz(b), b.stride(0), out.data_ptr(),
+                                    out.stride(0), 0, m, wbuf.data_ptr(), ws, popt),
           "spmm_csr_gathered")
     return out
 
@@ -177,17 +191,15 @@ def relu_bias_grad(y, dy, *, relu: bool, bias_grad: bool, num_threads: int = 0):
     db = torch.empty(n, dtype=dy.dtype, device=dy.device) if bias_grad else None
     if not relu and not bias_grad:
         return dx, db
-    nz = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
     yy = y if relu else None
-    args = (m, n, nz(yy), yy.stride(0) if yy is not None else n, nz(dy), dy.stride(0),
-            nz(dx) if relu else None, dx.stride(0) if relu else n, nz(db), 1 if relu else 0)
+    args = (m, n, _nz(yy), yy.stride(0) if yy is not None else n, _nz(dy), dy.stride(0),
+            _nz(dx) if relu else None, dx.stride(0) if relu else n, _nz(db), 1 if relu else 0)
     if dy.device.type == "cpu":
         check(LIB.ofx_relu_bias_grad_cpu(int(num_threads), dt, *args), "relu_bias_grad")
         return dx, db
-    size = ctypes.c_size_t(0)
-    check(LIB.ofx_relu_bias_grad_workspace_size(dt, m, n, ctypes.byref(size)), "relu_bias_grad")
-    ws = torch.empty(max(size.value, 1), dtype=torch.uint8, device=dy.device)
-    check(LIB.ofx_relu_bias_grad(current_stream_handle(dy), dt, *args, ws.data_ptr(), size.value),
+    wbuf, ws = _workspace(dy.device, "relu_bias_grad", LIB.ofx_relu_bias_grad_workspace_size, dt,
+                          m, n)
+    check(LIB.ofx_relu_bias_grad(current_stream_handle(dy), dt, *args, wbuf.data_ptr(), ws),
           "relu_bias_grad")
     return dx, db
 
@@ -209,10 +221,6 @@ def spmm_csr_cpu(row_ptr, col_idx, values, b, m, k, *, out=None, row_begin=0, ro
     return out
 
 
-def _nz(t):
-    return t.data_ptr() if t is not None and t.numel() else None
-
-
 def spmm_csr_heads(row_ptr, col_idx, values, b, m, k, heads, *, out=None, row_begin=0,
                    row_end=None, options: Options | None = None, num_threads: int = 0,
                    workspace_bytes: int | None = None):
@@ -232,11 +240,8 @@ def spmm_csr_heads(row_ptr, col_idx, values, b, m, k, heads, *, out=None, row_be
     if b.device.type == "cpu":
         check(LIB.ofx_spmm_csr_heads_cpu(int(num_threads), *body, popt), "spmm_csr_heads_cpu")
         return out
-    size = ctypes.c_size_t(0)
-    check(LIB.ofx_spmm_csr_heads_workspace_size(idt, vdt, m, k, heads, d, nnz, popt,
-                                                ctypes.byref(size)), "spmm_csr_heads")
-    ws = size.value if workspace_bytes is None else int(workspace_bytes)
-    wbuf = torch.empty(max(ws, 1), dtype=torch.uint8, device=b.device)
+    wbuf, ws = _workspace(b.device, "spmm_csr_heads", LIB.ofx_spmm_csr_heads_workspace_size, idt,
+                          vdt, m, k, heads, d, nnz, popt, workspace_bytes=workspace_bytes)
     check(LIB.ofx_spmm_csr_heads(current_stream_handle(b), *body, wbuf.data_ptr(), ws, popt),
           "spmm_csr_heads")
     return out
@@ -258,11 +263,8 @@ def sddmm_csr_heads(row_ptr, col_idx, a, b, m, k, heads, *, out=None, row_begin=
     if b.device.type == "cpu":
         check(LIB.ofx_sddmm_csr_heads_cpu(int(num_threads), *body), "sddmm_csr_heads_cpu")
         return out
-    size = ctypes.c_size_t(0)
-    check(LIB.ofx_sddmm_csr_heads_workspace_size(idt, vdt, m, heads, d, nnz, ctypes.byref(size)),
-          "sddmm_csr_heads")
-    ws = size.value if workspace_bytes is None else int(workspace_bytes)
-    wbuf = torch.empty(max(ws, 1), dtype=torch.uint8, device=b.device)
+    wbuf, ws = _workspace(b.device, "sddmm_csr_heads", LIB.ofx_sddmm_csr_heads_workspace_size,
+                          idt, vdt, m, heads, d, nnz, workspace_bytes=workspace_bytes)
     check(LIB.ofx_sddmm_csr_heads(current_stream_handle(b), *body, wbuf.data_ptr(), ws),
           "sddmm_csr_heads")
     return out
@@ -293,12 +295,9 @@ def graph_attention_csr_heads(row_ptr, col_idx, q, k_mat, v, m, k, heads, *, out
         check(LIB.ofx_graph_attention_csr_heads_cpu(int(num_threads), *body, popt),
               "graph_attention_csr_heads_cpu")
         return out, attn
-    size = ctypes.c_size_t(0)
-    check(LIB.ofx_graph_attention_csr_heads_workspace_size(idt, vdt, m, k, heads, d, nnz, popt,
-                                                           ctypes.byref(size)),
-          "graph_attention_csr_heads")
-    ws = size.value if workspace_bytes is None else int(workspace_bytes)
-    wbuf = torch.empty(max(ws, 1), dtype=torch.uint8, device=k_mat.device)
+    wbuf, ws = _workspace(k_mat.device, "graph_attention_csr_heads",
+                          LIB.ofx_graph_attention_csr_heads_workspace_size, idt, vdt, m, k, heads,
+                          d, nnz, popt, workspace_bytes=workspace_bytes)
     check(LIB.ofx_graph_attention_csr_heads(current_stream_handle(k_mat), *body, wbuf.data_ptr(),
                                             ws, popt), "graph_attention_csr_heads")
     return out, attn

@@ -7,7 +7,7 @@ The reference is never the code under test.  The scores are restated in numpy (a
 add, the z > 0 select and one multiply, helpers.from_f32 for the rounding to T), then fed to the
 existing ofx_edge_softmax_csr_heads_cpu and, per column, to edge_softmax_helpers.ref_forward.
 Backward: ref_backward gives de, the numpy mask multiply ds, edge_softmax_helpers.tree_sum d_row and
-autograd._heads_grad_b (the multi-head SpMM on the transpose) d_col."""
+autograd.TRANSPOSE_CACHE.grad_b_heads (the multi-head SpMM on the transpose) d_col."""
 from __future__ import annotations
 
 import ctypes
@@ -561,7 +561,7 @@ def check_public_api(dev):
 
 def check_grads(dev, heads, dtype, col_range=None):
     """s_row.grad and s_col.grad of gat_softmax against the reference chain, bit for bit: the
-    existing kCPU edge softmax and ref_backward for de, numpy for ds and d_row, _heads_grad_b on
+    existing kCPU edge softmax and ref_backward for de, numpy for ds and d_row, grad_b_heads on
     host tensors for d_col."""
     rp, ci, s_row, s_col, g = problem([3, 1, 0, 5, 2, 12, 4, 1, 7, 600, 33, 64, 130], heads, dtype,
                                       seed=21, col_range=col_range)
@@ -569,7 +569,8 @@ def check_grads(dev, heads, dtype, col_range=None):
     e, z = ref_scores(rp, ci, s_row, s_col, 0.2)
     y = hc.run_forward(rp, e, m)
     want_ds, want_d_row = ref_grad(rp, ci, y, g, z, 0.2)
-    want_d_col = autograd._heads_grad_b(rp, ci, want_ds, m, K, torch.ones_like(s_row))
+    want_d_col = autograd.TRANSPOSE_CACHE.grad_b_heads(rp, ci, want_ds, m, K,
+                                                       torch.ones_like(s_row))
     d_rp, d_ci, d_g = to_dev(dev, rp, ci, g)
     a, b = (t.clone().to(dev).requires_grad_(True) for t in (s_row, s_col))
     attn = flow_spmm.gat_softmax(d_rp, d_ci, a, b)
