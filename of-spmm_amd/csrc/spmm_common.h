@@ -1,6 +1,6 @@
 // spmm_common.h — numeric contract shared by the HIP kernels (spmm_csr.hip) and the CPU kernel
-// (spmm_cpu.cpp): storage types, conversions, dtype dispatch, schedule (split) resolution,
-// counter-based RNG.
+// (spmm_cpu.cpp): storage types, conversions, dtype dispatch and the generic argument checks of
+// the C-ABI entries, schedule (split) resolution, counter-based RNG.
 //
 // The accumulation contract restates the reference composition gather -> multiply ->
 // unsorted_segment_sum (oneflow/user/kernels/gather_kernel_util.cpp:72-92,
@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "ofx_internal.h"  // OFX_REQUIRE of the argument checks
 #include "ofx_spmm.h"
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -148,23 +149,28 @@ OFX_HD bool is_value_dtype(int dt) {
          dt == OFX_DT_BFLOAT16;
 }
 
-// Dtype dispatch of the C-ABI entries (host code): by_index calls f(I*), by_types f(T*, I*), with
-// null pointers of the index / value types the dtype codes name.  An unknown code falls through
-// to int64 / f16, so an entry checks is_index_dtype / is_value_dtype before it dispatches.
+// Dtype dispatch of the C-ABI entries (host code): by_index calls f(I*), by_value f(T*), by_types
+// f(T*, I*), with null pointers of the index / value types the dtype codes name.  An unknown code
+// falls through to int64 / f16, so an entry checks is_index_dtype / is_value_dtype before it
+// dispatches.
 template <typename F>
 int by_index(int idx_dtype, F&& f) {
   if (idx_dtype == OFX_DT_INT32) return f((int32_t*)nullptr);
   return f((int64_t*)nullptr);
 }
 template <typename F>
+int by_value(int val_dtype, F&& f) {
+  switch (val_dtype) {
+    case OFX_DT_FLOAT: return f((float*)nullptr);
+    case OFX_DT_DOUBLE: return f((double*)nullptr);
+    case OFX_DT_BFLOAT16: return f((bf16*)nullptr);
+    default: return f((f16*)nullptr);
+  }
+}
+template <typename F>
 int by_types(int idx_dtype, int val_dtype, F&& f) {
   return by_index(idx_dtype, [&](auto* ip) -> int {
-    switch (val_dtype) {
-      case OFX_DT_FLOAT: return f((float*)nullptr, ip);
-      case OFX_DT_DOUBLE: return f((double*)nullptr, ip);
-      case OFX_DT_BFLOAT16: return f((bf16*)nullptr, ip);
-      default: return f((f16*)nullptr, ip);
-    }
+    return by_value(val_dtype, [&](auto* tp) -> int { return f(tp, ip); });
   });
 }
 
@@ -172,6 +178,30 @@ int by_types(int idx_dtype, int val_dtype, F&& f) {
 // <= 0.
 static inline int threads_of(int num_threads) {
   return num_threads > 0 ? num_threads : omp_get_max_threads();
+}
+
+// ---- argument checks shared by the device and host entries ------------------------------------
+static inline int check_types_sizes(const char* fn, int idx_dtype, int val_dtype, int64_t m,
+                                    int64_t k, int64_t n, int64_t nnz) {
+  OFX_REQUIRE(is_index_dtype(idx_dtype), OFX_EUNSUPPORTED, "%s: index dtype %d is not int32/int64",
+              fn, idx_dtype);
+  OFX_REQUIRE(is_value_dtype(val_dtype), OFX_EUNSUPPORTED,
+              "%s: value dtype %d is not float/double/float16/bfloat16", fn, val_dtype);
+  OFX_REQUIRE(m >= 0 && k >= 0 && n >= 0 && nnz >= 0, OFX_EINVAL,
+              "%s: negative size (m=%lld k=%lld n=%lld nnz=%lld)", fn, (long long)m, (long long)k,
+              (long long)n, (long long)nnz);
+  OFX_REQUIRE(idx_dtype == OFX_DT_INT64 || (nnz <= INT32_MAX && k <= INT32_MAX && m <= INT32_MAX),
+              OFX_EINVAL, "%s: int32 indices cannot address nnz=%lld / m=%lld / k=%lld", fn,
+              (long long)nnz, (long long)m, (long long)k);
+  return OFX_OK;
+}
+
+static inline int check_row_range(const char* fn, int64_t row_begin, int64_t row_end,
+                                  int64_t rows) {
+  OFX_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= rows, OFX_EINVAL,
+              "%s: row range [%lld, %lld) outside [0, %lld)", fn, (long long)row_begin,
+              (long long)row_end, (long long)rows);
+  return OFX_OK;
 }
 
 // ---- schedule ---------------------------------------------------------------------------

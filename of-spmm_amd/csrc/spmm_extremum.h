@@ -56,34 +56,11 @@ OFX_HD T scale_by_degree(T x, int64_t deg) {
   return Num<T>::store(Num<T>::load(x) / A(deg));
 }
 
-// ---- argument checks shared by the device and host entries ----------------------------------
+// ---- argument checks shared by the device and host entries (on spmm_common.h's generic ones) --
 static inline int check_reduce_code(int reduce, const char* fn) {
   OFX_REQUIRE(reduce == OFX_REDUCE_SUM || reduce == OFX_REDUCE_MEAN || reduce == OFX_REDUCE_MAX ||
                   reduce == OFX_REDUCE_MIN,
               OFX_EINVAL, "%s: unknown reduce code %d (OFX_REDUCE_SUM/MEAN/MAX/MIN)", fn, reduce);
-  return OFX_OK;
-}
-
-static inline int check_types_sizes(const char* fn, int idx_dtype, int val_dtype, int64_t m,
-                                    int64_t k, int64_t n, int64_t nnz) {
-  OFX_REQUIRE(is_index_dtype(idx_dtype), OFX_EUNSUPPORTED, "%s: index dtype %d is not int32/int64",
-              fn, idx_dtype);
-  OFX_REQUIRE(is_value_dtype(val_dtype), OFX_EUNSUPPORTED,
-              "%s: value dtype %d is not float/double/float16/bfloat16", fn, val_dtype);
-  OFX_REQUIRE(m >= 0 && k >= 0 && n >= 0 && nnz >= 0, OFX_EINVAL,
-              "%s: negative size (m=%lld k=%lld n=%lld nnz=%lld)", fn, (long long)m, (long long)k,
-              (long long)n, (long long)nnz);
-  OFX_REQUIRE(idx_dtype == OFX_DT_INT64 || (nnz <= INT32_MAX && k <= INT32_MAX && m <= INT32_MAX),
-              OFX_EINVAL, "%s: int32 indices cannot address nnz=%lld / m=%lld / k=%lld", fn,
-              (long long)nnz, (long long)m, (long long)k);
-  return OFX_OK;
-}
-
-static inline int check_row_range(const char* fn, int64_t row_begin, int64_t row_end,
-                                  int64_t rows) {
-  OFX_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= rows, OFX_EINVAL,
-              "%s: row range [%lld, %lld) outside [0, %lld)", fn, (long long)row_begin,
-              (long long)row_end, (long long)rows);
   return OFX_OK;
 }
 

@@ -41,14 +41,12 @@ class SddmmCsrKernel final : public user_op::OpKernel, public user_op::CudaGraph
     int rc;
     if (device_type == DeviceType::kHIP) {
       const TmpBuffer tmp(ctx);
-      void* ws = tmp.ptr;  // replaced by a static plan's own workspace
-      size_t ws_bytes = tmp.bytes;
       ep::HipStream* hs = ctx->stream()->As<ep::HipStream>();
       void* stream = hs->hip_stream();
       ofx_spmm_options opts = OFX_SPMM_OPTIONS_INIT;
       auto* plans = dynamic_cast<SpmmCsrPlanState*>(state);
       const int64_t static_csr = ctx->Attr<int64_t>("static_csr");
-      StaticPlan sp;
+      StaticPlanLaunch launch(plans, hs->IsGraphCapturing(), tmp.ptr, tmp.bytes);
       if (plans != nullptr && static_csr != 0 && m > 0 && n > 0 && nnz > 0) {
         size_t need = 0;
         rc = ofx_sddmm_csr_workspace_size(idx_dt, val_dt, m, n, nnz, &need);
@@ -58,18 +56,15 @@ class SddmmCsrKernel final : public user_op::OpKernel, public user_op::CudaGraph
                                         plans->key_on_stream() ? stream : nullptr,
                                         hs->device_index(), idx_dt, val_dt, m, k, n, nnz, 0, m,
                                         0, 0, 0, 0};
-        auto plan = [&](void* sws, size_t bytes) {
+        launch.Use(key, need, "sddmm_csr", [&](void* sws, size_t bytes) {
           return ofx_sddmm_csr_plan(stream, idx_dt, val_dt, m, n, nnz, row_ptr->dptr(), 0, m, sws,
                                     bytes);
-        };
-        if (UseStaticPlan(plans, key, need, hs->IsGraphCapturing(), "sddmm_csr", plan, &ws,
-                          &ws_bytes, &sp))
-          opts.planned = 1;
+        }, &opts);
       }
-      rc = ofx_sddmm_csr_ex(stream, idx_dt, val_dt, m, k, n, nnz, row_ptr->dptr(),
-                            col_idx->dptr(), a->dptr(), a->row_stride(), b->dptr(),
-                            b->row_stride(), out->mut_dptr(), 0, m, ws, ws_bytes, &opts);
-      if (rc != OFX_OK && sp.keyed) plans->Drop(sp.key, hs->IsGraphCapturing());
+      rc = launch.Launched(ofx_sddmm_csr_ex(
+          stream, idx_dt, val_dt, m, k, n, nnz, row_ptr->dptr(), col_idx->dptr(), a->dptr(),
+          a->row_stride(), b->dptr(), b->row_stride(), out->mut_dptr(), 0, m, launch.ws(),
+          launch.ws_bytes(), &opts));
     } else {
       rc = ofx_sddmm_csr_cpu(ctx->stream()->As<ep::CpuStream>()->num_threads(), idx_dt, val_dt, m,
                              k, n, nnz, row_ptr->dptr(), col_idx->dptr(), a->dptr(),
@@ -111,17 +106,6 @@ class CsrTransposeKernel final : public user_op::OpKernel {
     OFX_KERNEL_CHECK(rc == OFX_OK, "csr_transpose kernel failed (" << rc << "): " << ofx_last_error());
   }
 };
-
-size_t InferSddmmTmpSize(user_op::InferSizeContext* ctx) {
-  const user_op::TensorDesc& row_ptr = ctx->InputTensorDesc("a_csr_row_ptr", 0);
-  const user_op::TensorDesc& col_idx = ctx->InputTensorDesc("a_csr_col_idx", 0);
-  const user_op::TensorDesc& b = ctx->InputTensorDesc("b", 0);
-  size_t bytes = 0;
-  const int rc = ofx_sddmm_csr_workspace_size(DtCode(row_ptr.data_type()), DtCode(b.data_type()),
-                                              ctx->Attr<int64_t>("a_num_rows"), b.shape().At(1),
-                                              col_idx.shape().At(0), &bytes);
-  return rc == OFX_OK ? bytes : 0;
-}
 
 size_t InferTransposeTmpSize(user_op::InferSizeContext* ctx) {
   const user_op::TensorDesc& row_ptr = ctx->InputTensorDesc("a_csr_row_ptr", 0);

@@ -1,6 +1,6 @@
 // spmm_plan_state.h — the static-CSR plan store of the spmm_csr family's HIP kernels (op attr
-// static_csr): the kernel state that keeps work-list plans across calls, and the helper a
-// Compute uses to launch over a kept plan.  Shared by spmm_kernel.cpp (spmm_csr,
+// static_csr): the kernel state that keeps work-list plans across calls, and the scope a
+// Compute launches in over a kept plan.  Shared by spmm_kernel.cpp (spmm_csr,
 // fused_spmm_csr, spmm_csr_gathered) and sddmm_kernel.cpp (sddmm_csr).
 #ifndef OFX_ONEFLOW_USER_KERNELS_SPMM_PLAN_STATE_H_
 #define OFX_ONEFLOW_USER_KERNELS_SPMM_PLAN_STATE_H_
@@ -164,40 +164,58 @@ class SpmmCsrPlanState final : public user_op::OpKernelState {
   int64_t plans_ = 0, hits_ = 0;
 };
 
-// A static call on a HIP kernel (attr static_csr != 0): the workspace of `plans` holding the
-// plan for `key` -- built by plan_fn(ws) on a miss -- replaces the tmp buffer (*ws, *ws_bytes)
-// and the function returns true (the caller launches with planned = 1).  sp->hold keeps the
-// state's lock until the launch is enqueued (the caller's scope); sp->keyed says a plan is in use
-// (the caller drops it if the launch fails).  `need` = 0 (no work list) or a miss while the
-// stream captures keep the ordinary path (false).
-struct StaticPlan {
-  SpmmCsrPlanState::Key key{};
-  bool keyed = false;
-  std::unique_lock<std::recursive_mutex> hold;
-};
+// The workspace of one launch on a HIP kernel: the op's tmp buffer, or -- for a static call
+// (attr static_csr != 0, `plans` not NULL) once Use has found or built key's plan -- the workspace
+// of `plans` that holds it.  The scope keeps the state's lock from Use until the launch is
+// enqueued (its end), and Launched(rc) drops the plan of a launch that failed.
+class StaticPlanLaunch {
+ public:
+  StaticPlanLaunch(SpmmCsrPlanState* plans, bool capturing, void* tmp, size_t tmp_bytes)
+      : plans_(plans), capturing_(capturing), ws_(tmp), ws_bytes_(tmp_bytes) {}
+  void* ws() const { return ws_; }
+  size_t ws_bytes() const { return ws_bytes_; }
 
-template <typename PlanFn>
-bool UseStaticPlan(SpmmCsrPlanState* plans, const SpmmCsrPlanState::Key& key, size_t need,
-                   bool capturing, const char* op_name, PlanFn&& plan_fn, void** ws,
-                   size_t* ws_bytes, StaticPlan* sp) {
-  if (need == 0) return false;
-  sp->hold = std::unique_lock<std::recursive_mutex>(plans->launch_mutex());
-  sp->key = key;
-  void* sws = nullptr;
-  bool planned = false;
-  int rc = plans->Acquire(key, need, capturing, &sws, &planned);
-  OFX_KERNEL_CHECK(rc == OFX_OK, op_name << " static_csr plan workspace: " << ofx_last_error());
-  if (sws == nullptr) return false;
-  sp->keyed = true;
-  if (!planned) {
-    rc = plan_fn(sws, need);
-    if (rc != OFX_OK) plans->Drop(key, capturing);
-    OFX_KERNEL_CHECK(rc == OFX_OK, op_name << " kernel failed (" << rc << "): " << ofx_last_error());
+  // Replaces the tmp buffer by the workspace holding the plan for `key` -- built by
+  // plan_fn(ws, need) on a miss -- and sets opts->planned.  `need` = 0 (no work list) or a miss
+  // while the stream captures keep the ordinary path.
+  template <typename PlanFn>
+  void Use(const SpmmCsrPlanState::Key& key, size_t need, const char* op_name, PlanFn&& plan_fn,
+           ofx_spmm_options* opts) {
+    if (need == 0) return;
+    hold_ = std::unique_lock<std::recursive_mutex>(plans_->launch_mutex());
+    key_ = key;
+    void* sws = nullptr;
+    bool planned = false;
+    int rc = plans_->Acquire(key, need, capturing_, &sws, &planned);
+    OFX_KERNEL_CHECK(rc == OFX_OK, op_name << " static_csr plan workspace: " << ofx_last_error());
+    if (sws == nullptr) return;
+    keyed_ = true;
+    if (!planned) {
+      rc = plan_fn(sws, need);
+      if (rc != OFX_OK) plans_->Drop(key, capturing_);
+      OFX_KERNEL_CHECK(rc == OFX_OK, op_name << " kernel failed (" << rc << "): " << ofx_last_error());
+    }
+    ws_ = sws;
+    ws_bytes_ = need;
+    opts->planned = 1;
   }
-  *ws = sws;
-  *ws_bytes = need;
-  return true;
-}
+
+  // The launch's status, passed through.  An earlier launch's loud failure (OFX_EPLAN) may have
+  // been this key's plan: the next call plans again.
+  int Launched(int rc) {
+    if (rc != OFX_OK && keyed_) plans_->Drop(key_, capturing_);
+    return rc;
+  }
+
+ private:
+  SpmmCsrPlanState* const plans_;
+  const bool capturing_;
+  void* ws_;
+  size_t ws_bytes_;
+  SpmmCsrPlanState::Key key_{};
+  bool keyed_ = false;
+  std::unique_lock<std::recursive_mutex> hold_;
+};
 
 }  // namespace oneflow
 

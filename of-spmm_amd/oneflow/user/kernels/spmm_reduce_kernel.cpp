@@ -15,36 +15,12 @@ namespace oneflow {
 
 namespace {
 
-class SpmmCsrReduceOpKernelCache final : public user_op::OpKernelCache {
- public:
-  SpmmCsrReduceOpKernelCache(int64_t lower, int64_t upper, int64_t logical_n)
-      : lower_(lower), upper_(upper), logical_n_(logical_n) {}
-  ~SpmmCsrReduceOpKernelCache() override = default;
-  int64_t lower() const { return lower_; }
-  int64_t upper() const { return upper_; }
-  int64_t logical_n() const { return logical_n_; }
-
- private:
-  const int64_t lower_;
-  const int64_t upper_;
-  const int64_t logical_n_;
-};
-
 template <DeviceType device_type>
 class SpmmCsrReduceKernel final : public user_op::OpKernel, public user_op::CudaGraphSupport {
  public:
   std::shared_ptr<user_op::OpKernelCache> InitOpKernelCache(
       user_op::KernelCacheContext* ctx) const override {
-    const Shape& shape = ctx->LogicalTensorDesc4ArgNameAndIndex("out", 0)->shape();
-    int64_t lower = 0, upper = shape.At(0);
-    if (ctx->parallel_ctx().parallel_num() > 1) {
-      const TensorSliceView view = GetTensorSliceView4ParallelId(
-          *ctx->parallel_desc().hierarchy(), ctx->NdSbp4ArgNameAndIndex("out", 0), shape,
-          ctx->parallel_ctx().parallel_id());
-      lower = view.At(0).begin();
-      upper = view.At(0).end();
-    }
-    return std::make_shared<SpmmCsrReduceOpKernelCache>(lower, upper, shape.At(1));
+    return CreateCsrRowRangeCache(ctx);
   }
 
   bool AlwaysComputeWhenAllOutputsEmpty() const override { return false; }
@@ -66,18 +42,8 @@ class SpmmCsrReduceKernel final : public user_op::OpKernel, public user_op::Cuda
     OFX_KERNEL_CHECK(out->data_type() == b->data_type(), "out datatype should be equal to b. ");
     const int64_t n = out->shape_view().At(1);
     const int64_t nnz = col_idx->shape_view().elem_cnt();
-    int64_t row_begin = 0, row_end = m;
-    ofx_spmm_options opts = OFX_SPMM_OPTIONS_INIT;
-    const auto* range = dynamic_cast<const SpmmCsrReduceOpKernelCache*>(cache);
-    OFX_KERNEL_CHECK(cache == nullptr || range != nullptr, "unexpected kernel cache type");
-    if (range != nullptr) {
-      row_begin = range->lower();
-      row_end = range->upper();
-      opts.split_threshold = ofx_spmm_default_split(range->logical_n());
-    }
-    OFX_KERNEL_CHECK(out->shape_view().At(0) == row_end - row_begin,
-                     "out rows " << out->shape_view().At(0) << " != row range "
-                                 << row_end - row_begin);
+    const CsrRowRange rows = RowRangeOf(cache, m, out->shape_view().At(0));
+    const int64_t row_begin = rows.begin, row_end = rows.end;
     const bool has_arg = reduce == OFX_REDUCE_MAX || reduce == OFX_REDUCE_MIN;
     void* arg_ptr = nullptr;
     int64_t ldarg = 0;
@@ -99,13 +65,13 @@ class SpmmCsrReduceKernel final : public user_op::OpKernel, public user_op::Cuda
                                k, n, nnz, row_ptr->dptr(), col_idx->dptr(), values->dptr(),
                                b->dptr(), b->row_stride(), out->mut_dptr(), out->row_stride(),
                                arg_ptr, ldarg, row_begin, row_end, reduce,
-                               tmp.ptr, tmp.bytes, &opts);
+                               tmp.ptr, tmp.bytes, &rows.opts);
     } else {
       rc = ofx_spmm_csr_reduce_cpu(ctx->stream()->As<ep::CpuStream>()->num_threads(), idx_dt,
                                    val_dt, m, k, n, nnz, row_ptr->dptr(), col_idx->dptr(),
                                    values->dptr(), b->dptr(), b->row_stride(), out->mut_dptr(),
                                    out->row_stride(), arg_ptr, ldarg, row_begin, row_end, reduce,
-                                   &opts);
+                                   &rows.opts);
     }
     OFX_KERNEL_CHECK(rc == OFX_OK,
                      "spmm_csr_reduce kernel failed (" << rc << "): " << ofx_last_error());
@@ -199,9 +165,8 @@ size_t InferReduceTmpSize(user_op::InferSizeContext* ctx) {
   const user_op::TensorDesc& row_ptr = ctx->InputTensorDesc("a_csr_row_ptr", 0);
   const user_op::TensorDesc& col_idx = ctx->InputTensorDesc("a_csr_col_idx", 0);
   const user_op::TensorDesc& b = ctx->InputTensorDesc("b", 0);
-  ofx_spmm_options opts = OFX_SPMM_OPTIONS_INIT;
-  if (const user_op::TensorDesc* lo = ctx->LogicalTensorDesc4ArgNameAndIndex("out", 0))
-    opts.split_threshold = ofx_spmm_default_split(lo->shape().At(1));
+  const ofx_spmm_options opts =
+      LogicalWidthOptions(ctx->LogicalTensorDesc4ArgNameAndIndex("out", 0));
   size_t bytes = 0;
   const int rc = ofx_spmm_csr_reduce_workspace_size(
       DtCode(row_ptr.data_type()), DtCode(b.data_type()), ctx->Attr<int64_t>("a_num_rows"),
@@ -221,17 +186,6 @@ size_t InferGradBTmpSize(user_op::InferSizeContext* ctx) {
   return rc == OFX_OK ? bytes : 0;
 }
 
-size_t InferGradValuesTmpSize(user_op::InferSizeContext* ctx) {
-  const user_op::TensorDesc& row_ptr = ctx->InputTensorDesc("a_csr_row_ptr", 0);
-  const user_op::TensorDesc& col_idx = ctx->InputTensorDesc("a_csr_col_idx", 0);
-  const user_op::TensorDesc& b = ctx->InputTensorDesc("b", 0);
-  size_t bytes = 0;
-  const int rc = ofx_sddmm_csr_workspace_size(DtCode(row_ptr.data_type()), DtCode(b.data_type()),
-                                              ctx->Attr<int64_t>("a_num_rows"), b.shape().At(1),
-                                              col_idx.shape().At(0), &bytes);
-  return rc == OFX_OK ? bytes : 0;
-}
-
 }  // namespace
 
 REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
@@ -244,7 +198,7 @@ REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_b", "out", "at_row_ptr", De
                                SpmmCsrReduceGradBKernel<DeviceType::kHIP>)
 REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_values", "out", "a_csr_row_ptr", DeviceType::kCPU, NoTmp,
                                SpmmCsrReduceGradValuesKernel<DeviceType::kCPU>)
-REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_values", "out", "a_csr_row_ptr", DeviceType::kHIP, InferGradValuesTmpSize,
+REGISTER_CSR_KERNEL_ALL_DTYPES("spmm_csr_reduce_grad_values", "out", "a_csr_row_ptr", DeviceType::kHIP, InferSddmmTmpSize,
                                SpmmCsrReduceGradValuesKernel<DeviceType::kHIP>)
 
 }  // namespace oneflow

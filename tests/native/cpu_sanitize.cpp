@@ -5,6 +5,8 @@
 // against naive loops written here, so a sanitizer-clean run is also a correctness run.
 // SURVEY.md §5 ("race detection / sanitizers"): the CPU kernel under ASan/UBSan.
 // Built and run by tests/test_native_abi.py::test_cpu_kernels_under_sanitizers.
+#include <omp.h>
+
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -234,6 +236,20 @@ void check_partition_synth() {
   EXPECT(ofx_synth_dense_host(OFX_DT_FLOAT, 3, 10, 5, 9, 2, 1, d.data()) == OFX_OK, "synth_dense");
 }
 
+// The fused epilogue's backward takes its thread count as an argument: a call leaves the
+// process's OpenMP setting as it found it.
+void check_relu_bias_grad_threads() {
+  const int64_t m = 5, n = 3;
+  std::vector<float> y(m * n, 1.f), dy(m * n, 2.f), dx(m * n), db(n);
+  const int before = omp_get_max_threads();
+  const int rc = ofx_relu_bias_grad_cpu(1, OFX_DT_FLOAT, m, n, y.data(), n, dy.data(), n,
+                                        dx.data(), n, db.data(), 1);
+  EXPECT(rc == OFX_OK, "relu_bias_grad rc=%d (%s)", rc, ofx_last_error());
+  EXPECT(db[0] == 10.f && dx[0] == 2.f, "relu_bias_grad values");
+  EXPECT(omp_get_max_threads() == before, "relu_bias_grad changed omp_get_max_threads: %d -> %d",
+         before, omp_get_max_threads());
+}
+
 void check_errors() {
   int32_t rp[3] = {0, 1, 2}, ci[2] = {0, 1};
   float v[2] = {1, 2}, b[4] = {1, 2, 3, 4}, c[4];
@@ -260,6 +276,7 @@ int main() {
   }
   check_coo();
   check_partition_synth();
+  check_relu_bias_grad_threads();
   check_errors();
   if (g_fail) {
     std::printf("FAILED %d checks\n", g_fail);

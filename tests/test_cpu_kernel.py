@@ -47,6 +47,33 @@ def test_cpu_kernel_schedules():
     assert_bitwise(out1, oracle_spmm(rp, ci, v, b)[5:40], "row range")
 
 
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("split,chunk", [(2, 1), (4, 3)])
+def test_cpu_kernel_chunk_boundaries(split, chunk, dtype):
+    """One row of every length at which the chunked sum changes its traversal -- 0, 1, split,
+    split + 1, 2*chunk - 1, 2*chunk, 2*chunk + 1, 3*chunk + 1 -- against the oracle, for the plain
+    SpMM and for the multi-head one with 1 and 3 heads (each head against the oracle on its slice).
+    (2, 1) is the smallest split with a chunk below it; with (4, 3) every 2*chunk +- 1 row is past
+    the split too, so the one-chunk row (5), the exact two chunks (6), the remainder absorbed by
+    the last chunk (7, 10) and the unsplit rows (0, 1, 4) all occur."""
+    rng = np.random.default_rng(10 * split + chunk)
+    lengths = [0, 1, split, split + 1, 2 * chunk - 1, 2 * chunk, 2 * chunk + 1, 3 * chunk + 1] * 3
+    m, k, d = len(lengths), 64, 5
+    rp, ci, _ = random_csr(m, k, lengths, rng, val_dtype=DTYPES[dtype])
+    opts = ops.make_options(split=split, chunk=chunk)
+    for heads in (1, 3):
+        vals = random_dense(ci.numel(), heads, rng, DTYPES[dtype])
+        b = random_dense(k, heads * d, rng, DTYPES[dtype])
+        out = ops.spmm_csr_heads(rp, ci, vals, b, m, k, heads, options=opts)
+        for h in range(heads):
+            vh, bh = vals[:, h].contiguous(), b[:, h * d:(h + 1) * d]
+            ref = oracle_spmm(rp, ci, vh, bh, split=split, chunk=chunk)
+            assert_bitwise(out[:, h * d:(h + 1) * d], ref, f"heads={heads} head {h}")
+            if heads == 1:
+                plain = ops.spmm_csr_cpu(rp, ci, vh, bh, m, k, options=opts)
+                assert_bitwise(plain, ref, "plain")
+
+
 @pytest.mark.parametrize("name", ["cora_f32", "cora_exact", "hub_n128_f32", "hub_n128_exact",
                                   "n1_f32", "n3_f32", "n17_f32", "empty_f32"])
 def test_cpu_kernel_on_golden(name):

@@ -26,8 +26,8 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="ROCm clang++ not found")
 def test_cpu_kernels_under_sanitizers(tmp_path):
-    """the host kernels (spmm_cpu.cpp, synth.cpp, errors.cpp) built from source
-    with AddressSanitizer + UndefinedBehaviorSanitizer (host code only) and driven over the edge
+    """the host kernels (spmm_cpu.cpp, csr_host_cpu.cpp, synth.cpp, errors.cpp)
+    built from source with AddressSanitizer + UndefinedBehaviorSanitizer (host code only) and driven over the edge
     cases by tests/native/cpu_sanitize.cpp, which also checks their results against naive loops."""
     exe = tmp_path / "cpu_sanitize"
     csrc = os.path.join(ROOT, "of-spmm_amd", "csrc")
@@ -36,7 +36,8 @@ def test_cpu_kernels_under_sanitizers(tmp_path):
                     "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas",
                     "-Wno-duplicate-decl-specifier", "-I", os.path.join(ROOT, "include"), "-I", csrc,
                     os.path.join(ROOT, "tests", "native", "cpu_sanitize.cpp"),
-                    os.path.join(csrc, "spmm_cpu.cpp"), os.path.join(csrc, "synth.cpp"),
+                    os.path.join(csrc, "spmm_cpu.cpp"), os.path.join(csrc, "csr_host_cpu.cpp"),
+                    os.path.join(csrc, "synth.cpp"),
                     os.path.join(csrc, "errors.cpp"), "-o", str(exe)], check=True)
     supp = tmp_path / "lsan.supp"
     supp.write_text("leak:___kmp_allocate\n")  # the OpenMP runtime's own thread-pool state
