@@ -691,6 +691,91 @@ int ofx_gat_softmax_csr_heads_grad_cpu(int num_threads, int idx_dtype, int val_d
                                        void* ds, void* d_row, int64_t row_begin, int64_t row_end,
                                        const ofx_spmm_options* opts);
 
+/* ---- GATv2 attention scores (ops "gatv2_scores_csr_heads" / "_grad") -------------
+ *   e[j, h] = sum over d of att[h, d] * LeakyReLU(x_row[row(j), h, d] + x_col[col_idx[j], h, d])
+ * The activation sits between the gather and the dot product, so neither ofx_sddmm_csr_heads nor
+ * ofx_gat_softmax_csr_heads can form it.  x_row T[rows, heads*d] with ldr, x_col T[k, heads*d] with
+ * ldc, att T[heads*d], e and de T[nnz, heads] contiguous; n = h*d + c; `a` is the accumulation
+ * type (f64 for f64, else f32) and slope_a is negative_slope converted to `a` once (finite and
+ * > 0, otherwise OFX_EINVAL, as for ofx_gat_softmax_csr_heads).  The contract is the composition
+ * with existing entries on materialised per-nonzero tensors, which the kernels never write.
+ *
+ * Forward, for nonzero j of row r with column c = col_idx[j]:
+ *   1. z = load(x_row[r, n]) + load(x_col[c, n]): one add in `a`.  A column outside [0, k) reads
+ *      x_col = +0.
+ *   2. u = (z > 0) ? z : z * slope_a; z = +-0 and NaN take the multiply branch.
+ *   3. U[j, n] = u rounded to T as a step of its own.  e[j, :] has exactly the bits of
+ *      ofx_sddmm_csr_heads for the left row att and the right row U[j, :]: products in `a` without
+ *      FMA, leaves of 8 consecutive columns of the head summed from +0, the head's leaves
+ *      zero-padded to a power of two and added pairwise, one rounding to T.
+ *   4. d <= 2048 (OFX_EUNSUPPORTED beyond).  heads == 0, nnz == 0 or an empty row range writes
+ *      nothing.
+ *
+ * Gradient, from the upstream de T[nnz, heads]; z is formed again by the same add:
+ *   1. per column w_pos[n] = load(att[n]) and w_neg[n] = load(att[n]) * slope_a, one multiply in `a`
+ *   2. T1[j, n] = store(load(de[j, h]) * (z > 0 ? w_pos[n] : w_neg[n]))
+ *   3. T2[j, n] = store(load(de[j, h]) * load(U[j, n]))
+ *   4. d_x[r, :] and p[r, :] have exactly the bits of ofx_spmm_csr_heads on the CSR
+ *      (row_ptr, arange(nnz)) with values of ones and b = T1, respectively b = T2, under the same
+ *      options: nonzeros ascending, the hub rule of resolve_schedule(d, opts) (a row of more than
+ *      `split` nonzeros summed per chunk from +0 and the partials added in chunk order), an empty
+ *      row writes +0; `planned` and `variant` are refused (OFX_EINVAL) as that entry refuses them.
+ *   5. d_x T[rows, heads*d] (ldd) is the gradient in x_row.
+ *   6. p T[rows, heads*d] (ldp) is written only when p != NULL.  The gradient in att is the column
+ *      sum of p in ofx_relu_bias_grad's fixed order (dy = p, no mask); there is no other reduction.
+ *   7. The gradient in x_col is this same entry on the transposed CSR (ofx_csr_transpose): the
+ *      rows are A^T's, x_row and x_col change places (the add commutes: z has the same bits), de is
+ *      gathered by the rows of perm and p is not requested.  No atomics anywhere.  The transpose
+ *      drops columns >= k, consistent with the forward's +0.
+ *
+ * Row range [row_begin, row_end): x_row, d_x and p hold the rows from row_begin on; e is written
+ * and de read at the global nonzero positions.  Offsets are formed in 64 bits.  The gradient
+ * writes every row of the range (nnz == 0: +0); rows == 0 or heads*d == 0 writes nothing.  Device
+ * versions: asynchronous on `stream`, no atomics, no allocation, no host synchronisation,
+ * capturable in a graph.  Workspace: the forward's is ofx_sddmm_csr_heads's, the gradient's the
+ * multi-head SpMM's layout with heads*d partial columns, or 2*heads*d when p is requested (with_p);
+ * OFX_EWORKSPACE when it is too small.  OFX_EINVAL: a negative size, a bad row range, a bad slope,
+ * a leading dimension below heads*d, a NULL pointer, an output that overlaps an input or the other
+ * output; OFX_EUNSUPPORTED: a dtype, d > 2048.  Nothing is launched on an error.  HIP kernels and
+ * kCPU kernels give the same bits; the kCPU kernels' bits do not depend on num_threads.          */
+int ofx_gatv2_scores_csr_heads_workspace_size(int idx_dtype, int val_dtype, int64_t m,
+                                              int64_t heads, int64_t d, int64_t nnz,
+                                              size_t* bytes);
+int ofx_gatv2_scores_csr_heads(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                               int64_t heads, int64_t d, int64_t nnz, const void* row_ptr,
+                               const void* col_idx, const void* x_row, int64_t ldr,
+                               const void* x_col, int64_t ldc, const void* att /* [heads*d] */,
+                               double negative_slope, void* e /* [nnz, heads] */,
+                               int64_t row_begin, int64_t row_end, void* workspace,
+                               size_t workspace_bytes);
+int ofx_gatv2_scores_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                   int64_t k, int64_t heads, int64_t d, int64_t nnz,
+                                   const void* row_ptr, const void* col_idx, const void* x_row,
+                                   int64_t ldr, const void* x_col, int64_t ldc, const void* att,
+                                   double negative_slope, void* e, int64_t row_begin,
+                                   int64_t row_end);
+int ofx_gatv2_scores_csr_heads_grad_workspace_size(int idx_dtype, int val_dtype, int64_t m,
+                                                   int64_t k, int64_t heads, int64_t d,
+                                                   int64_t nnz, int with_p,
+                                                   const ofx_spmm_options* opts, size_t* bytes);
+int ofx_gatv2_scores_csr_heads_grad(void* stream, int idx_dtype, int val_dtype, int64_t m,
+                                    int64_t k, int64_t heads, int64_t d, int64_t nnz,
+                                    const void* row_ptr, const void* col_idx, const void* x_row,
+                                    int64_t ldr, const void* x_col, int64_t ldc, const void* att,
+                                    double negative_slope, const void* de /* [nnz, heads] */,
+                                    void* d_x, int64_t ldd, void* p /* NULL: not requested */,
+                                    int64_t ldp, int64_t row_begin, int64_t row_end,
+                                    void* workspace, size_t workspace_bytes,
+                                    const ofx_spmm_options* opts);
+int ofx_gatv2_scores_csr_heads_grad_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                        int64_t k, int64_t heads, int64_t d, int64_t nnz,
+                                        const void* row_ptr, const void* col_idx,
+                                        const void* x_row, int64_t ldr, const void* x_col,
+                                        int64_t ldc, const void* att, double negative_slope,
+                                        const void* de, void* d_x, int64_t ldd, void* p,
+                                        int64_t ldp, int64_t row_begin, int64_t row_end,
+                                        const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -1139,6 +1224,28 @@ int ofx_functional_gat_softmax_csr_heads_grad(void* stream, const ofx_tensor_des
                                               double negative_slope, ofx_tensor_desc* ds,
                                               ofx_tensor_desc* d_row, void* tmp, size_t tmp_bytes,
                                               size_t* tmp_size_out);
+/* functional::Gatv2ScoresCsrHeads / Gatv2ScoresCsrHeadsGrad: ops "gatv2_scores_csr_heads" (row_ptr
+ * [M+1], col_idx [nnz], x_row [M, H*D], x_col [K, H*D], att [H*D]; attrs num_heads,
+ * negative_slope -> out [nnz, H]) and "gatv2_scores_csr_heads_grad" (+ dy [nnz, H]; attr with_att
+ * -> d_x [M, H*D], p [M, H*D], or p [0, H*D] with with_att == 0) of
+ * oneflow/user/ops/gatv2_scores_heads_op.cpp through the op-registry dispatch; the contract of
+ * ofx_gatv2_scores_csr_heads(_grad).  tmp_size_out != NULL: only the tmp size is computed.       */
+int ofx_functional_gatv2_scores_csr_heads(void* stream, const ofx_tensor_desc* row_ptr,
+                                          const ofx_tensor_desc* col_idx,
+                                          const ofx_tensor_desc* x_row,
+                                          const ofx_tensor_desc* x_col,
+                                          const ofx_tensor_desc* att, int64_t num_heads,
+                                          double negative_slope, ofx_tensor_desc* out, void* tmp,
+                                          size_t tmp_bytes, size_t* tmp_size_out);
+int ofx_functional_gatv2_scores_csr_heads_grad(void* stream, const ofx_tensor_desc* row_ptr,
+                                               const ofx_tensor_desc* col_idx,
+                                               const ofx_tensor_desc* x_row,
+                                               const ofx_tensor_desc* x_col,
+                                               const ofx_tensor_desc* att,
+                                               const ofx_tensor_desc* dy, int64_t num_heads,
+                                               double negative_slope, int64_t with_att,
+                                               ofx_tensor_desc* d_x, ofx_tensor_desc* p, void* tmp,
+                                               size_t tmp_bytes, size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

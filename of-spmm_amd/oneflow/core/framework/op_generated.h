@@ -182,6 +182,28 @@ class GatSoftmaxCsrHeadsGradOp {
                                     const user_op::UserOpConfWrapper& conf);
 };
 
+// The attention scores of a GATv2 layer (LeakyReLU between the gather and the dot product) and
+// their gradient op (oneflow/user/ops/gatv2_scores_heads_op.cpp).
+class Gatv2ScoresCsrHeadsOp {
+ public:
+  static Maybe<void> InferLogicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> InferPhysicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> GetSbp(user_op::SbpContext* ctx);
+  static Maybe<void> InferDataType(user_op::InferContext* ctx);
+  static Maybe<void> ModifyInputArg(const user_op::GetInputArgModifier& GetInputArgModifierFn,
+                                    const user_op::UserOpConfWrapper& conf);
+};
+
+class Gatv2ScoresCsrHeadsGradOp {
+ public:
+  static Maybe<void> InferLogicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> InferPhysicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> GetSbp(user_op::SbpContext* ctx);
+  static Maybe<void> InferDataType(user_op::InferContext* ctx);
+  static Maybe<void> ModifyInputArg(const user_op::GetInputArgModifier& GetInputArgModifierFn,
+                                    const user_op::UserOpConfWrapper& conf);
+};
+
 // The S(0) -> B collectives the row-split op's B operand goes through: eager boxing
 // (oneflow/user/ops/eager_nccl_ops.cpp:188-233) and the lazy graph's logical collective
 // (oneflow/user/ops/nccl_logical_ops.cpp:104-142, ODS OneFlowUserOps.td:5341-5357).

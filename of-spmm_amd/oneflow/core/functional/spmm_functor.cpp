@@ -859,6 +859,49 @@ extern "C" int ofx_functional_gat_softmax_csr_heads_grad(
   });
 }
 
+// ---- functional::Gatv2ScoresCsrHeads and its gradient functor -----------------------------------
+// Ops "gatv2_scores_csr_heads" and "gatv2_scores_csr_heads_grad"
+// (oneflow/user/ops/gatv2_scores_heads_op.cpp) through the same op-registry dispatch
+// (INTEGRATION.md §14).
+extern "C" int ofx_functional_gatv2_scores_csr_heads(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* x_row, const ofx_tensor_desc* x_col, const ofx_tensor_desc* att,
+    int64_t num_heads, double negative_slope, ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+    size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(x_row != nullptr && x_col != nullptr && att != nullptr, OFX_EINVAL,
+                "gatv2_scores_csr_heads: NULL input x_row, x_col or att");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("gatv2_scores_csr_heads");
+    return ToStatus(RunUserOp(
+        "gatv2_scores_csr_heads",
+        {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"x_row", x_row},
+         {"x_col", x_col}, {"att", att}},
+        {{"out", out}},
+        {{"num_heads", num_heads}, {"negative_slope", user_op::AttrBits<double>(negative_slope)}},
+        stream, tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
+extern "C" int ofx_functional_gatv2_scores_csr_heads_grad(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* x_row, const ofx_tensor_desc* x_col, const ofx_tensor_desc* att,
+    const ofx_tensor_desc* dy, int64_t num_heads, double negative_slope, int64_t with_att,
+    ofx_tensor_desc* d_x, ofx_tensor_desc* p, void* tmp, size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(x_row != nullptr && x_col != nullptr && att != nullptr && dy != nullptr,
+                OFX_EINVAL, "gatv2_scores_csr_heads_grad: NULL input x_row, x_col, att or dy");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("gatv2_scores_csr_heads_grad");
+    return ToStatus(RunUserOp(
+        "gatv2_scores_csr_heads_grad",
+        {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"x_row", x_row},
+         {"x_col", x_col}, {"att", att}, {"dy", dy}},
+        {{"d_x", d_x}, {"p", p}},
+        {{"num_heads", num_heads}, {"negative_slope", user_op::AttrBits<double>(negative_slope)},
+         {"with_att", with_att != 0 ? 1 : 0}},
+        stream, tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
 // ---- functional::GraphAttentionCsrHeads ----------------------------------------------------------
 // Op "graph_attention_csr_heads" (oneflow/user/ops/graph_attention_heads_op.cpp) through the same
 // op-registry dispatch; two outputs.

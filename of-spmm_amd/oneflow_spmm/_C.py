@@ -594,6 +594,84 @@ def gat_softmax_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch
     return ds, d_row
 
 
+def _gatv2_inputs(op, rp, ci, x_row, x_col, att, num_heads):
+    """The prepared inputs of the GATv2 ops after the shape checks they share: x_row [M, H*D],
+    x_col [K, H*D] (row-strided views in place), att [H*D]."""
+    x_row, x_col = _prep(x_row, "x_row", matrix=True), _prep(x_col, "x_col", matrix=True)
+    att = _prep(att, "att")
+    _check_inputs(op, rp, ci, [("x_row", x_row), ("x_col", x_col)], 2, "x_col", False)
+    heads = int(num_heads)
+    if att.dim() != 1:
+        raise RuntimeError(f"{op}: att should be 1-D [heads * D], got shape {tuple(att.shape)}")
+    if att.dtype != x_col.dtype:
+        raise TypeError(f"{op}: att datatype should be equal to x_col ({att.dtype} vs "
+                        f"{x_col.dtype})")
+    if x_row.device != x_col.device or att.device != x_col.device:
+        raise RuntimeError(f"{op}: expected all tensors on the same device, got x_row on "
+                           f"{x_row.device}, x_col on {x_col.device} and att on {att.device}")
+    if heads < 1 or x_col.shape[1] % heads != 0:
+        raise RuntimeError(f"{op}: x_col's columns ({x_col.shape[1]}) should be a multiple of "
+                           f"num_heads ({heads})")
+    if x_row.shape[1] != x_col.shape[1] or att.shape[0] != x_col.shape[1]:
+        raise RuntimeError(f"{op}: x_row, x_col and att should have the same number of columns "
+                           f"({x_row.shape[1]}, {x_col.shape[1]}, {att.shape[0]})")
+    if x_row.shape[0] != rp.numel() - 1:
+        raise RuntimeError(f"{op}: x_row should have a_num_rows = {rp.numel() - 1} rows, got "
+                           f"{x_row.shape[0]}")
+    return x_row, x_col, att, heads
+
+
+def gatv2_scores_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                           x_row: torch.Tensor, x_col: torch.Tensor, att: torch.Tensor,
+                           num_heads: int, negative_slope: float = 0.2, *,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "gatv2_scores_csr_heads": out[j, h] = sum over c of att[h*D + c] *
+    LeakyReLU(x_row[row(j), h*D + c] + x_col[a_csr_col_idx[j], h*D + c]) for x_row [M, H*D],
+    x_col [K, H*D], att [H*D], H = num_heads, in one launch: exactly the bits of sddmm_csr_heads
+    on the activated sum rounded to the dtype, which is never written (contract in
+    include/ofx_spmm.h).  `out`: a contiguous [nnz, H] tensor, written directly.  negative_slope
+    must be finite and > 0."""
+    op = "gatv2_scores_csr_heads"
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
+    x_row, x_col, att, heads = _gatv2_inputs(op, rp, ci, x_row, x_col, att, num_heads)
+    out = _check_out(op, out, (ci.numel(), heads), x_col, contiguous=True)
+    if out.numel() == 0:
+        return out
+    if x_col.shape[1] == 0:  # empty inner dimension: every dot product is +0
+        return out.zero_()
+    _two_phase(LIB.ofx_functional_gatv2_scores_csr_heads, x_row,
+               _refs(rp, ci, x_row, x_col, att) + (heads, float(negative_slope)), _refs(out))
+    return out
+
+
+def gatv2_scores_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                                x_row: torch.Tensor, x_col: torch.Tensor, att: torch.Tensor,
+                                dy: torch.Tensor, num_heads: int, negative_slope: float = 0.2,
+                                with_att: bool = True):
+    """Op "gatv2_scores_csr_heads_grad": (d_x [M, H*D], p) from the upstream dy [nnz, H], one
+    launch: d_x is the gradient in x_row; p [M, H*D] (with_att; None otherwise) holds the per-row
+    terms whose column sum is the gradient in att.  Both are sums over the row's nonzeros in
+    spmm_csr_heads's order (+0 for an empty row)."""
+    op = "gatv2_scores_csr_heads_grad"
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
+    x_row, x_col, att, heads = _gatv2_inputs(op, rp, ci, x_row, x_col, att, num_heads)
+    dy = _prep(dy, "dy")
+    if dy.dim() != 2 or tuple(dy.shape) != (ci.numel(), heads):
+        raise RuntimeError(f"{op}: dy should be [nnz, heads] = ({ci.numel()}, {heads}), got shape "
+                           f"{tuple(dy.shape)}")
+    if dy.dtype != x_col.dtype or dy.device != x_col.device:
+        raise TypeError(f"{op}: dy datatype and device should be equal to x_col's ({dy.dtype} on "
+                        f"{dy.device} vs {x_col.dtype} on {x_col.device})")
+    m, n = x_row.shape
+    d_x = torch.empty((m, n), dtype=x_col.dtype, device=x_col.device)
+    p = torch.empty((m if with_att else 0, n), dtype=x_col.dtype, device=x_col.device)
+    if d_x.numel():
+        _two_phase(LIB.ofx_functional_gatv2_scores_csr_heads_grad, x_row,
+                   _refs(rp, ci, x_row, x_col, att, dy) +
+                   (heads, float(negative_slope), 1 if with_att else 0), _refs(d_x, p))
+    return d_x, (p if with_att else None)
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

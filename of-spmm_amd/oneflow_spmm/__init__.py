@@ -17,6 +17,10 @@ bits and the same gradients:
 The original GAT layer (additive scores s_row [M, H] + s_col [K, H], LeakyReLU, softmax) in one launch:
     w = flow_spmm.gat_softmax(row_ptr, col_idx, s_row, s_col, negative_slope=0.2)   # [nnz, H]
     out = flow_spmm.gat_attention(row_ptr, col_idx, s_row, s_col, v)                 # [M, H, D]
+GATv2 (x_row [M, H, D], x_col [K, H, D], att [H, D]; LeakyReLU between the gather and the dot product):
+    e = flow_spmm.gatv2_scores(row_ptr, col_idx, x_row, x_col, att, negative_slope=0.2)   # [nnz, H]
+    w = flow_spmm.gatv2_softmax(row_ptr, col_idx, x_row, x_col, att)                 # [nnz, H]
+    out = flow_spmm.gatv2_attention(row_ptr, col_idx, x_row, x_col, att)             # [M, H, D]
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 
@@ -26,9 +30,10 @@ from . import _C, _lib, autograd, build, ops, synth  # noqa: F401
 from ._C import spmm_csr, spmm_csr_reduce
 from ._lib import OfxError
 from .autograd import (csr_transpose, edge_softmax, fused_spmm, gat_attention, gat_softmax,
-                       graph_attention, sddmm, spmm, spmm_reduce)
+                       gatv2_attention, gatv2_scores, gatv2_softmax, graph_attention, sddmm, spmm,
+                       spmm_reduce)
 from .build import coo_to_csr
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "_C"]
+__all__ = ["spmm", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "_C"]

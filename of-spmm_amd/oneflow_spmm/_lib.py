@@ -216,6 +216,26 @@ def _load():
         "ofx_functional_gat_softmax_csr_heads_grad": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, pdesc,
                                                        ctypes.c_double, pdesc, pdesc, p, sz,
                                                        ctypes.POINTER(sz)], i32),
+        "ofx_gatv2_scores_csr_heads_workspace_size": ([i32, i32, i64, i64, i64, i64,
+                                                       ctypes.POINTER(sz)], i32),
+        "ofx_gatv2_scores_csr_heads": ([p, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64, p, i64,
+                                        p, ctypes.c_double, p, i64, i64, p, sz], i32),
+        "ofx_gatv2_scores_csr_heads_cpu": ([i32, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64, p,
+                                            i64, p, ctypes.c_double, p, i64, i64], i32),
+        "ofx_gatv2_scores_csr_heads_grad_workspace_size": ([i32, i32, i64, i64, i64, i64, i64, i32,
+                                                            popt, ctypes.POINTER(sz)], i32),
+        "ofx_gatv2_scores_csr_heads_grad": ([p, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64, p,
+                                             i64, p, ctypes.c_double, p, p, i64, p, i64, i64, i64,
+                                             p, sz, popt], i32),
+        "ofx_gatv2_scores_csr_heads_grad_cpu": ([i32, i32, i32, i64, i64, i64, i64, i64, p, p, p,
+                                                 i64, p, i64, p, ctypes.c_double, p, p, i64, p, i64,
+                                                 i64, i64, popt], i32),
+        "ofx_functional_gatv2_scores_csr_heads": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64,
+                                                   ctypes.c_double, pdesc, p, sz,
+                                                   ctypes.POINTER(sz)], i32),
+        "ofx_functional_gatv2_scores_csr_heads_grad": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, pdesc,
+                                                        i64, ctypes.c_double, i64, pdesc, pdesc, p,
+                                                        sz, ctypes.POINTER(sz)], i32),
         "ofx_graph_attention_csr_heads_workspace_size": ([i32, i32, i64, i64, i64, i64, i64, popt,
                                                           ctypes.POINTER(sz)], i32),
         "ofx_graph_attention_csr_heads": ([p, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64, p,

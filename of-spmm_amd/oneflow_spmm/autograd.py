@@ -530,6 +530,116 @@ def gat_attention(a_csr_row_ptr, a_csr_col_idx, s_row, s_col, v, negative_slope=
     return (out, attn) if return_attention else out
 
 
+class Gatv2ScoresFunction(torch.autograd.Function):
+    """e [nnz, H] = the GATv2 scores of x_row [M, H*D], x_col [K, H*D] and att [H*D] through op
+    "gatv2_scores_csr_heads", differentiable in all three.  The inputs are saved (no per-nonzero
+    tensor is); the backward is one launch of op "gatv2_scores_csr_heads_grad" on A (d(x_row), and
+    p only when att needs a gradient: d(att) is its column sum in relu_bias_grad's fixed order) and,
+    only when x_col needs a gradient, one on the cached transpose with x_row and x_col exchanged
+    and the upstream gradient gathered by the transpose's perm (deterministic, no atomics, the
+    same bits on CPU and GPU)."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, x_row, x_col, att, heads, negative_slope):
+        x_row, x_col, att = x_row.contiguous(), x_col.contiguous(), att.contiguous()
+        e = _C.gatv2_scores_csr_heads(row_ptr, col_idx, x_row, x_col, att, heads, negative_slope)
+        ctx.save_for_backward(row_ptr, col_idx, x_row, x_col, att)
+        ctx.heads, ctx.negative_slope = heads, negative_slope
+        return e
+
+    @staticmethod
+    def backward(ctx, d_e):
+        row_ptr, col_idx, x_row, x_col, att = ctx.saved_tensors
+        d_e = d_e.contiguous()
+        d_row = d_col = d_att = None
+        need_row, need_col, need_att = ctx.needs_input_grad[2:5]
+        if need_row or need_att:
+            d_row, p = _C.gatv2_scores_csr_heads_grad(row_ptr, col_idx, x_row, x_col, att, d_e,
+                                                      ctx.heads, ctx.negative_slope,
+                                                      with_att=need_att)
+            if need_att:
+                d_att = ops.relu_bias_grad(None, p, relu=False, bias_grad=True)[1]
+        if need_col:
+            rp_t, ci_t, _, de_t = TRANSPOSE_CACHE.transposed_values(row_ptr, col_idx, d_e,
+                                                                    x_col.shape[0], "gather")
+            d_col, _ = _C.gatv2_scores_csr_heads_grad(rp_t, ci_t, x_col, x_row, att, de_t,
+                                                      ctx.heads, ctx.negative_slope,
+                                                      with_att=False)
+        return None, None, d_row if need_row else None, d_col, d_att, None, None
+
+
+def _gatv2_forms(op, x_row, x_col, att):
+    """(x_row [M, H*D], x_col [K, H*D], att [H*D], H, D, flat) of the public GATv2 entries'
+    3-D form (x [rows, H, D], att [H, D]) or 2-D form (x [rows, D], att [D]: H = 1, flat)."""
+    flat = x_row.dim() == 2
+    if x_row.dim() != x_col.dim() or x_row.dim() not in (2, 3) or att.dim() != x_row.dim() - 1:
+        raise RuntimeError(f"{op}: x_row [M, H, D], x_col [K, H, D] and att [H, D] (or x_row "
+                           f"[M, D], x_col [K, D] and att [D]) are expected, got "
+                           f"{tuple(x_row.shape)}, {tuple(x_col.shape)} and {tuple(att.shape)}")
+    if x_row.shape[1:] != x_col.shape[1:] or att.shape != x_col.shape[1:]:
+        raise RuntimeError(f"{op}: x_row, x_col and att should agree in heads and D, got "
+                           f"{tuple(x_row.shape)}, {tuple(x_col.shape)} and {tuple(att.shape)}")
+    if x_row.dtype != x_col.dtype or att.dtype != x_col.dtype:
+        raise TypeError(f"{op}: x_row, x_col and att should have one dtype, got "
+                        f"{x_row.dtype}, {x_col.dtype}, {att.dtype}")
+    if x_row.device != x_col.device or att.device != x_col.device:
+        raise RuntimeError(f"{op}: expected all tensors on the same device, got "
+                           f"{x_row.device}, {x_col.device}, {att.device}")
+    heads = 1 if flat else x_col.shape[1]
+    d = x_col.shape[-1]
+    return (x_row.reshape(x_row.shape[0], heads * d), x_col.reshape(x_col.shape[0], heads * d),
+            att.reshape(heads * d), heads, d, flat)
+
+
+def gatv2_scores(a_csr_row_ptr, a_csr_col_idx, x_row, x_col, att, negative_slope=0.2, *, out=None):
+    """The attention scores of a GATv2 layer over a CSR, in one launch:
+        e[j, h] = sum over d of att[h, d] * LeakyReLU(x_row[row(j), h, d] + x_col[col[j], h, d])
+    for x_row [M, H, D] (W_l h_i per destination), x_col [K, H, D] (W_r h_j per source) and
+    att [H, D]; 2-D x_row [M, D], x_col [K, D] and 1-D att [D] mean H = 1 and return e [nnz].  The
+    activated sum is rounded to the dtype and never written: e has exactly the bits of
+    `sddmm(rp, arange(nnz), att repeated, U)` on it, on CPU and GPU tensors.
+    negative_slope must be finite and > 0.  Differentiable in x_row, x_col and att; the gradient
+    in x_col (one launch on the cached transpose) is built only when it is needed.  `out=` (a
+    contiguous [nnz, H] tensor, [nnz] for the 2-D form) only when no gradient is being recorded.
+    A column index outside [0, K) reads x_col as +0."""
+    xr, xc, w, heads, _, flat = _gatv2_forms("gatv2_scores", x_row, x_col, att)
+    negative_slope = float(negative_slope)
+    if _recording("gatv2_scores", out, x_row, x_col, att):
+        e = Gatv2ScoresFunction.apply(a_csr_row_ptr, a_csr_col_idx, xr, xc, w, heads,
+                                      negative_slope)
+        return e.squeeze(1) if flat else e
+    if flat and out is not None:
+        if out.dim() != 1 or not out.is_contiguous():
+            raise RuntimeError("gatv2_scores: out must be a contiguous [nnz] tensor for the 2-D "
+                               f"form, got {tuple(out.shape)}")
+        _C.gatv2_scores_csr_heads(a_csr_row_ptr, a_csr_col_idx, xr, xc, w, heads, negative_slope,
+                                  out=out.unsqueeze(1))
+        return out
+    e = _C.gatv2_scores_csr_heads(a_csr_row_ptr, a_csr_col_idx, xr, xc, w, heads, negative_slope,
+                                  out=out)
+    return e.squeeze(1) if flat else e
+
+
+def gatv2_softmax(a_csr_row_ptr, a_csr_col_idx, x_row, x_col, att, negative_slope=0.2):
+    """The attention weights of a GATv2 layer: edge_softmax(rp, ci, gatv2_scores(...)), [nnz, H]
+    ([nnz] for the 2-D form).  Plain composition: the bits and gradients of the two ops."""
+    return edge_softmax(a_csr_row_ptr, a_csr_col_idx,
+                        gatv2_scores(a_csr_row_ptr, a_csr_col_idx, x_row, x_col, att,
+                                     negative_slope))
+
+
+def gatv2_attention(a_csr_row_ptr, a_csr_col_idx, x_row, x_col, att, negative_slope=0.2, *,
+                    v=None, return_attention=False):
+    """A GATv2 layer's aggregation: out = spmm(rp, ci, gatv2_softmax(rp, ci, x_row, x_col, att,
+    negative_slope), M, K, v) with v = x_col unless given ([K, H, D'] or, for the 2-D form,
+    [K, D']).  Plain composition of the three ops: their bits and their gradients.  Returns out,
+    or (out, attn) with return_attention=True."""
+    attn = gatv2_softmax(a_csr_row_ptr, a_csr_col_idx, x_row, x_col, att, negative_slope)
+    out = spmm(a_csr_row_ptr, a_csr_col_idx, attn, x_row.shape[0], x_col.shape[0],
+               x_col if v is None else v)
+    return (out, attn) if return_attention else out
+
+
 class SpmmCsrReduceFunction(torch.autograd.Function):
     """(out, arg) = spmm_csr_reduce(..., reduce) for reduce in {"mean", "max", "min"},
     differentiable in `a_csr_values` and `b`; `arg` is not differentiable.
@@ -658,4 +768,5 @@ __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm",
            "FusedSpmmCsrFunction", "fused_spmm", "SpmmCsrReduceFunction", "spmm_reduce",
            "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax", "SpmmCsrHeadsFunction",
            "SddmmCsrHeadsFunction", "EdgeSoftmaxHeadsFunction", "GatSoftmaxFunction", "gat_softmax",
-           "gat_attention"]
+           "gat_attention", "Gatv2ScoresFunction", "gatv2_scores", "gatv2_softmax",
+           "gatv2_attention"]

@@ -303,6 +303,66 @@ def graph_attention_csr_heads(row_ptr, col_idx, q, k_mat, v, m, k, heads, *, out
     return out, attn
 
 
+def gatv2_scores_csr_heads(row_ptr, col_idx, x_row, x_col, att, m, k, heads, negative_slope=0.2, *,
+                           out=None, row_begin=0, row_end=None, num_threads: int = 0,
+                           workspace_bytes: int | None = None):
+    """The GATv2 scores at the C-ABI (ofx_gatv2_scores_csr_heads on device tensors, the kCPU kernel
+    ofx_gatv2_scores_csr_heads_cpu on host tensors): x_row holds rows [row_begin, row_end) of the
+    destination features, x_col is [K, heads * D] (unit column stride both), att [heads * D] ->
+    out [nnz, heads]; a row range writes its own nonzeros' rows of it."""
+    row_end = m if row_end is None else row_end
+    n, nnz = x_col.shape[1], col_idx.numel()
+    d = n // heads if heads else 0
+    if out is None:
+        out = torch.empty((nnz, heads), dtype=x_col.dtype, device=x_col.device)
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(x_col.dtype)
+    body = (idt, vdt, m, k, heads, d, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(x_row),
+            x_row.stride(0), _nz(x_col), x_col.stride(0), _nz(att), float(negative_slope), _nz(out),
+            row_begin, row_end)
+    if x_col.device.type == "cpu":
+        check(LIB.ofx_gatv2_scores_csr_heads_cpu(int(num_threads), *body),
+              "gatv2_scores_csr_heads_cpu")
+        return out
+    wbuf, ws = _workspace(x_col.device, "gatv2_scores_csr_heads",
+                          LIB.ofx_gatv2_scores_csr_heads_workspace_size, idt, vdt, m, heads, d,
+                          nnz, workspace_bytes=workspace_bytes)
+    check(LIB.ofx_gatv2_scores_csr_heads(current_stream_handle(x_col), *body, wbuf.data_ptr(), ws),
+          "gatv2_scores_csr_heads")
+    return out
+
+
+def gatv2_scores_csr_heads_grad(row_ptr, col_idx, x_row, x_col, att, de, m, k, heads,
+                                negative_slope=0.2, *, with_att=True, d_x=None, p=None,
+                                row_begin=0, row_end=None, options: Options | None = None,
+                                num_threads: int = 0, workspace_bytes: int | None = None):
+    """The gradient of the GATv2 scores at the C-ABI (ofx_gatv2_scores_csr_heads_grad /
+    ofx_gatv2_scores_csr_heads_grad_cpu by device): de [nnz, heads] -> (d_x, p), both
+    [row_end - row_begin, heads * D]; p is None unless with_att (or a p is passed)."""
+    row_end = m if row_end is None else row_end
+    n, nnz = x_col.shape[1], col_idx.numel()
+    d = n // heads if heads else 0
+    if d_x is None:
+        d_x = torch.empty((row_end - row_begin, n), dtype=x_col.dtype, device=x_col.device)
+    if p is None and with_att:
+        p = torch.empty((row_end - row_begin, n), dtype=x_col.dtype, device=x_col.device)
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(x_col.dtype)
+    popt = ctypes.byref(options) if options else None
+    body = (idt, vdt, m, k, heads, d, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(x_row),
+            x_row.stride(0), _nz(x_col), x_col.stride(0), _nz(att), float(negative_slope), _nz(de),
+            _nz(d_x), d_x.stride(0), _nz(p), p.stride(0) if p is not None else n, row_begin,
+            row_end)
+    if x_col.device.type == "cpu":
+        check(LIB.ofx_gatv2_scores_csr_heads_grad_cpu(int(num_threads), *body, popt),
+              "gatv2_scores_csr_heads_grad_cpu")
+        return d_x, p
+    wbuf, ws = _workspace(x_col.device, "gatv2_scores_csr_heads_grad",
+                          LIB.ofx_gatv2_scores_csr_heads_grad_workspace_size, idt, vdt, m, k, heads,
+                          d, nnz, 1 if p is not None else 0, popt, workspace_bytes=workspace_bytes)
+    check(LIB.ofx_gatv2_scores_csr_heads_grad(current_stream_handle(x_col), *body, wbuf.data_ptr(),
+                                              ws, popt), "gatv2_scores_csr_heads_grad")
+    return d_x, p
+
+
 def validate_csr(row_ptr, col_idx, m, k) -> int:
     """Device-side CSR check; returns 0 ok, 1 bad row_ptr, 2 column out of range (syncs)."""
     flag = torch.zeros(1, dtype=torch.int32, device=row_ptr.device)
@@ -330,5 +390,6 @@ def csr_row_slice(row_ptr, row_begin: int, row_end: int):
 
 __all__ = ["make_options", "default_split", "workspace_size", "SpmmCsrKernel", "spmm_csr_device",
            "describe",
-           "spmm_csr_gathered", "spmm_csr_heads", "sddmm_csr_heads",
+           "spmm_csr_gathered", "spmm_csr_heads", "sddmm_csr_heads", "gatv2_scores_csr_heads",
+           "gatv2_scores_csr_heads_grad",
            "spmm_csr_cpu", "validate_csr", "csr_row_slice", "INT64_MAX", "_lib"]

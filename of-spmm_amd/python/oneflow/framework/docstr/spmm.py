@@ -112,3 +112,54 @@ add_docstr(
 
     """,
 )
+
+add_docstr(
+    oneflow._C.gatv2_scores_csr_heads,
+    r"""
+    gatv2_scores_csr_heads(a_csr_row_ptr, a_csr_col_idx, x_row, x_col, att, num_heads, negative_slope=0.2) -> Tensor
+
+    The attention scores of a GATv2 layer over a CSR pattern, in one launch:
+
+    .. math::
+
+        e_{j,h} = \sum_d att_{h,d} \cdot \mathrm{LeakyReLU}(x\_row_{row(j),h,d} + x\_col_{col_j,h,d})
+
+    The activation sits between the gather and the dot product, so the score is neither a bilinear
+    SDDMM nor a per-node scalar; the activated sum is rounded to the dtype and never written.
+
+    Args:
+        a_csr_row_ptr (Tensor): ``[M + 1]``, int32 or int64.
+        a_csr_col_idx (Tensor): ``[nnz]``, the dtype of ``a_csr_row_ptr``.  A column outside
+            ``[0, K)`` reads ``x_col`` as ``+0``.
+        x_row (Tensor): ``[M, num_heads * D]``, the transformed destination features.
+        x_col (Tensor): ``[K, num_heads * D]``, the transformed source features.
+        att (Tensor): ``[num_heads * D]``, the attention vector of every head.
+        num_heads (int): the number of heads; head ``h`` owns columns ``[h * D, (h + 1) * D)``.
+        negative_slope (float): LeakyReLU's slope, finite and ``> 0``.
+
+    Returns:
+        ``out`` of shape ``[nnz, num_heads]``: exactly the bits of ``sddmm_csr_heads`` with the left
+        row ``att`` and the right row the activated sum of the nonzero, identical on CPU and GPU.
+
+    Differentiable in ``x_row``, ``x_col`` and ``att``.  The gradients are deterministic sums in the
+    order of ``spmm_csr_heads`` (the one in ``x_col`` on :math:`A^T`), without atomics.  The
+    softmax over each row (``edge_softmax_csr_heads``) and the aggregation (``spmm_csr_heads``) are
+    separate ops.
+
+    For example:
+
+    .. code-block:: python
+
+        >>> import oneflow as flow
+        >>> row_ptr = flow.tensor([0, 2, 3], dtype=flow.int32)
+        >>> col_idx = flow.tensor([0, 1, 1], dtype=flow.int32)
+        >>> x_row = flow.tensor([[1.0, -1.0], [0.5, 0.5]])
+        >>> x_col = flow.tensor([[1.0, 0.0], [-2.0, 0.0]])
+        >>> att = flow.tensor([1.0, 1.0])
+        >>> flow._C.gatv2_scores_csr_heads(row_ptr, col_idx, x_row, x_col, att, 1, 0.5)
+        tensor([[ 1.5000],
+                [-1.0000],
+                [-0.2500]], dtype=oneflow.float32)
+
+    """,
+)
