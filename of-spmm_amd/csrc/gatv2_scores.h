@@ -54,14 +54,11 @@ static inline int check_gatv2_args(const char* fn, bool grad, int idx_dtype, int
                                    double negative_slope, const void* de, const void* out,
                                    int64_t ldo, const void* p, int64_t ldp, int64_t row_begin,
                                    int64_t row_end, const ofx_spmm_options* opts, bool* nothing) {
-  OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d), OFX_EINVAL,
-              "%s: bad heads=%lld / d=%lld", fn, (long long)heads, (long long)d);
+  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
   if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
   OFX_REQUIRE(heads == 0 || nnz <= INT64_MAX / heads, OFX_EINVAL, "%s: bad heads=%lld for nnz=%lld",
               fn, (long long)heads, (long long)nnz);
-  OFX_REQUIRE(!grad || (opts->planned == 0 && opts->variant == 0), OFX_EINVAL,
-              "%s: options planned=%d / variant=%d are not supported (plan-once and the tuning "
-              "variants belong to spmm_csr)", fn, (int)opts->planned, (int)opts->variant);
+  if (const int rc = grad ? check_no_plan_options(fn, opts) : OFX_OK) return rc;
   if (const int rc = check_row_range(fn, row_begin, row_end, m)) return rc;
   if (const int rc = gsm::check_slope(fn, val_dtype, negative_slope)) return rc;
   const int64_t n = heads * d, nrows = row_end - row_begin;

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gatv2_scores.h"
+#include "heads_steps.h"  // the lane ladder
 #include "spmm_extremum.h"
 #include "spmm_items_dev.h"
 
@@ -222,19 +223,9 @@ int grad_cfg(const GradArgs& a) {
                        p.wl.counters, p.wl.items, p.wl.order, part1, part2, b0, p.err);
   });
   if (rc) return rc;
-  if (!p.has_plan || p.w.max_hubs == 0) return OFX_OK;
-  const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
-  hipLaunchKernelGGL((hub_sum_kernel<T>), dim3(hgrid), dim3(kBlock), 0, a.s, p.wl.counters,
-                     p.wl.hubs, static_cast<const A*>(part1), static_cast<T*>(a.dx), a.ldd,
-                     a.nrows, n);
-  OFX_HIP_CHECK(hipGetLastError());
-  if constexpr (WITH_P) {
-    hipLaunchKernelGGL((hub_sum_kernel<T>), dim3(hgrid), dim3(kBlock), 0, a.s, p.wl.counters,
-                       p.wl.hubs, static_cast<const A*>(part2), static_cast<T*>(a.p), a.ldp,
-                       a.nrows, n);
-    OFX_HIP_CHECK(hipGetLastError());
-  }
-  return OFX_OK;
+  rc = launch_hub_sum<T>(a.s, p, part1, static_cast<T*>(a.dx), a.ldd, a.nrows, n);
+  if (rc || !WITH_P) return rc;
+  return launch_hub_sum<T>(a.s, p, part2, static_cast<T*>(a.p), a.ldp, a.nrows, n);
 }
 
 // One layout per width class: the lanes of a group cover the H*D columns in one tile up to
@@ -242,12 +233,9 @@ int grad_cfg(const GradArgs& a) {
 template <typename T, typename I, bool HEADVEC, bool WITH_P>
 int grad_width(const GradArgs& a) {
   constexpr int VEC = 16 / sizeof(T);
-  const int64_t lanes = (a.heads * a.d + VEC - 1) / VEC;
-  if (lanes <= 1) return grad_cfg<T, I, VEC, 1, HEADVEC, WITH_P>(a);
-  if (lanes <= 4) return grad_cfg<T, I, VEC, 4, HEADVEC, WITH_P>(a);
-  if (lanes <= 16) return grad_cfg<T, I, VEC, 16, HEADVEC, WITH_P>(a);
-  if (lanes <= 32) return grad_cfg<T, I, VEC, 32, HEADVEC, WITH_P>(a);
-  return grad_cfg<T, I, VEC, 64, HEADVEC, WITH_P>(a);
+  return hsteps::by_lane_group((a.heads * a.d + VEC - 1) / VEC, [&](auto lpr) -> int {
+    return grad_cfg<T, I, VEC, decltype(lpr)::value, HEADVEC, WITH_P>(a);
+  });
 }
 
 template <typename T, typename I>
@@ -285,12 +273,11 @@ extern "C" int ofx_gatv2_scores_csr_heads_grad_workspace_size(int idx_dtype, int
     const char* fn = "gatv2_scores_csr_heads_grad_workspace_size";
     OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "%s: bytes is NULL", fn);
     OFX_READ_OPTIONS(opts, "gatv2_scores_csr_heads_grad_workspace_size");
+    // two planes of partials: 2 * heads * d is representable too
     OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d / 2), OFX_EINVAL,
                 "%s: bad heads=%lld / d=%lld", fn, (long long)heads, (long long)d);
     if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
-    OFX_REQUIRE(opts->planned == 0 && opts->variant == 0, OFX_EINVAL,
-                "%s: options planned=%d / variant=%d are not supported (plan-once and the tuning "
-                "variants belong to spmm_csr)", fn, (int)opts->planned, (int)opts->variant);
+    if (const int rc = check_no_plan_options(fn, opts)) return rc;
     *bytes = grad_ws_bytes(m, nnz, heads * d, d, with_p != 0, val_dtype, opts);
     return OFX_OK;
   });
@@ -314,9 +301,9 @@ extern "C" int ofx_gatv2_scores_csr_heads_grad(
     if (nothing) return OFX_OK;
     const int64_t nrows = row_end - row_begin;
     const size_t need = grad_ws_bytes(nrows, nnz, heads * d, d, p != nullptr, val_dtype, opts);
-    OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
-                "gatv2_scores_csr_heads_grad: workspace of %zu bytes is smaller than the %zu bytes "
-                "required", workspace_bytes, need);
+    if (const int rc =
+            check_workspace("gatv2_scores_csr_heads_grad", workspace, workspace_bytes, need))
+      return rc;
     const GradArgs a{static_cast<hipStream_t>(stream), row_ptr, col_idx, x_row, x_col, att, de,
                      d_x, p, ldr, ldc, ldd, ldp, m, row_begin, nrows, heads, d, nnz,
                      x_col ? k : 0, negative_slope, workspace, workspace_bytes, opts};

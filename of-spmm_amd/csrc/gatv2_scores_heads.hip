@@ -27,9 +27,7 @@ namespace ofx {
 namespace {
 
 using namespace item;
-using namespace hsteps;  // kLeaf, kMaxHeadsN, load_leaf (heads_steps.h)
-
-constexpr int64_t kHeadsChunk = 256;  // items of at most this many nonzeros (work only)
+using namespace hsteps;  // load_leaf, the layout ladder and the schedule (heads_steps.h)
 
 // The scores of nonzeros [j0, j1) of the row `xrow` by a group of LG lanes (gl: the lane in the
 // group, gbase: the group's first lane), out[j * heads + h] rounded to T.  FAST / !FAST as
@@ -167,21 +165,6 @@ __device__ __forceinline__ void gatv2_scores_item(const I* __restrict__ col,
   }
 }
 
-template <typename T, typename I>
-__device__ __forceinline__ bool poison_head_nonzeros(const unsigned long long* __restrict__ counters,
-                                                     int64_t block_base, unsigned* err,
-                                                     const I* __restrict__ rp, int64_t row_begin,
-                                                     int64_t nrows, int64_t heads,
-                                                     T* __restrict__ out) {
-  if (!plan_failed(counters, block_base, err)) return false;
-  const int64_t e0 = (int64_t)rp[row_begin] * heads, e1 = (int64_t)rp[row_begin + nrows] * heads;
-  const T p = poison_value<T>();
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = e0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < e1; e += stride)
-    out[e] = p;
-  return true;
-}
-
 // FAST: the group covers the n = H*D columns of an item, a head is `lh` = D/8 leaves (a power of
 // two).  !FAST: group index = item * H + head; the group covers the head's D columns.
 template <typename T, typename I, int LG, int L, int U, bool FAST>
@@ -220,16 +203,10 @@ struct Gv2Args {
   size_t ws_bytes;
 };
 
-// Work layout only (every e[j, h] is its own dot product): the multi-head SDDMM's items.
-Schedule scores_schedule() {
-  Schedule s = resolve_schedule(1, nullptr);
-  s.split = s.chunk = kHeadsChunk;
-  return s;
-}
-
 template <typename T, typename I, int LG, int L, bool FAST>
-int gv2_cfg(const Gv2Args& x, int lh) {
+int gv2_cfg(const Gv2Args& x) {
   using A = typename Num<T>::acc;
+  const int lh = FAST ? (int)(x.d / kLeaf) : 0;
   // loads in flight per lane: four leaves' worth; an f64 lane of four leaves holds x_row's and
   // att's 64 registers each, so it streams one nonzero at a time
   constexpr int U = L >= 4 ? (sizeof(T) == 8 ? 1 : 2) : (L == 2 && sizeof(T) == 8 ? 2 : 4);
@@ -251,31 +228,13 @@ int gv2_cfg(const Gv2Args& x, int lh) {
 
 template <typename T, typename I>
 int gv2_typed(const Gv2Args& x) {
-  const int64_t n = x.heads * x.d;
-  const int64_t lh = x.d / kLeaf;
-  // k == 0 (every column out of range) takes the general path: the fast one needs a row 0
-  const bool fast = x.d % kLeaf == 0 && (lh & (lh - 1)) == 0 && n <= kMaxHeadsN && x.k > 0 &&
+  const bool fast = fast_score_shape(x.heads, x.d, x.k) &&
                     rows_aligned(x.xr, x.ldr, sizeof(T), kLeaf) &&
                     rows_aligned(x.xc, x.ldc, sizeof(T), kLeaf) &&
-                    rows_aligned(x.att, n, sizeof(T), kLeaf);
-  if (fast) {
-    const int64_t leaves = n / kLeaf;
-    if (leaves <= 1) return gv2_cfg<T, I, 1, 1, true>(x, (int)lh);
-    if (leaves <= 2) return gv2_cfg<T, I, 2, 1, true>(x, (int)lh);
-    if (leaves <= 4) return gv2_cfg<T, I, 4, 1, true>(x, (int)lh);
-    if (leaves <= 8) return gv2_cfg<T, I, 8, 1, true>(x, (int)lh);
-    if (leaves <= 16) return gv2_cfg<T, I, 16, 1, true>(x, (int)lh);
-    if (leaves <= 32) return gv2_cfg<T, I, 32, 1, true>(x, (int)lh);
-    if (leaves <= 64) return gv2_cfg<T, I, 64, 1, true>(x, (int)lh);
-    if (leaves <= 128) return gv2_cfg<T, I, 64, 2, true>(x, (int)lh);
-    return gv2_cfg<T, I, 64, 4, true>(x, (int)lh);
-  }
-  const int64_t leaves = (x.d + kLeaf - 1) / kLeaf;
-  if (leaves <= 1) return gv2_cfg<T, I, 1, 1, false>(x, 0);
-  if (leaves <= 4) return gv2_cfg<T, I, 4, 1, false>(x, 0);
-  if (leaves <= 16) return gv2_cfg<T, I, 16, 1, false>(x, 0);
-  if (leaves <= 64) return gv2_cfg<T, I, 64, 1, false>(x, 0);
-  return gv2_cfg<T, I, 64, 4, false>(x, 0);
+                    rows_aligned(x.att, x.heads * x.d, sizeof(T), kLeaf);
+  return by_score_layout(fast, x.heads, x.d, [&](auto lg, auto l, auto f) -> int {
+    return gv2_cfg<T, I, decltype(lg)::value, decltype(l)::value, decltype(f)::value>(x);
+  });
 }
 
 }  // namespace
@@ -288,9 +247,8 @@ extern "C" int ofx_gatv2_scores_csr_heads_workspace_size(int idx_dtype, int val_
                                                          size_t* bytes) {
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "gatv2_scores_csr_heads_workspace_size: bytes is NULL");
-    OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d), OFX_EINVAL,
-                "gatv2_scores_csr_heads_workspace_size: bad heads=%lld / d=%lld", (long long)heads,
-                (long long)d);
+    if (const int rc = check_heads_shape("gatv2_scores_csr_heads_workspace_size", heads, d))
+      return rc;
     if (const int rc = check_types_sizes("gatv2_scores_csr_heads_workspace_size", idx_dtype,
                                          val_dtype, m, 0, heads * d, nnz))
       return rc;
@@ -316,9 +274,8 @@ extern "C" int ofx_gatv2_scores_csr_heads(void* stream, int idx_dtype, int val_d
       return rc;
     if (nothing) return OFX_OK;
     const size_t need = plan::ws_layout(row_end - row_begin, nnz, 0, 0, scores_schedule()).total;
-    OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
-                "gatv2_scores_csr_heads: workspace of %zu bytes is smaller than the %zu bytes "
-                "required", workspace_bytes, need);
+    if (const int rc = check_workspace("gatv2_scores_csr_heads", workspace, workspace_bytes, need))
+      return rc;
     const Gv2Args x{static_cast<hipStream_t>(stream), row_ptr, col_idx, x_row, x_col, att, e, ldr,
                     ldc, row_begin, row_end - row_begin, heads, d, nnz, x_col ? k : 0,
                     negative_slope, workspace, workspace_bytes};

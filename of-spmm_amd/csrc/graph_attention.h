@@ -35,14 +35,11 @@ static inline int check_graph_attention_args(const char* fn, int idx_dtype, int 
                                              const void* out, int64_t ldo, const void* attn,
                                              int64_t row_begin, int64_t row_end,
                                              const ofx_spmm_options* opts, Shape* sh) {
-  OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d), OFX_EINVAL,
-              "%s: bad heads=%lld / d=%lld", fn, (long long)heads, (long long)d);
+  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
   if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
   OFX_REQUIRE(heads == 0 || nnz <= INT64_MAX / heads, OFX_EINVAL, "%s: bad heads=%lld for nnz=%lld",
               fn, (long long)heads, (long long)nnz);
-  OFX_REQUIRE(opts->planned == 0 && opts->variant == 0, OFX_EINVAL,
-              "%s: options planned=%d / variant=%d are not supported (plan-once and the tuning "
-              "variants belong to spmm_csr)", fn, (int)opts->planned, (int)opts->variant);
+  if (const int rc = check_no_plan_options(fn, opts)) return rc;
   if (const int rc = check_row_range(fn, row_begin, row_end, m)) return rc;
   const int64_t n = heads * d;
   OFX_REQUIRE(ldq >= n && ldk >= n && ldv >= n && ldo >= n, OFX_EINVAL,

@@ -293,11 +293,7 @@ int gat_width(const GatArgs& a) {
 template <typename T, typename I>
 int gat_typed(const GatArgs& a) {
   constexpr int SV = esmh::packed_heads<T>();
-  const int64_t n = a.heads * a.d;
-  const int64_t lh = a.d / hsteps::kLeaf;
-  // K == 0 (every column out of range) takes the general path: the fast one needs a row 0
-  const bool fast = a.d % hsteps::kLeaf == 0 && (lh & (lh - 1)) == 0 && n <= hsteps::kMaxHeadsN &&
-                    a.kk > 0 && a.heads % SV == 0 &&
+  const bool fast = hsteps::fast_score_shape(a.heads, a.d, a.kk) && a.heads % SV == 0 &&
                     rows_aligned(a.q, a.ldq, sizeof(T), hsteps::kLeaf) &&
                     rows_aligned(a.k, a.ldk, sizeof(T), hsteps::kLeaf) &&
                     rows_aligned(a.v, a.ldv, sizeof(T), hsteps::kLeaf) &&
@@ -352,9 +348,9 @@ extern "C" int ofx_graph_attention_csr_heads(void* stream, int idx_dtype, int va
     if (sh.nothing) return OFX_OK;
     const size_t need = plan::ws_layout(sh.nrows, nnz, sh.n, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
                                         resolve_schedule(d, opts)).total;
-    OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
-                "graph_attention_csr_heads: workspace of %zu bytes is smaller than the %zu bytes "
-                "required", workspace_bytes, need);
+    if (const int rc =
+            check_workspace("graph_attention_csr_heads", workspace, workspace_bytes, need))
+      return rc;
     const GatArgs a{static_cast<hipStream_t>(stream), row_ptr, col_idx, q, kmat, v, out, attn, ldq,
                     ldk, ldv, ldo, k, m, row_begin, sh.nrows, heads, d, nnz, workspace,
                     workspace_bytes, opts};

@@ -3,7 +3,8 @@
 // a run of nonzeros into a lane's columns (spmm_heads.hip and phase 3 of
 // graph_attention_heads.hip).  Every unit takes these arithmetic steps from here, so the fused
 // kernel has the bits of the three ops' composition by construction (contract in
-// include/ofx_spmm.h).
+// include/ofx_spmm.h).  Below them, the host side those units and the GATv2
+// units share: the layout ladders, the fast path's shape test and the per-nonzero ops' schedule.
 // Included by HIP translation units only.
 #ifndef OFX_HEADS_STEPS_H_
 #define OFX_HEADS_STEPS_H_
@@ -243,6 +244,64 @@ __device__ __forceinline__ void spmm_heads_accumulate(
       }
     }
   }
+}
+
+// ---- host side: what the units' launch paths share (none of it reaches a kernel) --
+
+constexpr int64_t kHeadsChunk = 256;  // items of at most this many nonzeros (work only)
+
+// The schedule of the ops with one output per (nonzero, head): work layout only (every output is
+// its own dot product), the narrow SDDMM's items.
+inline Schedule scores_schedule() {
+  Schedule s = resolve_schedule(1, nullptr);
+  s.split = s.chunk = kHeadsChunk;
+  return s;
+}
+
+// The shape a score kernel's fast path needs (each user adds rows_aligned of its own operands).
+// k == 0 (every column out of range) takes the general path: the fast one needs a row 0.
+inline bool fast_score_shape(int64_t heads, int64_t d, int64_t k) {
+  const int64_t lh = d / kLeaf;
+  return d % kLeaf == 0 && (lh & (lh - 1)) == 0 && heads * d <= kMaxHeadsN && k > 0;
+}
+
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// The LG x L table of the score kernels (sddmm_heads_item and its like): f(LG, L, FAST) as
+// integral constants, in the style of by_types.  Fast: the group covers the H*D / 8 leaves of the
+// row.  General: the ceil(D / 8) leaves of one head.
+template <typename F>
+int by_score_layout(bool fast, int64_t heads, int64_t d, F&& f) {
+  if (fast) {
+    const int64_t leaves = heads * d / kLeaf;
+    if (leaves <= 1) return f(Int<1>{}, Int<1>{}, std::true_type{});
+    if (leaves <= 2) return f(Int<2>{}, Int<1>{}, std::true_type{});
+    if (leaves <= 4) return f(Int<4>{}, Int<1>{}, std::true_type{});
+    if (leaves <= 8) return f(Int<8>{}, Int<1>{}, std::true_type{});
+    if (leaves <= 16) return f(Int<16>{}, Int<1>{}, std::true_type{});
+    if (leaves <= 32) return f(Int<32>{}, Int<1>{}, std::true_type{});
+    if (leaves <= 64) return f(Int<64>{}, Int<1>{}, std::true_type{});
+    if (leaves <= 128) return f(Int<64>{}, Int<2>{}, std::true_type{});
+    return f(Int<64>{}, Int<4>{}, std::true_type{});
+  }
+  const int64_t leaves = (d + kLeaf - 1) / kLeaf;
+  if (leaves <= 1) return f(Int<1>{}, Int<1>{}, std::false_type{});
+  if (leaves <= 4) return f(Int<4>{}, Int<1>{}, std::false_type{});
+  if (leaves <= 16) return f(Int<16>{}, Int<1>{}, std::false_type{});
+  if (leaves <= 64) return f(Int<64>{}, Int<1>{}, std::false_type{});
+  return f(Int<64>{}, Int<4>{}, std::false_type{});
+}
+
+// The lane group of the row-output kernels (spmm_heads_accumulate and its like): f(LPR) for
+// `lanes` lanes of 16 bytes; a wider row loops over tiles of 64 lanes.
+template <typename F>
+int by_lane_group(int64_t lanes, F&& f) {
+  if (lanes <= 1) return f(Int<1>{});
+  if (lanes <= 4) return f(Int<4>{});
+  if (lanes <= 16) return f(Int<16>{});
+  if (lanes <= 32) return f(Int<32>{});
+  return f(Int<64>{});
 }
 
 }  // namespace

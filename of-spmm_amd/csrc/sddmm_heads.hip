@@ -32,24 +32,7 @@ namespace {
 
 using namespace item;
 
-using namespace hsteps;  // kLeaf, kMaxHeadsN, load_leaf and the item's scores (heads_steps.h)
-
-constexpr int64_t kHeadsChunk = 256;          // items of at most this many nonzeros (work only)
-
-template <typename T, typename I>
-__device__ __forceinline__ bool poison_head_nonzeros(const unsigned long long* __restrict__ counters,
-                                                     int64_t block_base, unsigned* err,
-                                                     const I* __restrict__ rp, int64_t row_begin,
-                                                     int64_t nrows, int64_t heads,
-                                                     T* __restrict__ out) {
-  if (!plan_failed(counters, block_base, err)) return false;
-  const int64_t e0 = (int64_t)rp[row_begin] * heads, e1 = (int64_t)rp[row_begin + nrows] * heads;
-  const T p = poison_value<T>();
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = e0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < e1; e += stride)
-    out[e] = p;
-  return true;
-}
+using namespace hsteps;  // the item's scores, the layout ladder and the schedule (heads_steps.h)
 
 // FAST: the group covers the n = H*D columns of an item, a head is `lh` = D/8 leaves (a power of
 // two).  !FAST: group index = item * H + head; the group covers the head's D columns.
@@ -87,20 +70,14 @@ struct SdHeadsArgs {
   size_t ws_bytes;
 };
 
-// Work layout only (every out[j, h] is its own dot product): the narrow SDDMM's items.
-Schedule sddmm_schedule() {
-  Schedule s = resolve_schedule(1, nullptr);
-  s.split = s.chunk = kHeadsChunk;
-  return s;
-}
-
 template <typename T, typename I, int LG, int L, bool FAST>
-int sd_heads_cfg(const SdHeadsArgs& x, int lh) {
+int sd_heads_cfg(const SdHeadsArgs& x) {
   constexpr int U = L >= 4 ? 2 : 4;
+  const int lh = FAST ? (int)(x.d / kLeaf) : 0;
   Planned p;
   if (const int rc = prepare_plan<I>("sddmm_csr_heads", x.s, static_cast<const I*>(x.rp),
                                      x.row_begin, x.nrows, x.nnz, x.nnz, 0, 0,
-                                     sddmm_schedule(), false, x.ws, x.ws_bytes, &p))
+                                     scores_schedule(), false, x.ws, x.ws_bytes, &p))
     return rc;
   const int64_t groups = FAST ? p.work : p.work * x.heads;
   return launch_cut_grid(groups, (kBlock / 64) * (64 / LG), [&](dim3 grid, int64_t b0) {
@@ -114,36 +91,17 @@ int sd_heads_cfg(const SdHeadsArgs& x, int lh) {
 
 template <typename T, typename I>
 int sd_heads_typed(const SdHeadsArgs& x) {
-  const int64_t n = x.heads * x.d;
-  const int64_t lh = x.d / kLeaf;
-  // k == 0 (every column out of range) takes the general path: the fast one needs a row 0
-  const bool fast = x.d % kLeaf == 0 && (lh & (lh - 1)) == 0 && n <= kMaxHeadsN && x.k > 0 &&
+  const bool fast = fast_score_shape(x.heads, x.d, x.k) &&
                     rows_aligned(x.a, x.lda, sizeof(T), kLeaf) &&
                     rows_aligned(x.b, x.ldb, sizeof(T), kLeaf);
-  if (fast) {
-    const int64_t leaves = n / kLeaf;
-    if (leaves <= 1) return sd_heads_cfg<T, I, 1, 1, true>(x, (int)lh);
-    if (leaves <= 2) return sd_heads_cfg<T, I, 2, 1, true>(x, (int)lh);
-    if (leaves <= 4) return sd_heads_cfg<T, I, 4, 1, true>(x, (int)lh);
-    if (leaves <= 8) return sd_heads_cfg<T, I, 8, 1, true>(x, (int)lh);
-    if (leaves <= 16) return sd_heads_cfg<T, I, 16, 1, true>(x, (int)lh);
-    if (leaves <= 32) return sd_heads_cfg<T, I, 32, 1, true>(x, (int)lh);
-    if (leaves <= 64) return sd_heads_cfg<T, I, 64, 1, true>(x, (int)lh);
-    if (leaves <= 128) return sd_heads_cfg<T, I, 64, 2, true>(x, (int)lh);
-    return sd_heads_cfg<T, I, 64, 4, true>(x, (int)lh);
-  }
-  const int64_t leaves = (x.d + kLeaf - 1) / kLeaf;
-  if (leaves <= 1) return sd_heads_cfg<T, I, 1, 1, false>(x, 0);
-  if (leaves <= 4) return sd_heads_cfg<T, I, 4, 1, false>(x, 0);
-  if (leaves <= 16) return sd_heads_cfg<T, I, 16, 1, false>(x, 0);
-  if (leaves <= 64) return sd_heads_cfg<T, I, 64, 1, false>(x, 0);
-  return sd_heads_cfg<T, I, 64, 4, false>(x, 0);
+  return by_score_layout(fast, x.heads, x.d, [&](auto lg, auto l, auto f) -> int {
+    return sd_heads_cfg<T, I, decltype(lg)::value, decltype(l)::value, decltype(f)::value>(x);
+  });
 }
 
 int check_sd_heads_args(const char* fn, int idx_dtype, int val_dtype, int64_t m, int64_t k,
                         int64_t heads, int64_t d, int64_t nnz) {
-  OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d), OFX_EINVAL,
-              "%s: bad heads=%lld / d=%lld", fn, (long long)heads, (long long)d);
+  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
   return check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz);
 }
 
@@ -160,7 +118,7 @@ extern "C" int ofx_sddmm_csr_heads_workspace_size(int idx_dtype, int val_dtype, 
     if (const int rc = check_sd_heads_args("sddmm_csr_heads_workspace_size", idx_dtype, val_dtype,
                                            m, 0, heads, d, nnz))
       return rc;
-    *bytes = plan::ws_layout(m, nnz, 0, 0, sddmm_schedule()).total;
+    *bytes = plan::ws_layout(m, nnz, 0, 0, scores_schedule()).total;
     return OFX_OK;
   });
 }
@@ -184,11 +142,8 @@ extern "C" int ofx_sddmm_csr_heads(void* stream, int idx_dtype, int val_dtype, i
                 "sddmm_csr_heads: d=%lld > %lld is not supported", (long long)d,
                 (long long)kMaxHeadsN);
     OFX_REQUIRE(row_ptr && col_idx && out && a && b, OFX_EINVAL, "sddmm_csr_heads: NULL pointer");
-    const size_t need =
-        plan::ws_layout(row_end - row_begin, nnz, 0, 0, sddmm_schedule()).total;
-    OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
-                "sddmm_csr_heads: workspace of %zu bytes is smaller than the %zu bytes required",
-                workspace_bytes, need);
+    const size_t need = plan::ws_layout(row_end - row_begin, nnz, 0, 0, scores_schedule()).total;
+    if ((rc = check_workspace("sddmm_csr_heads", workspace, workspace_bytes, need))) return rc;
     const SdHeadsArgs x{static_cast<hipStream_t>(stream), row_ptr, col_idx, a, b, out, lda, ldb,
                         row_begin, row_end - row_begin, heads, d, nnz, k, workspace,
                         workspace_bytes};

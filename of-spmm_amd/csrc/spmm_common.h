@@ -204,6 +204,30 @@ static inline int check_row_range(const char* fn, int64_t row_begin, int64_t row
   return OFX_OK;
 }
 
+// The multi-head entries: H heads of width D, n = H*D representable.
+static inline int check_heads_shape(const char* fn, int64_t heads, int64_t d) {
+  OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d), OFX_EINVAL,
+              "%s: bad heads=%lld / d=%lld", fn, (long long)heads, (long long)d);
+  return OFX_OK;
+}
+
+// Plan-once and the tuning variants belong to spmm_csr: every other entry that reads options
+// refuses them.
+static inline int check_no_plan_options(const char* fn, const ofx_spmm_options* opts) {
+  OFX_REQUIRE(opts->planned == 0 && opts->variant == 0, OFX_EINVAL,
+              "%s: options planned=%d / variant=%d are not supported (plan-once and the tuning "
+              "variants belong to spmm_csr)", fn, (int)opts->planned, (int)opts->variant);
+  return OFX_OK;
+}
+
+// The caller's workspace against the `need` bytes of the launch's layout.
+static inline int check_workspace(const char* fn, const void* ws, size_t ws_bytes, size_t need) {
+  OFX_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need), OFX_EWORKSPACE,
+              "%s: workspace of %zu bytes is smaller than the %zu bytes required", fn, ws_bytes,
+              need);
+  return OFX_OK;
+}
+
 // ---- schedule ---------------------------------------------------------------------------
 // Default split threshold: rows with more than T nonzeros are cut into chunks of T, where
 // T = clamp(65536 / n, 128, 512) rounded down to a power of two (T*n <= 64K multiply-adds

@@ -29,7 +29,7 @@ namespace ofx {
 namespace {
 
 using namespace item;
-using namespace hsteps;  // the accumulation of a run of nonzeros (heads_steps.h)
+using namespace hsteps;  // the accumulation of a run of nonzeros, the lane ladder (heads_steps.h)
 
 // HEADVEC: ALIGNED rows and D % VEC == 0 (one head per lane).
 template <typename T, typename I, int VEC, int LPR, int U, bool HEADVEC>
@@ -117,12 +117,9 @@ int heads_cfg(const HeadsArgs& a) {
 template <typename T, typename I, bool HEADVEC>
 int heads_width(const HeadsArgs& a) {
   constexpr int VEC = 16 / sizeof(T);
-  const int64_t lanes = (a.heads * a.d + VEC - 1) / VEC;
-  if (lanes <= 1) return heads_cfg<T, I, VEC, 1, HEADVEC>(a);
-  if (lanes <= 4) return heads_cfg<T, I, VEC, 4, HEADVEC>(a);
-  if (lanes <= 16) return heads_cfg<T, I, VEC, 16, HEADVEC>(a);
-  if (lanes <= 32) return heads_cfg<T, I, VEC, 32, HEADVEC>(a);
-  return heads_cfg<T, I, VEC, 64, HEADVEC>(a);
+  return by_lane_group((a.heads * a.d + VEC - 1) / VEC, [&](auto lpr) -> int {
+    return heads_cfg<T, I, VEC, decltype(lpr)::value, HEADVEC>(a);
+  });
 }
 
 template <typename T, typename I>
@@ -137,13 +134,9 @@ int heads_typed(const HeadsArgs& a) {
 
 int check_heads_args(const char* fn, int idx_dtype, int val_dtype, int64_t m, int64_t k,
                      int64_t heads, int64_t d, int64_t nnz, const ofx_spmm_options* opts) {
-  OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d), OFX_EINVAL,
-              "%s: bad heads=%lld / d=%lld", fn, (long long)heads, (long long)d);
+  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
   if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
-  OFX_REQUIRE(opts->planned == 0 && opts->variant == 0, OFX_EINVAL,
-              "%s: options planned=%d / variant=%d are not supported (plan-once and the tuning "
-              "variants belong to spmm_csr)", fn, (int)opts->planned, (int)opts->variant);
-  return OFX_OK;
+  return check_no_plan_options(fn, opts);
 }
 
 }  // namespace
@@ -189,9 +182,7 @@ extern "C" int ofx_spmm_csr_heads(void* stream, int idx_dtype, int val_dtype, in
     // these entries' wording of the size error, ahead of the shared check
     const size_t need = plan::ws_layout(nrows, nnz, n, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
                                         resolve_schedule(d, opts)).total;
-    OFX_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), OFX_EWORKSPACE,
-                "spmm_csr_heads: workspace of %zu bytes is smaller than the %zu bytes required",
-                workspace_bytes, need);
+    if ((rc = check_workspace("spmm_csr_heads", workspace, workspace_bytes, need))) return rc;
     const HeadsArgs a{static_cast<hipStream_t>(stream), row_ptr, col_idx, values, b, c, ldb, ldc,
                       m, row_begin, nrows, heads, d, nnz, k, workspace, workspace_bytes, opts};
     return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {

@@ -20,8 +20,7 @@ namespace {
 
 int check_heads_sizes(const char* fn, int idx_dtype, int val_dtype, int64_t m, int64_t k,
                       int64_t heads, int64_t d, int64_t nnz, int64_t row_begin, int64_t row_end) {
-  OFX_REQUIRE(heads >= 0 && d >= 0 && (d == 0 || heads <= INT64_MAX / d), OFX_EINVAL,
-              "%s: bad heads=%lld / d=%lld", fn, (long long)heads, (long long)d);
+  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
   if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
   return check_row_range(fn, row_begin, row_end, m);
 }
@@ -42,10 +41,7 @@ extern "C" int ofx_spmm_csr_heads_cpu(int num_threads, int idx_dtype, int val_dt
     int rc = check_heads_sizes("spmm_csr_heads_cpu", idx_dtype, val_dtype, m, k, heads, d, nnz,
                                row_begin, row_end);
     if (rc) return rc;
-    OFX_REQUIRE(opts->planned == 0 && opts->variant == 0, OFX_EINVAL,
-                "spmm_csr_heads_cpu: options planned=%d / variant=%d are not supported (plan-once "
-                "and the tuning variants belong to spmm_csr)", (int)opts->planned,
-                (int)opts->variant);
+    if ((rc = check_no_plan_options("spmm_csr_heads_cpu", opts))) return rc;
     const int64_t n = heads * d;
     OFX_REQUIRE(ldb >= n && ldc >= n, OFX_EINVAL, "spmm_csr_heads_cpu: ldb=%lld / ldc=%lld < n=%lld",
                 (long long)ldb, (long long)ldc, (long long)n);

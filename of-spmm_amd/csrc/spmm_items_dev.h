@@ -121,6 +121,23 @@ __device__ __forceinline__ bool poison_nonzeros(const unsigned long long* __rest
   return true;
 }
 
+// The same for `heads` outputs per nonzero (out is [nnz, heads] row-major).  A function of its
+// own: the narrow SDDMM's kernels keep the one above as it is.
+template <typename T, typename I>
+__device__ __forceinline__ bool poison_head_nonzeros(const unsigned long long* __restrict__ counters,
+                                                     int64_t block_base, unsigned* err,
+                                                     const I* __restrict__ rp, int64_t row_begin,
+                                                     int64_t nrows, int64_t heads,
+                                                     T* __restrict__ out) {
+  if (!plan_failed(counters, block_base, err)) return false;
+  const int64_t e0 = (int64_t)rp[row_begin] * heads, e1 = (int64_t)rp[row_begin + nrows] * heads;
+  const T p = poison_value<T>();
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = e0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < e1; e += stride)
+    out[e] = p;
+  return true;
+}
+
 // VEC consecutive elements of one row as one load of up to 16 bytes.
 template <typename E, int VEC>
 struct alignas(VEC * sizeof(E) >= 16 ? 16 : VEC * sizeof(E)) Pack {
@@ -251,9 +268,7 @@ int prepare_plan(const char* fn, hipStream_t stream, const I* rp, int64_t m, int
                        launch_form(nrows, nnz_est, n, sched) != Form::Small;
   // these entries' wording of the size error, ahead of the shared check
   const size_t need = plan::ws_layout(nrows, nnz, n, part_bytes_per_elem, sched).total;
-  OFX_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need), OFX_EWORKSPACE,
-              "%s: workspace of %zu bytes is smaller than the %zu bytes required", fn, ws_bytes,
-              need);
+  if (const int rc = check_workspace(fn, ws, ws_bytes, need)) return rc;
   return prepare_plan<I>(fn, stream, rp, row_begin, nrows, nnz, nnz_est, n, part_bytes_per_elem,
                          sched, planned, ws, ws_bytes, out);
 }
@@ -299,17 +314,23 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-// Launches it over the hubs of plan `p` (nothing without a plan or without room for a hub).
+// Launches it over the hubs of plan `p` (nothing without a plan or without room for a hub), for
+// the plane of partials `part`: the workspace's own, or one of several an op laid out there.
 template <typename T>
-int launch_hub_sum(hipStream_t stream, const Planned& p, T* out, int64_t ldc, int64_t nrows,
-                   int64_t n) {
+int launch_hub_sum(hipStream_t stream, const Planned& p, const typename Num<T>::acc* part, T* out,
+                   int64_t ldc, int64_t nrows, int64_t n) {
   if (!p.has_plan || p.w.max_hubs == 0) return OFX_OK;
   const unsigned hgrid = (unsigned)std::min<int64_t>(p.w.max_hubs, 8192);
   hipLaunchKernelGGL((hub_sum_kernel<T>), dim3(hgrid), dim3(kBlock), 0, stream, p.wl.counters,
-                     p.wl.hubs, static_cast<const typename Num<T>::acc*>(p.wl.part), out, ldc,
-                     nrows, n);
+                     p.wl.hubs, part, out, ldc, nrows, n);
   OFX_HIP_CHECK(hipGetLastError());
   return OFX_OK;
+}
+template <typename T>
+int launch_hub_sum(hipStream_t stream, const Planned& p, T* out, int64_t ldc, int64_t nrows,
+                   int64_t n) {
+  return launch_hub_sum<T>(stream, p, static_cast<const typename Num<T>::acc*>(p.wl.part), out, ldc,
+                           nrows, n);
 }
 
 }  // namespace

@@ -10,12 +10,16 @@ refactor of the Python layer (oneflow_spmm/_C.py, autograd.py, ops.py) must leav
 
 Every attribute of _lib.LIB is wrapped after import (the wrappers keep __name__, which the
 two-phase call uses in its messages).  The problem is the smallest with empty rows: a 5-row CSR
-with row lengths [0, 3, 1, 0, 2], K = 4, N = 8, H = 2, D = 4, f32 / int32.  Bad inputs always use
-CPU tensors (they must raise before any kernel runs; a GPU is no place to find out).
+with row lengths [0, 3, 1, 0, 2], K = 4, N = 8, H = 2, D = 4, f32 / int32.  Bad inputs to the
+Python layer always use CPU tensors (they must raise before any kernel runs; a GPU is no place to
+find out).  What the multi-head C-ABI entries themselves refuse (entry_errors) is asked on the
+traced device, where the HIP entries and their workspace queries answer: the record a refactor of
+those entries' host side must leave unchanged.
 """
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -122,6 +126,93 @@ def good_calls(fs, torch, p):
     add("ops.graph_attention_csr_heads", lambda: ops.graph_attention_csr_heads(
         rp, ci, p["ah"].reshape(M, H * D), b2, b2, M, K, H))
     add("_C.spmm_csr_gathered", lambda: fs._C.spmm_csr_gathered(rt, ct, p["v"], perm, K, M, p["g"]))
+    # the GATv2 scores: the public entries, then ops.py's
+    att = p["bias"].reshape(H, D)
+    add("gatv2_scores", lambda: fs.gatv2_scores(rp, ci, p["ah"], p["bh"], att))
+    steps("gatv2_scores backward", p["ah"], lambda xx: fs.gatv2_scores(
+        rp, ci, xx, leaf(p["bh"]), leaf(att)).backward(p["eh"]))
+    add("gatv2_attention", lambda: fs.gatv2_attention(rp, ci, p["ah"], p["bh"], att))
+    a2 = p["ah"].reshape(M, H * D)
+    add("ops.gatv2_scores_csr_heads", lambda: ops.gatv2_scores_csr_heads(
+        rp, ci, a2, b2, p["bias"], M, K, H))
+    for with_att in (True, False):
+        add(f"ops.gatv2_scores_csr_heads_grad with_att={with_att}",
+            lambda with_att=with_att: ops.gatv2_scores_csr_heads_grad(
+                rp, ci, a2, b2, p["bias"], p["eh"], M, K, H, with_att=with_att))
+    return out
+
+
+def entry_errors(fs, torch, p):
+    """[(label, thunk)]: what the multi-head entries of ops.py refuse, on the traced device's
+    tensors (the HIP entry and its workspace query there, the kCPU entry on host tensors): bad
+    heads / d, a workspace of one byte (ignored by the kCPU entries, which take none), planned /
+    variant options, a leading dimension below n.
+    Every refusal returns before a launch.  The rows here are long enough to need a workspace:
+    row lengths [300, 1] (the per-nonzero ops cut their items at 256 nonzeros)."""
+    ops, _lib, dev = fs.ops, fs._lib, p["rp"].device
+    n, nnz = H * D, 301
+    rp = torch.tensor([0, 300, 301], dtype=torch.int32, device=dev)
+    ci = (torch.arange(nnz, dtype=torch.int32) % K).to(dev)
+    g = torch.Generator().manual_seed(6)
+    r = lambda *s: (torch.rand(*s, generator=g) - 0.5).to(dev)  # noqa: E731
+    a, b, att, vh, eh = r(2, n), r(K, n), r(n), r(nnz, H), r(nnz, H)
+    e_out, o_out = torch.empty_like(eh), torch.empty_like(a)
+    split8 = ops.make_options(split=8, chunk=8)
+    # op -> call(heads, a, b, **kw): kw are options= / workspace_bytes= where the op takes them
+    entries = {
+        "spmm_csr_heads": lambda heads, a, b, **kw: ops.spmm_csr_heads(
+            rp, ci, vh, b, 2, K, heads, out=o_out, **kw),
+        "sddmm_csr_heads": lambda heads, a, b, **kw: ops.sddmm_csr_heads(
+            rp, ci, a, b, 2, K, heads, out=e_out, **kw),
+        "graph_attention_csr_heads": lambda heads, a, b, **kw: ops.graph_attention_csr_heads(
+            rp, ci, a, b, b, 2, K, heads, out=o_out, attn=e_out, **kw),
+        "gatv2_scores_csr_heads": lambda heads, a, b, **kw: ops.gatv2_scores_csr_heads(
+            rp, ci, a, b, att, 2, K, heads, out=e_out, **kw),
+        "gatv2_scores_csr_heads_grad": lambda heads, a, b, **kw: ops.gatv2_scores_csr_heads_grad(
+            rp, ci, a, b, att, eh, 2, K, heads, d_x=o_out, p=torch.empty_like(a), **kw),
+        "gatv2_scores_csr_heads_grad no p": lambda heads, a, b, **kw:
+            ops.gatv2_scores_csr_heads_grad(rp, ci, a, b, att, eh, 2, K, heads, with_att=False,
+                                            d_x=o_out, **kw),
+    }
+    takes_options = lambda op: "sddmm" not in op and op != "gatv2_scores_csr_heads"  # noqa: E731
+    out = []
+    add = lambda label, fn: out.append((label, fn))  # noqa: E731
+    for op, call in entries.items():
+        add(f"{op}: good", lambda call=call: call(H, a, b))
+        add(f"{op}: heads < 0", lambda call=call: call(-1, a, b))
+        short = dict(workspace_bytes=1, **(dict(options=split8) if takes_options(op) else {}))
+        add(f"{op}: workspace of one byte", lambda call=call, short=short: call(H, a, b, **short))
+        add(f"{op}: ld < n", lambda call=call: call(H, a.as_strided((2, n), (n - 1, 1)),
+                                                    b.as_strided((K, n), (n - 1, 1))))
+        if takes_options(op):
+            add(f"{op}: good, split 8", lambda call=call: call(H, a, b, options=split8))
+            add(f"{op}: planned", lambda call=call: call(H, a, b, options=ops.make_options(planned=True)))
+            add(f"{op}: variant", lambda call=call: call(H, a, b, options=ops.make_options(variant=1)))
+    # the HIP entries' own refusal of heads * d (their workspace queries answer first above): no
+    # pointer is read and nothing is launched, on any machine
+    I, F, LIB = _lib.DT_INT32, _lib.DT_FLOAT, _lib.LIB
+    big = 1 << 62
+    direct = {
+        "ofx_spmm_csr_heads": lambda: LIB.ofx_spmm_csr_heads(
+            None, I, F, 2, K, big, 4, nnz, None, None, None, None, n, None, n, 0, 2, None, 0, None),
+        "ofx_sddmm_csr_heads": lambda: LIB.ofx_sddmm_csr_heads(
+            None, I, F, 2, K, big, 4, nnz, None, None, None, n, None, n, None, 0, 2, None, 0),
+        "ofx_graph_attention_csr_heads": lambda: LIB.ofx_graph_attention_csr_heads(
+            None, I, F, 2, K, big, 4, nnz, None, None, None, n, None, n, None, n, None, n, None, 0,
+            2, None, 0, None),
+        "ofx_gatv2_scores_csr_heads": lambda: LIB.ofx_gatv2_scores_csr_heads(
+            None, I, F, 2, K, big, 4, nnz, None, None, None, n, None, n, None, 0.2, None, 0, 2,
+            None, 0),
+        "ofx_gatv2_scores_csr_heads_grad": lambda: LIB.ofx_gatv2_scores_csr_heads_grad(
+            None, I, F, 2, K, big, 4, nnz, None, None, None, n, None, n, None, 0.2, None, None, n,
+            None, n, 0, 2, None, 0, None),
+    }
+    for name, fn in direct.items():
+        add(f"{name}: heads * d overflows", lambda fn=fn, name=name: _lib.check(fn(), name))
+    size = ctypes.c_size_t(0)
+    add("ofx_gatv2_scores_csr_heads_grad_workspace_size: 2 * heads * d overflows",
+        lambda: _lib.check(LIB.ofx_gatv2_scores_csr_heads_grad_workspace_size(
+            I, F, 2, K, 1 << 61, 3, nnz, 1, None, ctypes.byref(size)), "grad workspace_size"))
     return out
 
 
@@ -226,7 +317,9 @@ def main():
         fn()
         record["calls"].append([label, list(log)])
     fs.autograd.TRANSPOSE_CACHE.__init__()
-    for label, fn in bad_calls(fs, torch, problem(torch, torch.device("cpu"))):
+    bad = bad_calls(fs, torch, problem(torch, torch.device("cpu"))) + \
+        entry_errors(fs, torch, problem(torch, torch.device(args.device)))
+    for label, fn in bad:
         del log[:]
         try:
             fn()

@@ -13,21 +13,11 @@
 #include <cstring>
 #include <vector>
 
-#include "ofx_spmm.h"
+#include "sanitize_common.h"
 
 namespace {
 
-int g_fail = 0;
-#define EXPECT(cond, ...)                        \
-  do {                                           \
-    if (!(cond)) {                               \
-      ++g_fail;                                  \
-      std::printf("FAIL %s:%d ", __FILE__, __LINE__); \
-      std::printf(__VA_ARGS__);                  \
-      std::printf("\n");                         \
-    }                                            \
-  } while (0)
-
+// this program's own generator (xorshift): its cases keep the data they were written with
 uint64_t g_state = 0x9e3779b97f4a7c15ull;
 uint64_t next_u64() {
   g_state ^= g_state << 13;
@@ -278,8 +268,8 @@ int main() {
   check_partition_synth();
   check_relu_bias_grad_threads();
   check_errors();
-  if (g_fail) {
-    std::printf("FAILED %d checks\n", g_fail);
+  if (g_failures) {
+    std::printf("FAILED %d checks\n", g_failures);
     return 1;
   }
   std::printf("OK\n");

@@ -14,55 +14,9 @@
 #include <cstring>
 #include <vector>
 
-#include "ofx_spmm.h"
-#include "spmm_common.h"
+#include "sanitize_common.h"
 
 namespace {
-
-int g_failures = 0;
-
-#define EXPECT(cond, ...)                        \
-  do {                                           \
-    if (!(cond)) {                               \
-      ++g_failures;                              \
-      fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-      fprintf(stderr, __VA_ARGS__);              \
-      fprintf(stderr, "\n");                     \
-    }                                            \
-  } while (0)
-
-template <typename T>
-struct Code;
-template <>
-struct Code<float> {
-  static constexpr int dt = OFX_DT_FLOAT;
-  static constexpr double tol = 1e-6;
-};
-template <>
-struct Code<double> {
-  static constexpr int dt = OFX_DT_DOUBLE;
-  static constexpr double tol = 1e-14;
-};
-template <>
-struct Code<ofx::bf16> {
-  static constexpr int dt = OFX_DT_BFLOAT16;
-  static constexpr double tol = 1e-2;
-};
-template <>
-struct Code<ofx::f16> {
-  static constexpr int dt = OFX_DT_FLOAT16;
-  static constexpr double tol = 2e-3;
-};
-template <typename I>
-constexpr int idx_code() {
-  return sizeof(I) == 4 ? OFX_DT_INT32 : OFX_DT_INT64;
-}
-
-uint64_t g_rng = 4242;
-double uniform() {  // [0, 1)
-  g_rng = ofx::splitmix64(g_rng);
-  return (double)(g_rng >> 11) / 9007199254740992.0;
-}
 
 constexpr double kSlope = 0.2;
 
@@ -222,6 +176,7 @@ void error_paths() {
 }  // namespace
 
 int main() {
+  g_rng = 4242;
   run_type<float, int32_t>();
   run_type<float, int64_t>();
   run_type<double, int32_t>();

@@ -15,41 +15,14 @@
 #include <cstring>
 #include <vector>
 
-#include "ofx_spmm.h"
-#include "spmm_common.h"
+#include "sanitize_common.h"
 
 namespace {
 
-int g_failures = 0;
-
-#define EXPECT(cond, ...)                        \
-  do {                                           \
-    if (!(cond)) {                               \
-      ++g_failures;                              \
-      fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); \
-      fprintf(stderr, __VA_ARGS__);              \
-      fprintf(stderr, "\n");                     \
-    }                                            \
-  } while (0)
-
-template <typename T>
-constexpr int val_code() {
-  if (__is_same(T, float)) return OFX_DT_FLOAT;
-  if (__is_same(T, double)) return OFX_DT_DOUBLE;
-  if (__is_same(T, ofx::bf16)) return OFX_DT_BFLOAT16;
-  return OFX_DT_FLOAT16;
-}
-template <typename I>
-constexpr int idx_code() {
-  return sizeof(I) == 4 ? OFX_DT_INT32 : OFX_DT_INT64;
-}
 template <typename T>
 constexpr double tolerance() {  // of out against the naive double attention: |values| <= 1
   return sizeof(T) == 8 ? 1e-12 : (sizeof(T) == 4 ? 1e-5 : 3e-2);
 }
-
-uint64_t g_rng = 2026;
-uint64_t next() { return g_rng = ofx::splitmix64(g_rng); }
 
 template <typename T>
 T make(double x) {
@@ -98,7 +71,7 @@ void run(int64_t heads, int64_t d) {
               s[(size_t)(j - j0)] / sum * get(v[(size_t)((int64_t)col[j] * n + h * d + c)]);
     }
 
-  const int it = idx_code<I>(), vt = val_code<T>();
+  const int it = idx_code<I>(), vt = Code<T>::dt;
   ofx_spmm_options hub = OFX_SPMM_OPTIONS_INIT;
   hub.split_threshold = 8;
   hub.chunk = 8;
@@ -154,6 +127,7 @@ void run_types() {
 }  // namespace
 
 int main() {
+  g_rng = 2026;
   run_types<float>();
   run_types<double>();
   run_types<ofx::bf16>();

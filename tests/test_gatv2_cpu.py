@@ -6,15 +6,12 @@ layer, the C-ABI's argument checks, and the kCPU kernels under the host sanitize
 from __future__ import annotations
 
 import os
-import subprocess
 
 import pytest
 
 import gatv2_cases as gc
 from helpers import DTYPES
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+from sanitize_helpers import CLANG, build_and_run
 
 
 @pytest.mark.parametrize("h,d,dt", gc.fwd_cases(gc.FAST_HD))
@@ -132,20 +129,4 @@ def test_cpu_kernels_under_sanitizers(tmp_path):
     AddressSanitizer + UndefinedBehaviorSanitizer and driven by tests/native/gatv2_sanitize.cpp,
     which also checks them against a naive loop.  Host code only: nothing is loaded into Python and
     nothing runs on the GPU."""
-    exe = tmp_path / "gatv2_sanitize"
-    csrc = os.path.join(ROOT, "of-spmm_amd", "csrc")
-    subprocess.run([CLANG, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fopenmp",
-                    "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas",
-                    "-Wno-duplicate-decl-specifier", "-Wno-unused-function",
-                    "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                    os.path.join(ROOT, "tests", "native", "gatv2_sanitize.cpp"),
-                    os.path.join(csrc, "gatv2_scores_cpu.cpp"), os.path.join(csrc, "errors.cpp"),
-                    "-o", str(exe)], check=True)
-    supp = tmp_path / "lsan.supp"
-    supp.write_text("leak:___kmp_allocate\n")  # the OpenMP runtime's own thread-pool state
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
-               LSAN_OPTIONS=f"suppressions={supp}", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.strip().endswith("OK") and "runtime error" not in r.stderr, r.stdout + r.stderr
+    build_and_run(tmp_path, "gatv2_sanitize", ["gatv2_scores_cpu.cpp", "errors.cpp"])
