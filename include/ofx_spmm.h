@@ -776,6 +776,51 @@ int ofx_gatv2_scores_csr_heads_grad_cpu(int num_threads, int idx_dtype, int val_
                                         int64_t ldp, int64_t row_begin, int64_t row_end,
                                         const ofx_spmm_options* opts);
 
+/* ---- multi-head SpMM over an FP8 feature table (op "spmm_csr_heads_fp8") ---------
+ * ofx_spmm_csr_heads with b stored in OCP FP8, one byte per element, and an optional f32 scale per
+ * row of b: half the gathered bytes of bf16 for a quantised feature table.  values T[nnz, heads],
+ * b_q [k, heads*d] bytes of format b_format with leading dimension ldb in bytes, b_scale f32[k] or
+ * NULL, c T[rows, heads*d]; T is float, float16 or bfloat16 (double: OFX_EUNSUPPORTED) and `a` =
+ * f32 is the accumulation type of all three.  The format codes are constants of their own, not
+ * OFX_DT_* values (OneFlow's DataType has no 8-bit float).
+ *
+ * The contract is a composition with ofx_spmm_csr_heads on two tensors the kernels never write:
+ *   1. Bd[c, n] = store_T(dequant(b_q[c, n])): exact, every finite code of both formats is
+ *      representable in f32, f16 and bf16; a NaN code gives a NaN, e5m2's infinities infinities.
+ *   2. V'[j, h] = store_T(load(values[j, h]) * b_scale[col_idx[j]]): one product in `a` and one
+ *      rounding to T as a step of its own.  b_scale == NULL: V' = values bit for bit (no multiply
+ *      by one).  A column outside [0, k) reads the scale +0 and a zero row of b, as the sum op
+ *      gathers it; the kCPU kernel refuses a negative column (OFX_EINVAL) as
+ *      ofx_spmm_csr_heads_cpu does.
+ *   3. c has exactly the bits of ofx_spmm_csr_heads in type T on (row_ptr, col_idx, V', Bd) under
+ *      the same options: multiply rounded to T, add in `a`, nonzeros ascending, the hub rule of the
+ *      schedule resolved from d (chunk partials added in chunk order into +0), +0 for an empty row;
+ *      planned != 0 or variant != 0 is refused (OFX_EINVAL).  heads == 0, d == 0 or an empty row
+ *      range write nothing; nnz == 0 writes +0 rows, as that entry does.
+ * Device version: asynchronous on `stream`, no atomics, no allocation, no host synchronisation,
+ * capturable in a graph.  The workspace is ofx_spmm_csr_heads's for the same shapes (4-byte
+ * partials); OFX_EWORKSPACE when it is too small.  OFX_EINVAL: a negative size, a bad row range, a
+ * leading dimension below heads*d, a NULL pointer, an unknown format code.  Nothing is launched on
+ * an error.  HIP kernel and kCPU kernel give the same bits; the kCPU kernel's bits do not depend
+ * on num_threads.                                                                                */
+#define OFX_FP8_E4M3 1 /* e4m3fn: 1-4-3, bias 7, no infinity, S.1111.111 is NaN; max 448 */
+#define OFX_FP8_E5M2 2 /* e5m2: 1-5-2, bias 15, IEEE infinities and NaNs; max 57344      */
+int ofx_spmm_csr_heads_fp8_workspace_size(int idx_dtype, int val_dtype, int b_format, int64_t m,
+                                          int64_t k, int64_t heads, int64_t d, int64_t nnz,
+                                          const ofx_spmm_options* opts, size_t* bytes);
+int ofx_spmm_csr_heads_fp8(void* stream, int idx_dtype, int val_dtype, int b_format, int64_t m,
+                           int64_t k, int64_t heads, int64_t d, int64_t nnz, const void* row_ptr,
+                           const void* col_idx, const void* values /* [nnz, heads] */,
+                           const void* b_q, int64_t ldb, const void* b_scale /* f32 [k] or NULL */,
+                           void* c, int64_t ldc, int64_t row_begin, int64_t row_end,
+                           void* workspace, size_t workspace_bytes, const ofx_spmm_options* opts);
+int ofx_spmm_csr_heads_fp8_cpu(int num_threads, int idx_dtype, int val_dtype, int b_format,
+                               int64_t m, int64_t k, int64_t heads, int64_t d, int64_t nnz,
+                               const void* row_ptr, const void* col_idx, const void* values,
+                               const void* b_q, int64_t ldb, const void* b_scale, void* c,
+                               int64_t ldc, int64_t row_begin, int64_t row_end,
+                               const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -1246,6 +1291,17 @@ int ofx_functional_gatv2_scores_csr_heads_grad(void* stream, const ofx_tensor_de
                                                double negative_slope, int64_t with_att,
                                                ofx_tensor_desc* d_x, ofx_tensor_desc* p, void* tmp,
                                                size_t tmp_bytes, size_t* tmp_size_out);
+/* functional::SpmmCsrHeadsFp8: op "spmm_csr_heads_fp8" (values [nnz, H], b [K, N] of dtype uint8
+ * holding FP8 codes, optional b_scale [K] float (NULL: absent); attr b_format = OFX_FP8_E4M3 /
+ * OFX_FP8_E5M2 -> out [M, N] of values' dtype) of oneflow/user/ops/spmm_heads_fp8_op.cpp through
+ * the op-registry dispatch; the contract of ofx_spmm_csr_heads_fp8.  tmp_size_out != NULL: only
+ * the tmp size is computed.                                                                     */
+int ofx_functional_spmm_csr_heads_fp8(void* stream, const ofx_tensor_desc* row_ptr,
+                                      const ofx_tensor_desc* col_idx,
+                                      const ofx_tensor_desc* values, const ofx_tensor_desc* b,
+                                      const ofx_tensor_desc* b_scale, int64_t a_num_rows,
+                                      int64_t a_num_cols, int64_t b_format, ofx_tensor_desc* out,
+                                      void* tmp, size_t tmp_bytes, size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

@@ -204,6 +204,18 @@ class Gatv2ScoresCsrHeadsGradOp {
                                     const user_op::UserOpConfWrapper& conf);
 };
 
+// The multi-head SpMM over an FP8 feature table with an optional scale per row of it
+// (oneflow/user/ops/spmm_heads_fp8_op.cpp).
+class SpmmCsrHeadsFp8Op {
+ public:
+  static Maybe<void> InferLogicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> InferPhysicalTensorDesc(user_op::InferContext* ctx);
+  static Maybe<void> GetSbp(user_op::SbpContext* ctx);
+  static Maybe<void> InferDataType(user_op::InferContext* ctx);
+  static Maybe<void> ModifyInputArg(const user_op::GetInputArgModifier& GetInputArgModifierFn,
+                                    const user_op::UserOpConfWrapper& conf);
+};
+
 // The S(0) -> B collectives the row-split op's B operand goes through: eager boxing
 // (oneflow/user/ops/eager_nccl_ops.cpp:188-233) and the lazy graph's logical collective
 // (oneflow/user/ops/nccl_logical_ops.cpp:104-142, ODS OneFlowUserOps.td:5341-5357).

@@ -902,6 +902,28 @@ extern "C" int ofx_functional_gatv2_scores_csr_heads_grad(
   });
 }
 
+// ---- functional::SpmmCsrHeadsFp8 -----------------------------------------------------------------
+// Op "spmm_csr_heads_fp8" (oneflow/user/ops/spmm_heads_fp8_op.cpp) through the same op-registry
+// dispatch; `b_scale` may be NULL (the optional input is then absent).
+extern "C" int ofx_functional_spmm_csr_heads_fp8(
+    void* stream, const ofx_tensor_desc* row_ptr, const ofx_tensor_desc* col_idx,
+    const ofx_tensor_desc* values, const ofx_tensor_desc* b, const ofx_tensor_desc* b_scale,
+    int64_t a_num_rows, int64_t a_num_cols, int64_t b_format, ofx_tensor_desc* out, void* tmp,
+    size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(values != nullptr && b != nullptr, OFX_EINVAL,
+                "spmm_csr_heads_fp8: NULL input a_csr_values or b");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_heads_fp8");
+    std::vector<Arg> ins = {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                            {"a_csr_values", values}, {"b", b}};
+    if (b_scale != nullptr) ins.push_back({"b_scale", b_scale});
+    return ToStatus(RunUserOp("spmm_csr_heads_fp8", ins, {{"out", out}},
+                              {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols},
+                               {"b_format", b_format}},
+                              stream, tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
 // ---- functional::GraphAttentionCsrHeads ----------------------------------------------------------
 // Op "graph_attention_csr_heads" (oneflow/user/ops/graph_attention_heads_op.cpp) through the same
 // op-registry dispatch; two outputs.

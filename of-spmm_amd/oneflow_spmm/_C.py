@@ -459,6 +459,70 @@ def spmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     return out
 
 
+FP8_FORMATS = {torch.float8_e4m3fn: _lib.FP8_E4M3, torch.float8_e5m2: _lib.FP8_E5M2}
+
+
+def _codes_desc(b_q: torch.Tensor) -> TensorDesc:
+    """The descriptor of an FP8 tensor as the op takes it: its codes as kUInt8 (DataType has no
+    8-bit float; the format travels in attr b_format)."""
+    d = TensorDesc()
+    d.dtype = _lib.DT_UINT8
+    d.device = _device_index(b_q)
+    d.ndim = b_q.dim()
+    for i in range(b_q.dim()):
+        d.shape[i] = b_q.shape[i]
+        d.stride[i] = b_q.stride(i)
+    d.data = b_q.data_ptr() if b_q.numel() > 0 else None
+    return d
+
+
+def spmm_csr_heads_fp8(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                       a_csr_values: torch.Tensor, a_num_rows: int, a_num_cols: int,
+                       b: torch.Tensor, b_scale: torch.Tensor | None = None, *,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "spmm_csr_heads_fp8": spmm_csr_heads over a feature table stored in FP8.  b is [K, H*D] of
+    dtype torch.float8_e4m3fn or torch.float8_e5m2 (a row-strided view is read in place), b_scale
+    an optional float32 [K] scale per row of b, a_csr_values [nnz, H] of dtype float32, float16 or
+    bfloat16, which is out's.  out has exactly the bits of spmm_csr_heads on the values times
+    b_scale[col] rounded to the dtype and on b converted to the dtype (contract in
+    include/ofx_spmm.h)."""
+    op = "spmm_csr_heads_fp8"
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
+    vals = _prep(a_csr_values, "a_csr_values")
+    if not isinstance(b, torch.Tensor) or b.dtype not in FP8_FORMATS:
+        raise TypeError(f"{op}: b should be float8_e4m3fn or float8_e5m2, got "
+                        f"{getattr(b, 'dtype', type(b).__name__)}")
+    bb = _prep(b, "b", matrix=True)
+    _check_inputs(op, rp, ci, [("a_csr_values", vals)], 2, "a_csr_values", True)
+    if vals.dtype == torch.float64:
+        raise TypeError(f"{op} supports float, float16, bfloat16; got {vals.dtype}")
+    if bb.dim() != 2:
+        raise RuntimeError(f"{op}: b should be 2-D [K, heads * D], got shape {tuple(bb.shape)}")
+    if vals.shape[1] < 1 or bb.shape[1] % vals.shape[1] != 0:
+        raise RuntimeError(f"{op}: b's columns ({bb.shape[1]}) should be a multiple of the number "
+                           f"of heads ({vals.shape[1]})")
+    if bb.device != vals.device:
+        raise RuntimeError(f"{op}: expected all tensors on the same device, got b on {bb.device} "
+                           f"and a_csr_values on {vals.device}")
+    r_scale = None
+    if b_scale is not None:
+        b_scale = _prep(b_scale, "b_scale")
+        if b_scale.dtype != torch.float32 or tuple(b_scale.shape) != (bb.shape[0],):
+            raise RuntimeError(f"{op}: b_scale should be float32 [K] = ({bb.shape[0]},), got "
+                               f"{b_scale.dtype} {tuple(b_scale.shape)}")
+        if b_scale.device != vals.device:
+            raise RuntimeError(f"{op}: expected all tensors on the same device, got b_scale on "
+                               f"{b_scale.device}")
+        r_scale = ctypes.byref(desc(b_scale))
+    out = _check_out(op, out, (int(a_num_rows), bb.shape[1]), vals)
+    if out.numel() == 0:
+        return out
+    _two_phase(LIB.ofx_functional_spmm_csr_heads_fp8, vals,
+               _refs(rp, ci, vals) + (ctypes.byref(_codes_desc(bb)), r_scale, int(a_num_rows),
+                                      int(a_num_cols), FP8_FORMATS[bb.dtype]), _refs(out))
+    return out
+
+
 def sddmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, a: torch.Tensor,
                     b: torch.Tensor, num_heads: int, *,
                     out: torch.Tensor | None = None) -> torch.Tensor:

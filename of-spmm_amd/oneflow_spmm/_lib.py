@@ -20,6 +20,8 @@ DT_FLOAT, DT_DOUBLE, DT_INT32, DT_INT64, DT_FLOAT16, DT_BFLOAT16 = 2, 3, 5, 6, 9
 # test knobs of ofx_debug_set (include/ofx_spmm.h)
 DEBUG_PLAN_SPIN_LIMIT, DEBUG_THROW_IN_COMPUTE, DEBUG_EXCHANGE_STALL = 1, 2, 3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 0, 1, 2, 3  # OFX_REDUCE_*
+DT_UINT8 = 7  # DataType kUInt8: the codes of an FP8 tensor (op "spmm_csr_heads_fp8")
+FP8_E4M3, FP8_E5M2 = 1, 2  # OFX_FP8_*
 MEMCPY_H2D, MEMCPY_D2H, MEMCPY_D2D, MEMCPY_DEFAULT = 1, 2, 3, 4
 UNIQUE_ID_BYTES = 128
 PEER_HANDLE_BYTES = 96   # OFX_PEER_HANDLE_BYTES
@@ -236,6 +238,14 @@ def _load():
         "ofx_functional_gatv2_scores_csr_heads_grad": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, pdesc,
                                                         i64, ctypes.c_double, i64, pdesc, pdesc, p,
                                                         sz, ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_heads_fp8_workspace_size": ([i32, i32, i32, i64, i64, i64, i64, i64, popt,
+                                                   ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_heads_fp8": ([p, i32, i32, i32, i64, i64, i64, i64, i64, p, p, p, p, i64, p,
+                                    p, i64, i64, i64, p, sz, popt], i32),
+        "ofx_spmm_csr_heads_fp8_cpu": ([i32, i32, i32, i32, i64, i64, i64, i64, i64, p, p, p, p,
+                                        i64, p, p, i64, i64, i64, popt], i32),
+        "ofx_functional_spmm_csr_heads_fp8": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64, i64, i64,
+                                               pdesc, p, sz, ctypes.POINTER(sz)], i32),
         "ofx_graph_attention_csr_heads_workspace_size": ([i32, i32, i64, i64, i64, i64, i64, popt,
                                                           ctypes.POINTER(sz)], i32),
         "ofx_graph_attention_csr_heads": ([p, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64, p,

@@ -320,6 +320,101 @@ def _spmm_heads(row_ptr, col_idx, values, m, k, b, out, reduce):
     return out if out is not None else res.view(m, heads, d)
 
 
+FP8_MAX = {torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
+
+
+def quantize_rows_fp8(b: torch.Tensor, dtype: torch.dtype = torch.float8_e4m3fn):
+    """(b_q, b_scale) for `spmm_fp8`: every row of b (the last dimension of a [K, N] or [K, H, D]
+    tensor) scaled into the range of `dtype` (torch.float8_e4m3fn, max 448, or torch.float8_e5m2,
+    max 57344) and rounded to it.  scale = amax / max per row in float32, 1 for an all-zero row;
+    b_q = (b / scale).to(dtype), so b is b_q * scale[:, None] up to the format's rounding.  One-off
+    preprocessing of a feature table: a torch composition, no kernel of its own."""
+    if dtype not in FP8_MAX:
+        raise TypeError(f"quantize_rows_fp8: dtype should be float8_e4m3fn or float8_e5m2, got "
+                        f"{dtype}")
+    if b.dim() not in (2, 3):
+        raise RuntimeError("quantize_rows_fp8: b should be [K, N] or [K, H, D], got shape "
+                           f"{tuple(b.shape)}")
+    bf = b.detach().to(torch.float32)
+    amax = bf.flatten(1).abs().amax(dim=1) if bf.numel() else bf.new_zeros(bf.shape[0])
+    scale = torch.where(amax > 0, amax / FP8_MAX[dtype], torch.ones_like(amax))
+    b_q = (bf / scale.view(-1, *([1] * (bf.dim() - 1)))).to(dtype)
+    return b_q, scale
+
+
+class SpmmFp8Function(torch.autograd.Function):
+    """out = spmm_fp8(values, b_q, b_scale), differentiable in values [nnz, H] alone:
+    d(values)[j, h] = <d(out)[row(j), h, :], Bd[col[j], h, :]> * b_scale[col[j]], the multi-head
+    SDDMM over Bd = b_q converted to the values' dtype, which only the backward materialises."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, values, m, k, b_q2, b_scale, heads):
+        out = _C.spmm_csr_heads_fp8(row_ptr, col_idx, values, m, k, b_q2, b_scale)
+        ctx.save_for_backward(row_ptr, col_idx, b_q2, b_scale)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        row_ptr, col_idx, b_q2, b_scale = ctx.saved_tensors
+        d_values = None
+        if ctx.needs_input_grad[2]:
+            g = d_out.contiguous()
+            d_values = _C.sddmm_csr_heads(row_ptr, col_idx, g, b_q2.to(g.dtype), ctx.heads)
+            if b_scale is not None:
+                ci = col_idx.long()
+                inside = (ci >= 0) & (ci < b_scale.numel())
+                s = torch.where(inside, b_scale[ci.clamp(0, max(b_scale.numel() - 1, 0))],
+                                torch.zeros((), dtype=b_scale.dtype, device=b_scale.device))
+                d_values = (d_values.to(torch.float32) * s.unsqueeze(1)).to(g.dtype)
+        return None, None, d_values, None, None, None, None, None
+
+
+def spmm_fp8(row_ptr, col_idx, values, m, k, b_q, b_scale=None, *, out=None):
+    """`spmm` over a feature table stored in FP8: b_q is torch.float8_e4m3fn or torch.float8_e5m2,
+    [K, N] with values [nnz] (or [nnz, 1]) or [K, H, D] with values [nnz, H]; b_scale an optional
+    float32 [K] scale per row of b_q (`quantize_rows_fp8` makes the pair).  values is float32,
+    float16 or bfloat16 and so is the result, [M, N] or [M, H, D]:
+        out[r, h, :] = sum_j (values[j, h] * b_scale[col[j]]) * b_q[col[j], h, :]
+    in one launch for all heads (op "spmm_csr_heads_fp8"), accumulated in float32, with exactly the
+    bits of `spmm` on the scaled values rounded to the dtype and on b_q.to(dtype); without b_scale,
+    those of `spmm(values, b_q.to(dtype))`.  The gathered rows are one byte per element.
+
+    Differentiable in values only (b_q and b_scale get no gradient): the gradient is
+    sddmm(d(out), b_q.to(dtype)) * b_scale[col].  That backward dequantises the whole of b_q to the
+    values' dtype, K * N elements each time it runs; an FP8 SDDMM does not exist yet.  `out=` is
+    only accepted when no gradient is being recorded."""
+    if not isinstance(b_q, torch.Tensor) or b_q.dtype not in FP8_MAX:
+        raise TypeError("spmm_fp8: b_q should be float8_e4m3fn or float8_e5m2, got "
+                        f"{getattr(b_q, 'dtype', type(b_q).__name__)}")
+    m, k = int(m), int(k)
+    if b_q.dim() == 3:
+        heads, d = b_q.shape[1], b_q.shape[2]
+        if values.dim() != 2 or values.shape[1] != heads:
+            raise RuntimeError("spmm_fp8: a multi-head b_q [K, H, D] needs values [nnz, H], got "
+                               f"{tuple(values.shape)} for b_q {tuple(b_q.shape)}")
+        b2, vals, shape = _heads_2d(b_q, "b_q"), values, (m, heads, d)
+    elif b_q.dim() == 2:
+        if values.dim() == 2 and values.shape[1] != 1:
+            raise RuntimeError("spmm_fp8: b_q [K, N] needs values [nnz] or [nnz, 1], got "
+                               f"{tuple(values.shape)}")
+        heads, b2, shape = 1, b_q, (m, b_q.shape[1])
+        vals = values.reshape(-1, 1) if values.dim() == 1 else values
+    else:
+        raise RuntimeError(f"spmm_fp8: b_q should be [K, N] or [K, H, D], got {tuple(b_q.shape)}")
+    if _recording("spmm_fp8", out, values):
+        return SpmmFp8Function.apply(row_ptr, col_idx, vals, m, k, b2, b_scale, heads).view(shape)
+    out2 = None
+    if out is not None:
+        if tuple(out.shape) != shape or (len(shape) == 3 and not out.is_contiguous()):
+            raise RuntimeError(f"spmm_fp8: out must be a {shape} tensor"
+                               f"{' (contiguous)' if len(shape) == 3 else ''}, got "
+                               f"{tuple(out.shape)}")
+        out2 = out.view(m, -1) if len(shape) == 3 else out
+    res = _C.spmm_csr_heads_fp8(row_ptr, col_idx, vals, m, k, b2, b_scale, out=out2)
+    return out if out is not None else res.view(shape)
+
+
 class EdgeSoftmaxFunction(torch.autograd.Function):
     """y = edge_softmax(row_ptr, e) for e [nnz] or [nnz, H], differentiable in e.  The output is
     saved and the backward is one launch of op "edge_softmax_csr_grad" (for [nnz, H]:

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._C import current_stream_handle, dtype_code
+from ._C import FP8_FORMATS, current_stream_handle, dtype_code
 from ._lib import LIB, Options, check
 
 INT64_MAX = (1 << 63) - 1
@@ -247,6 +247,39 @@ def spmm_csr_heads(row_ptr, col_idx, values, b, m, k, heads, *, out=None, row_be
     return out
 
 
+def spmm_csr_heads_fp8(row_ptr, col_idx, values, b_q, b_scale, m, k, heads, *, b_format=None,
+                       val_dtype=None, out=None, row_begin=0, row_end=None,
+                       options: Options | None = None, num_threads: int = 0,
+                       workspace_bytes: int | None = None):
+    """The multi-head SpMM over an FP8 table at the C-ABI (ofx_spmm_csr_heads_fp8 on device
+    tensors, the kCPU kernel ofx_spmm_csr_heads_fp8_cpu on host tensors): values [nnz, heads]
+    contiguous, b_q [K, heads * D] of a torch FP8 dtype (or uint8 codes with b_format given) with
+    unit column stride, b_scale float32 [K] or None -> out [row_end - row_begin, heads * D] of
+    values' dtype.  b_format / val_dtype: the codes to pass instead of the tensors' own;
+    workspace_bytes: the device workspace to pass instead of the query's size (tests)."""
+    row_end = m if row_end is None else row_end
+    n, nnz = b_q.shape[1], col_idx.numel()
+    d = n // heads if heads else 0
+    if out is None:
+        out = torch.empty((row_end - row_begin, n), dtype=values.dtype, device=values.device)
+    fmt = FP8_FORMATS[b_q.dtype] if b_format is None else int(b_format)
+    idt = dtype_code(row_ptr.dtype)
+    vdt = dtype_code(values.dtype) if val_dtype is None else int(val_dtype)
+    popt = ctypes.byref(options) if options else None
+    body = (idt, vdt, fmt, m, k, heads, d, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(values),
+            _nz(b_q), b_q.stride(0), _nz(b_scale), _nz(out), out.stride(0), row_begin, row_end)
+    if values.device.type == "cpu":
+        check(LIB.ofx_spmm_csr_heads_fp8_cpu(int(num_threads), *body, popt),
+              "spmm_csr_heads_fp8_cpu")
+        return out
+    wbuf, ws = _workspace(values.device, "spmm_csr_heads_fp8",
+                          LIB.ofx_spmm_csr_heads_fp8_workspace_size, idt, vdt, fmt, m, k, heads, d,
+                          nnz, popt, workspace_bytes=workspace_bytes)
+    check(LIB.ofx_spmm_csr_heads_fp8(current_stream_handle(values), *body, wbuf.data_ptr(), ws,
+                                     popt), "spmm_csr_heads_fp8")
+    return out
+
+
 def sddmm_csr_heads(row_ptr, col_idx, a, b, m, k, heads, *, out=None, row_begin=0, row_end=None,
                     num_threads: int = 0, workspace_bytes: int | None = None):
     """The multi-head SDDMM at the C-ABI (ofx_sddmm_csr_heads / ofx_sddmm_csr_heads_cpu by device):
@@ -390,6 +423,6 @@ def csr_row_slice(row_ptr, row_begin: int, row_end: int):
 
 __all__ = ["make_options", "default_split", "workspace_size", "SpmmCsrKernel", "spmm_csr_device",
            "describe",
-           "spmm_csr_gathered", "spmm_csr_heads", "sddmm_csr_heads", "gatv2_scores_csr_heads",
+           "spmm_csr_gathered", "spmm_csr_heads", "spmm_csr_heads_fp8", "sddmm_csr_heads", "gatv2_scores_csr_heads",
            "gatv2_scores_csr_heads_grad",
            "spmm_csr_cpu", "validate_csr", "csr_row_slice", "INT64_MAX", "_lib"]

@@ -163,3 +163,55 @@ add_docstr(
 
     """,
 )
+
+add_docstr(
+    oneflow._C.spmm_csr_heads_fp8,
+    r"""
+    spmm_csr_heads_fp8(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b, b_scale=None, b_format=1) -> Tensor
+
+    The multi-head SpMM of ``spmm_csr_heads`` over a feature table stored in OCP FP8, one byte per
+    element, with an optional scale per row of the table, in one launch:
+
+    .. math::
+
+        out_{r,hD+c} = \sum_{j \in row(r)} (values_{j,h} \cdot b\_scale_{col_j}) \cdot \mathrm{dequant}(b_{col_j,hD+c})
+
+    The gathered rows of ``b`` are half the bytes of a bfloat16 table and a quarter of a float32
+    one.  The sum is accumulated in float32.
+
+    Args:
+        a_csr_row_ptr (Tensor): ``[M + 1]``, int32 or int64.
+        a_csr_col_idx (Tensor): ``[nnz]``, the dtype of ``a_csr_row_ptr``.  A column outside
+            ``[0, K)`` reads a zero row of ``b`` and the scale ``+0``.
+        a_csr_values (Tensor): ``[nnz, H]``, float32, float16 or bfloat16.
+        a_num_rows (int), a_num_cols (int): ``M`` and ``K``.
+        b (Tensor): ``[K, H * D]`` uint8, the FP8 codes; head ``h`` owns columns ``[h * D, (h + 1) * D)``.
+        b_scale (Tensor, optional): ``[K]`` float32, the scale of every row of ``b``.
+        b_format (int): 1 for ``e4m3fn`` (max 448), 2 for ``e5m2`` (max 57344).
+
+    Returns:
+        ``out`` of shape ``[M, H * D]`` and the dtype of ``a_csr_values``: exactly the bits of
+        ``spmm_csr_heads`` on the values times ``b_scale[col]`` rounded to the dtype and on ``b``
+        dequantised to the dtype (exact), identical on CPU and GPU.  Without ``b_scale`` the values
+        are used as they are.
+
+    Differentiable in ``a_csr_values`` only: the gradient is ``sddmm_csr_heads`` of the upstream
+    gradient and the dequantised table, times ``b_scale[col]``.  That backward dequantises the whole
+    table each time it runs.  ``b`` and ``b_scale`` have no gradient.
+
+    For example:
+
+    .. code-block:: python
+
+        >>> import oneflow as flow
+        >>> row_ptr = flow.tensor([0, 2, 3], dtype=flow.int32)
+        >>> col_idx = flow.tensor([0, 1, 1], dtype=flow.int32)
+        >>> values = flow.tensor([[1.0], [2.0], [4.0]])
+        >>> b = flow.tensor([[0x38, 0x40], [0xB8, 0x30]], dtype=flow.uint8)  # e4m3fn: 1, 2; -1, 0.5
+        >>> b_scale = flow.tensor([2.0, 0.5])
+        >>> flow._C.spmm_csr_heads_fp8(row_ptr, col_idx, values, 2, 2, b, b_scale, 1)
+        tensor([[ 1.0000,  4.5000],
+                [-2.0000,  1.0000]], dtype=oneflow.float32)
+
+    """,
+)
