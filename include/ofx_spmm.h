@@ -837,6 +837,39 @@ int ofx_coo_to_csr_cpu(int idx_dtype, int val_dtype, int64_t m, int64_t k, int64
                        const void* row, const void* col, const void* values, int merge_duplicates,
                        void* out_row_ptr, void* out_col_idx, void* out_values, int64_t* out_nnz);
 
+/* ---- neighbour sampling over CSR --------------------------------------------
+ * The mini-batch CSR of `num_seeds` seed nodes: output row i holds min(deg, fanout) entries of
+ * row v = seeds[i] of the m-row input, deg = row_ptr[v+1] - row_ptr[v], as positions p inside the
+ * row in ascending order (a sorted row stays sorted; the input's duplicate columns are kept):
+ *   out_col_idx = col_idx[row_ptr[v] + p] (columns stay global ids), out_edge_ids = row_ptr[v] + p
+ *   (may be NULL), out_row_ptr [num_seeds + 1] the scan of the row lengths, out_nnz its last entry
+ *   (device int64 scalar; host int64* for the CPU version).
+ * deg <= fanout keeps the whole row.  Otherwise the positions are a uniform subset without
+ * replacement by Floyd's algorithm: for t = 0..fanout-1, j = deg - fanout + t,
+ *   u = philox4x32_10(counter = (v & 0xffffffff, v >> 32, t, 0),
+ *                     key = (seed & 0xffffffff, seed >> 32))[0],   r = (u * (j + 1)) >> 32,
+ * keep r unless already kept, else j; then ascending.  The multiply-shift draw is biased by at
+ * most deg / 2^32.  The draw is keyed by the node id, not by its place among the seeds: a node's
+ * sample under one seed does not depend on the batch, and a repeated seed gives identical rows.
+ * Integers only: HIP kernel and kCPU kernel give the same bits for both index dtypes, and the
+ * kCPU kernel's do not depend on num_threads.
+ * All index arrays share idx_dtype.  Outputs must hold num_seeds * fanout entries (the upper
+ * bound).  1 <= fanout <= 64, else OFX_EINVAL; int32 needs num_seeds * fanout < 2^31; the device
+ * version needs num_seeds < 2^31.  A seed outside [0, m) or a row whose degree is outside
+ * [0, 2^31) is bad: its output row is empty and row_ptr is not read for it; the device version
+ * sets bad_flag (device uint32, may be NULL) non-zero, the CPU version returns OFX_EINVAL.
+ * Device version: asynchronous on `stream`, no allocation, no host synchronisation.             */
+int ofx_sample_neighbors_workspace_size(int idx_dtype, int64_t num_seeds, size_t* bytes);
+int ofx_sample_neighbors(void* stream, int idx_dtype, int64_t m, int64_t num_seeds,
+                         const void* row_ptr, const void* col_idx, const void* seeds, int fanout,
+                         uint64_t seed, void* out_row_ptr, void* out_col_idx,
+                         void* out_edge_ids /* may be NULL */, void* out_nnz /* device int64 */,
+                         void* bad_flag, void* workspace, size_t workspace_bytes);
+int ofx_sample_neighbors_cpu(int num_threads, int idx_dtype, int64_t m, int64_t num_seeds,
+                             const void* row_ptr, const void* col_idx, const void* seeds,
+                             int fanout, uint64_t seed, void* out_row_ptr, void* out_col_idx,
+                             void* out_edge_ids /* may be NULL */, int64_t* out_nnz);
+
 /* ---- fused-epilogue backward ------------------------------------------
  * For y = relu?(A @ b + bias?):  dx = relu ? (y > 0 ? dy : 0) : dy   (ReluGrad from the output,
  * oneflow/core/autograd/gradient_funcs/activation.cpp:195-205) and d_bias[j] = sum_i dx[i, j]

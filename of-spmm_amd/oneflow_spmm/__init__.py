@@ -24,19 +24,22 @@ GATv2 (x_row [M, H, D], x_col [K, H, D], att [H, D]; LeakyReLU between the gathe
 A feature table stored in FP8 (torch.float8_e4m3fn / float8_e5m2) with a float32 scale per row:
     b_q, b_scale = flow_spmm.quantize_rows_fp8(b)                                    # one-off
     out = flow_spmm.spmm_fp8(row_ptr, col_idx, values, M, K, b_q, b_scale)           # [M, N] / [M, H, D]
+A mini-batch: at most `fanout` sampled in-neighbours of each seed node, as a CSR the ops above take:
+    rp_s, ci_s, eid = flow_spmm.sample_neighbors(row_ptr, col_idx, seeds, fanout, seed=0)
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 
 Re-exports mirror python/oneflow/__init__.py:158-160 (`from oneflow._C import ... as mv`).
 """
-from . import _C, _lib, autograd, build, ops, synth  # noqa: F401
+from . import _C, _lib, autograd, build, ops, sampling, synth  # noqa: F401
 from ._C import spmm_csr, spmm_csr_reduce
 from ._lib import OfxError
 from .autograd import (csr_transpose, edge_softmax, fused_spmm, gat_attention, gat_softmax,
                        gatv2_attention, gatv2_scores, gatv2_softmax, graph_attention,
                        quantize_rows_fp8, sddmm, spmm, spmm_fp8, spmm_reduce)
 from .build import coo_to_csr
+from .sampling import sample_blocks, sample_neighbors
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "_C"]
+__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "sample_neighbors", "sample_blocks", "sampling", "_C"]

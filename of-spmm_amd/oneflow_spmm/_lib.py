@@ -258,6 +258,10 @@ def _load():
         "ofx_coo_to_csr_workspace_size": ([i32, i64, i64, i64, ctypes.POINTER(sz)], i32),
         "ofx_coo_to_csr": ([p, i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, p, p, p, sz], i32),
         "ofx_coo_to_csr_cpu": ([i32, i32, i64, i64, i64, p, p, p, i32, p, p, p, ctypes.POINTER(i64)], i32),
+        "ofx_sample_neighbors_workspace_size": ([i32, i64, ctypes.POINTER(sz)], i32),
+        "ofx_sample_neighbors": ([p, i32, i64, i64, p, p, p, i32, u64, p, p, p, p, p, p, sz], i32),
+        "ofx_sample_neighbors_cpu": ([i32, i32, i64, i64, p, p, p, i32, u64, p, p, p,
+                                      ctypes.POINTER(i64)], i32),
         "ofx_balanced_range": ([i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "ofx_csr_row_slice": ([p, i32, p, i64, i64, p], i32),
         "ofx_csr_row_slice_host": ([i32, p, i64, i64, p, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
