@@ -4,7 +4,8 @@
 // graph_attention_heads.hip).  Every unit takes these arithmetic steps from here, so the fused
 // kernel has the bits of the three ops' composition by construction (contract in
 // include/ofx_spmm.h).  Below them, the host side those units and the GATv2
-// units share: the layout ladders, the fast path's shape test and the per-nonzero ops' schedule.
+// units share: the layout ladders, the fast path's shape test, the per-nonzero ops' schedule and
+// the launch of the two sums over heads (spmm_heads.hip, spmm_heads_fp8.hip).
 // Included by HIP translation units only.
 #ifndef OFX_HEADS_STEPS_H_
 #define OFX_HEADS_STEPS_H_
@@ -302,6 +303,65 @@ int by_lane_group(int64_t lanes, F&& f) {
   if (lanes <= 16) return f(Int<16>{});
   if (lanes <= 32) return f(Int<32>{});
   return f(Int<64>{});
+}
+
+// The FP8 sum's fast path (spmm_heads_fp8.hip), a lane 16 one-byte columns: by_lane_group's steps
+// and one of 8 lanes, the N = 128 row (8 lanes, one 128-byte line).
+template <typename F>
+int by_fast_lanes(int64_t lanes, F&& f) {
+  if (lanes <= 1) return f(Int<1>{});
+  if (lanes <= 4) return f(Int<4>{});
+  if (lanes <= 8) return f(Int<8>{});
+  if (lanes <= 16) return f(Int<16>{});
+  if (lanes <= 32) return f(Int<32>{});
+  return f(Int<64>{});
+}
+
+// Its general path, a lane 4 columns by byte loads: no step of 32 lanes (the correctness path of
+// shapes no benchmark configuration takes: four kernels per type and format).
+template <typename F>
+int by_general_lanes(int64_t lanes, F&& f) {
+  if (lanes <= 1) return f(Int<1>{});
+  if (lanes <= 4) return f(Int<4>{});
+  if (lanes <= 16) return f(Int<16>{});
+  return f(Int<64>{});
+}
+
+// A launch of the sum SpMM over heads (spmm_heads.hip, spmm_heads_fp8.hip): rows [row_begin,
+// row_begin + nrows) of C; scale: the FP8 op's scale per row of B, NULL there and in the dense op.
+struct RowSumArgs {
+  hipStream_t s;
+  const void *rp, *col, *val, *b, *scale;
+  void* c;
+  int64_t ldb, ldc, m, row_begin, nrows, heads, d, nnz, k;
+  void* ws;
+  size_t ws_bytes;
+  const ofx_spmm_options* opts;
+};
+
+// The workspace of such a launch: the schedule is the sum op's, resolved from the width of ONE
+// head (the numeric contract); partials in the accumulation type.
+inline size_t row_sum_ws_bytes(int64_t nrows, int64_t nnz, int64_t heads, int64_t d, int val_dtype,
+                               const ofx_spmm_options* opts) {
+  return plan::ws_layout(nrows, nnz, heads * d, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
+                         resolve_schedule(d, opts)).total;
+}
+
+// The launch: the plan (with this launch's share of the nonzeros for the automatic heavy
+// threshold), kernel(grid, block_base, plan) over the items in groups of `lpr` lanes, the hub sum.
+template <typename T, typename I, typename K>
+int launch_row_sum(const char* fn, const RowSumArgs& a, int lpr, K&& kernel) {
+  const int64_t n = a.heads * a.d;
+  Planned p;
+  int rc = prepare_plan<I>(fn, a.s, static_cast<const I*>(a.rp), a.row_begin, a.nrows, a.nnz,
+                           launch_nnz(a.m, a.nrows, a.nnz, a.opts), n,
+                           sizeof(typename Num<T>::acc), resolve_schedule(a.d, a.opts), false,
+                           a.ws, a.ws_bytes, &p);
+  if (rc) return rc;
+  rc = launch_cut_grid(p.work, (kBlock / 64) * (64 / lpr),
+                       [&](dim3 grid, int64_t b0) { kernel(grid, b0, p); });
+  if (rc) return rc;
+  return launch_hub_sum(a.s, p, static_cast<T*>(a.c), a.ldc, a.nrows, n);
 }
 
 }  // namespace

@@ -220,6 +220,51 @@ static inline int check_no_plan_options(const char* fn, const ofx_spmm_options* 
   return OFX_OK;
 }
 
+// The entry checks of the sum SpMM over heads: "spmm_csr_heads", "spmm_csr_heads_fp8" and their
+// kCPU kernels.  b_format: the FP8 entries' format code, NULL for the dense ones.  The first part
+// is all a workspace query checks.
+static inline int check_heads_spmm_sizes(const char* fn, const int* b_format, int idx_dtype,
+                                         int val_dtype, int64_t m, int64_t k, int64_t heads,
+                                         int64_t d, int64_t nnz, const ofx_spmm_options* opts) {
+  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
+  if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
+  if (b_format != nullptr) {
+    OFX_REQUIRE(val_dtype != OFX_DT_DOUBLE, OFX_EUNSUPPORTED,
+                "%s: value dtype double is not supported (float, float16, bfloat16)", fn);
+    OFX_REQUIRE(*b_format == OFX_FP8_E4M3 || *b_format == OFX_FP8_E5M2, OFX_EINVAL,
+                "%s: unknown FP8 format code %d (OFX_FP8_E4M3 / OFX_FP8_E5M2)", fn, *b_format);
+  }
+  return check_no_plan_options(fn, opts);
+}
+
+// device: a HIP entry (its wording of the NULL-pointer errors).  An FP8 table may be NULL with
+// k == 0.  *nothing: there is no output element to write.
+static inline int check_heads_spmm(const char* fn, bool device, const int* b_format, int idx_dtype,
+                                   int val_dtype, int64_t m, int64_t k, int64_t heads, int64_t d,
+                                   int64_t nnz, const void* row_ptr, const void* col_idx,
+                                   const void* values, const void* b, int64_t ldb, const void* c,
+                                   int64_t ldc, int64_t row_begin, int64_t row_end,
+                                   const ofx_spmm_options* opts, bool* nothing) {
+  if (const int rc = check_heads_spmm_sizes(fn, b_format, idx_dtype, val_dtype, m, k, heads, d,
+                                            nnz, opts))
+    return rc;
+  if (const int rc = check_row_range(fn, row_begin, row_end, m)) return rc;
+  const int64_t n = heads * d;
+  OFX_REQUIRE(ldb >= n && ldc >= n, OFX_EINVAL, "%s: ldb=%lld / ldc=%lld < n=%lld", fn,
+              (long long)ldb, (long long)ldc, (long long)n);
+  *nothing = row_end == row_begin || n == 0;
+  if (*nothing) return OFX_OK;
+  const bool edges = nnz == 0 || (col_idx && values && (b || (b_format != nullptr && k == 0)));
+  if (!device) {
+    OFX_REQUIRE(row_ptr && c && edges, OFX_EINVAL, "%s: NULL pointer", fn);
+    return OFX_OK;
+  }
+  OFX_REQUIRE(row_ptr && c, OFX_EINVAL, "%s: NULL row_ptr or output", fn);
+  OFX_REQUIRE(edges, OFX_EINVAL, "%s: NULL col_idx/values/%s with nnz=%lld", fn,
+              b_format != nullptr ? "b_q" : "b", (long long)nnz);
+  return OFX_OK;
+}
+
 // The caller's workspace against the `need` bytes of the launch's layout.
 static inline int check_workspace(const char* fn, const void* ws, size_t ws_bytes, size_t need) {
   OFX_REQUIRE(need == 0 || (ws != nullptr && ws_bytes >= need), OFX_EWORKSPACE,

@@ -77,45 +77,25 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-struct HeadsArgs {
-  hipStream_t s;
-  const void *rp, *col, *val, *b;
-  void* c;
-  int64_t ldb, ldc, m, row_begin, nrows, heads, d, nnz, k;
-  void* ws;
-  size_t ws_bytes;
-  const ofx_spmm_options* opts;
-};
-
+// The kernel of one layout, issued by the shared launch (heads_steps.h).
 template <typename T, typename I, int VEC, int LPR, bool HEADVEC>
-int heads_cfg(const HeadsArgs& a) {
-  using A = typename Num<T>::acc;
+int heads_cfg(const RowSumArgs& a) {
   constexpr int U = 8;
-  constexpr int64_t GPB = (kBlock / 64) * (64 / LPR);
-  const int64_t n = a.heads * a.d;
-  Planned p;
-  // the schedule: the sum op's, resolved from the width of ONE head (the numeric contract), with
-  // this launch's share of the nonzeros for the automatic heavy threshold
-  int rc = prepare_plan<I>("spmm_csr_heads", a.s, static_cast<const I*>(a.rp), a.row_begin,
-                           a.nrows, a.nnz, launch_nnz(a.m, a.nrows, a.nnz, a.opts), n, sizeof(A),
-                           resolve_schedule(a.d, a.opts), false, a.ws, a.ws_bytes, &p);
-  if (rc) return rc;
-  A* part = static_cast<A*>(p.wl.part);
-  rc = launch_cut_grid(p.work, GPB, [&](dim3 grid, int64_t b0) {
+  const char* fn = "spmm_csr_heads";
+  return launch_row_sum<T, I>(fn, a, LPR, [&](dim3 grid, int64_t b0, const Planned& p) {
     hipLaunchKernelGGL((spmm_heads_kernel<T, I, VEC, LPR, U, HEADVEC>), grid, dim3(kBlock), 0, a.s,
                        static_cast<const I*>(a.rp), static_cast<const I*>(a.col),
                        static_cast<const T*>(a.val), static_cast<const T*>(a.b), a.ldb, a.k,
-                       static_cast<T*>(a.c), a.ldc, a.row_begin, a.nrows, n, a.heads, a.d, p.chunk,
-                       p.wl.counters, p.wl.items, p.wl.order, part, b0, p.err);
+                       static_cast<T*>(a.c), a.ldc, a.row_begin, a.nrows, a.heads * a.d, a.heads,
+                       a.d, p.chunk, p.wl.counters, p.wl.items, p.wl.order,
+                       static_cast<typename Num<T>::acc*>(p.wl.part), b0, p.err);
   });
-  if (rc) return rc;
-  return launch_hub_sum(a.s, p, static_cast<T*>(a.c), a.ldc, a.nrows, n);
 }
 
 // One layout per width class: the lanes of a group cover the H*D columns in one tile up to
 // 64 * VEC of them; wider rows loop over tiles.
 template <typename T, typename I, bool HEADVEC>
-int heads_width(const HeadsArgs& a) {
+int heads_width(const RowSumArgs& a) {
   constexpr int VEC = 16 / sizeof(T);
   return by_lane_group((a.heads * a.d + VEC - 1) / VEC, [&](auto lpr) -> int {
     return heads_cfg<T, I, VEC, decltype(lpr)::value, HEADVEC>(a);
@@ -123,20 +103,13 @@ int heads_width(const HeadsArgs& a) {
 }
 
 template <typename T, typename I>
-int heads_typed(const HeadsArgs& a) {
+int heads_typed(const RowSumArgs& a) {
   constexpr int VEC = 16 / sizeof(T);
   // k == 0 (every column out of range, B may be empty) takes the general path: the fast one
   // loads unconditionally and needs a row 0 to read
   const bool headvec = a.d % VEC == 0 && a.k > 0 && rows_aligned(a.b, a.ldb, sizeof(T), VEC) &&
                        rows_aligned(a.c, a.ldc, sizeof(T), VEC);
   return headvec ? heads_width<T, I, true>(a) : heads_width<T, I, false>(a);
-}
-
-int check_heads_args(const char* fn, int idx_dtype, int val_dtype, int64_t m, int64_t k,
-                     int64_t heads, int64_t d, int64_t nnz, const ofx_spmm_options* opts) {
-  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
-  if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
-  return check_no_plan_options(fn, opts);
 }
 
 }  // namespace
@@ -150,11 +123,10 @@ extern "C" int ofx_spmm_csr_heads_workspace_size(int idx_dtype, int val_dtype, i
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "spmm_csr_heads_workspace_size: bytes is NULL");
     OFX_READ_OPTIONS(opts, "spmm_csr_heads_workspace_size");
-    if (const int rc = check_heads_args("spmm_csr_heads_workspace_size", idx_dtype, val_dtype, m,
-                                        k, heads, d, nnz, opts))
+    if (const int rc = check_heads_spmm_sizes("spmm_csr_heads_workspace_size", nullptr, idx_dtype,
+                                              val_dtype, m, k, heads, d, nnz, opts))
       return rc;
-    *bytes = plan::ws_layout(m, nnz, heads * d, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
-                             resolve_schedule(d, opts)).total;
+    *bytes = row_sum_ws_bytes(m, nnz, heads, d, val_dtype, opts);
     return OFX_OK;
   });
 }
@@ -168,23 +140,18 @@ extern "C" int ofx_spmm_csr_heads(void* stream, int idx_dtype, int val_dtype, in
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_TAKE_DEVICE_ERROR("spmm_csr_heads");  // an earlier launch's loud failure (spmm_plan.h)
     OFX_READ_OPTIONS(opts, "spmm_csr_heads");
-    int rc = check_heads_args("spmm_csr_heads", idx_dtype, val_dtype, m, k, heads, d, nnz, opts);
-    if (rc) return rc;
-    const int64_t n = heads * d;
-    rc = check_reduce_args("spmm_csr_heads", idx_dtype, val_dtype, m, k, n, nnz, ldb, ldc, false,
-                           0, row_begin, row_end);
-    if (rc) return rc;
+    bool nothing = false;
+    int rc = check_heads_spmm("spmm_csr_heads", true, nullptr, idx_dtype, val_dtype, m, k, heads, d,
+                              nnz, row_ptr, col_idx, values, b, ldb, c, ldc, row_begin, row_end,
+                              opts, &nothing);
+    if (rc || nothing) return rc;
     const int64_t nrows = row_end - row_begin;
-    if (nrows == 0 || n == 0) return OFX_OK;  // nothing to write
-    OFX_REQUIRE(row_ptr && c, OFX_EINVAL, "spmm_csr_heads: NULL row_ptr or output");
-    OFX_REQUIRE(nnz == 0 || (col_idx && values && b), OFX_EINVAL,
-                "spmm_csr_heads: NULL col_idx/values/b with nnz=%lld", (long long)nnz);
     // these entries' wording of the size error, ahead of the shared check
-    const size_t need = plan::ws_layout(nrows, nnz, n, val_dtype == OFX_DT_DOUBLE ? 8 : 4,
-                                        resolve_schedule(d, opts)).total;
+    const size_t need = row_sum_ws_bytes(nrows, nnz, heads, d, val_dtype, opts);
     if ((rc = check_workspace("spmm_csr_heads", workspace, workspace_bytes, need))) return rc;
-    const HeadsArgs a{static_cast<hipStream_t>(stream), row_ptr, col_idx, values, b, c, ldb, ldc,
-                      m, row_begin, nrows, heads, d, nnz, k, workspace, workspace_bytes, opts};
+    const RowSumArgs a{static_cast<hipStream_t>(stream), row_ptr, col_idx, values, b, nullptr, c,
+                       ldb, ldc, m, row_begin, nrows, heads, d, nnz, k, workspace, workspace_bytes,
+                       opts};
     return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
       return heads_typed<std::remove_pointer_t<decltype(tp)>,
                          std::remove_pointer_t<decltype(ip)>>(a);

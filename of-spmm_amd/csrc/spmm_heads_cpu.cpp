@@ -15,19 +15,6 @@
 #include "spmm_common.h"
 #include "spmm_rows_cpu.h"
 
-namespace ofx {
-namespace {
-
-int check_heads_sizes(const char* fn, int idx_dtype, int val_dtype, int64_t m, int64_t k,
-                      int64_t heads, int64_t d, int64_t nnz, int64_t row_begin, int64_t row_end) {
-  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
-  if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
-  return check_row_range(fn, row_begin, row_end, m);
-}
-
-}  // namespace
-}  // namespace ofx
-
 using namespace ofx;
 
 extern "C" int ofx_spmm_csr_heads_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
@@ -38,16 +25,12 @@ extern "C" int ofx_spmm_csr_heads_cpu(int num_threads, int idx_dtype, int val_dt
                                       const ofx_spmm_options* opts) {
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_READ_OPTIONS(opts, "spmm_csr_heads_cpu");
-    int rc = check_heads_sizes("spmm_csr_heads_cpu", idx_dtype, val_dtype, m, k, heads, d, nnz,
-                               row_begin, row_end);
-    if (rc) return rc;
-    if ((rc = check_no_plan_options("spmm_csr_heads_cpu", opts))) return rc;
-    const int64_t n = heads * d;
-    OFX_REQUIRE(ldb >= n && ldc >= n, OFX_EINVAL, "spmm_csr_heads_cpu: ldb=%lld / ldc=%lld < n=%lld",
-                (long long)ldb, (long long)ldc, (long long)n);
-    if (row_end == row_begin || n == 0) return OFX_OK;
-    OFX_REQUIRE(row_ptr && c && (nnz == 0 || (col_idx && values && b)), OFX_EINVAL,
-                "spmm_csr_heads_cpu: NULL pointer");
+    bool nothing = false;
+    if (const int rc = check_heads_spmm("spmm_csr_heads_cpu", false, nullptr, idx_dtype, val_dtype,
+                                        m, k, heads, d, nnz, row_ptr, col_idx, values, b, ldb, c,
+                                        ldc, row_begin, row_end, opts, &nothing))
+      return rc;
+    if (nothing) return OFX_OK;
     const Schedule s = resolve_schedule(d, opts);  // of ONE head's width: the numeric contract
     return by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
       using T = std::remove_pointer_t<decltype(tp)>;
@@ -66,10 +49,11 @@ extern "C" int ofx_sddmm_csr_heads_cpu(int num_threads, int idx_dtype, int val_d
                                        int64_t lda, const void* b, int64_t ldb, void* out,
                                        int64_t row_begin, int64_t row_end) {
   return ::ofx::guarded(__func__, [&]() -> int {
-    int rc = check_heads_sizes("sddmm_csr_heads_cpu", idx_dtype, val_dtype, m, k, heads, d, nnz,
-                               row_begin, row_end);
-    if (rc) return rc;
+    const char* fn = "sddmm_csr_heads_cpu";
+    if (const int rc = check_heads_shape(fn, heads, d)) return rc;
     const int64_t n = heads * d;
+    if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, n, nnz)) return rc;
+    if (const int rc = check_row_range(fn, row_begin, row_end, m)) return rc;
     OFX_REQUIRE(lda >= n && ldb >= n, OFX_EINVAL,
                 "sddmm_csr_heads_cpu: lda=%lld / ldb=%lld < n=%lld", (long long)lda,
                 (long long)ldb, (long long)n);

@@ -1,7 +1,8 @@
 // spmm_heads_fp8.h — what the HIP kernel (spmm_heads_fp8.hip) and the kCPU kernel
 // (spmm_heads_fp8_cpu.cpp) of op "spmm_csr_heads_fp8" share: the decoding of the two OCP FP8
-// formats in plain C++, the scaled value V' and the argument checks of the C-ABI entries
-// (contract in include/ofx_spmm.h).
+// formats in plain C++, the scaled value V' and the dispatch over the op's three value types
+// (contract in include/ofx_spmm.h; the entry checks are spmm_common.h's
+// check_heads_spmm).
 #ifndef OFX_SPMM_HEADS_FP8_H_
 #define OFX_SPMM_HEADS_FP8_H_
 
@@ -46,24 +47,6 @@ template <typename T>
 OFX_HD typename Num<T>::acc scaled_value(typename Num<T>::acc v, float s) {
 #pragma clang fp contract(off)
   return gv2::rounded<T>(v * s);
-}
-
-static inline int check_format(const char* fn, int b_format) {
-  OFX_REQUIRE(b_format == OFX_FP8_E4M3 || b_format == OFX_FP8_E5M2, OFX_EINVAL,
-              "%s: unknown FP8 format code %d (OFX_FP8_E4M3 / OFX_FP8_E5M2)", fn, b_format);
-  return OFX_OK;
-}
-
-// What the three entries refuse ahead of their own pointer and workspace checks.
-static inline int check_fp8_args(const char* fn, int idx_dtype, int val_dtype, int b_format,
-                                 int64_t m, int64_t k, int64_t heads, int64_t d, int64_t nnz,
-                                 const ofx_spmm_options* opts) {
-  if (const int rc = check_heads_shape(fn, heads, d)) return rc;
-  if (const int rc = check_types_sizes(fn, idx_dtype, val_dtype, m, k, heads * d, nnz)) return rc;
-  OFX_REQUIRE(val_dtype != OFX_DT_DOUBLE, OFX_EUNSUPPORTED,
-              "%s: value dtype double is not supported (float, float16, bfloat16)", fn);
-  if (const int rc = check_format(fn, b_format)) return rc;
-  return check_no_plan_options(fn, opts);
 }
 
 // Dispatch over the three value types of the op (f64 is refused before it).

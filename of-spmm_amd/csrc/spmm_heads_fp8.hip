@@ -21,7 +21,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "heads_steps.h"  // Int<>
+#include "heads_steps.h"  // the lane ladders and the launch path
 #include "spmm_heads_fp8.h"
 #include "spmm_items_dev.h"
 
@@ -29,6 +29,7 @@ namespace ofx {
 namespace {
 
 using namespace item;
+using namespace hsteps;
 
 constexpr int kFastCols = 16;  // columns per lane of the fast path: one 16-byte load
 constexpr int kSlowCols = 4;   // of the general path
@@ -220,66 +221,25 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-struct Fp8Args {
-  hipStream_t s;
-  const void *rp, *col, *val, *b, *scale;
-  void* c;
-  int64_t ldb, ldc, m, row_begin, nrows, heads, d, nnz, k;
-  void* ws;
-  size_t ws_bytes;
-  const ofx_spmm_options* opts;
-};
-
+// The kernel of one layout, issued by the shared launch (heads_steps.h).
 template <typename T, typename I, int FMT, int LPR, bool FAST, bool SCALED>
-int fp8_cfg(const Fp8Args& a) {
+int fp8_cfg(const RowSumArgs& a) {
   constexpr int U = 8;
-  constexpr int64_t GPB = (kBlock / 64) * (64 / LPR);
-  const int64_t n = a.heads * a.d;
-  Planned p;
-  // the schedule: the sum op's, resolved from the width of ONE head (the numeric contract)
-  int rc = prepare_plan<I>("spmm_csr_heads_fp8", a.s, static_cast<const I*>(a.rp), a.row_begin,
-                           a.nrows, a.nnz, launch_nnz(a.m, a.nrows, a.nnz, a.opts), n,
-                           sizeof(float), resolve_schedule(a.d, a.opts), false, a.ws, a.ws_bytes,
-                           &p);
-  if (rc) return rc;
-  float* part = static_cast<float*>(p.wl.part);
-  rc = launch_cut_grid(p.work, GPB, [&](dim3 grid, int64_t b0) {
-    hipLaunchKernelGGL((spmm_heads_fp8_kernel<T, I, FMT, LPR, U, FAST, SCALED>), grid,
-                       dim3(kBlock), 0, a.s, static_cast<const I*>(a.rp),
-                       static_cast<const I*>(a.col), static_cast<const T*>(a.val),
-                       static_cast<const uint8_t*>(a.b), a.ldb,
-                       static_cast<const float*>(a.scale), a.k, static_cast<T*>(a.c), a.ldc,
-                       a.row_begin, a.nrows, n, a.heads, a.d, p.chunk, p.wl.counters, p.wl.items,
-                       p.wl.order, part, b0, p.err);
-  });
-  if (rc) return rc;
-  return launch_hub_sum(a.s, p, static_cast<T*>(a.c), a.ldc, a.nrows, n);
-}
-
-// The fast path's lane ladder: by_lane_group's steps and one of 8 lanes (N = 128 at 16 columns
-// per lane); a wider row loops over tiles of 64 lanes.
-template <typename F>
-int by_fast_lanes(int64_t lanes, F&& f) {
-  using hsteps::Int;
-  if (lanes <= 1) return f(Int<1>{});
-  if (lanes <= 4) return f(Int<4>{});
-  if (lanes <= 8) return f(Int<8>{});
-  if (lanes <= 16) return f(Int<16>{});
-  if (lanes <= 32) return f(Int<32>{});
-  return f(Int<64>{});
-}
-
-template <typename F>
-int by_general_lanes(int64_t lanes, F&& f) {
-  using hsteps::Int;
-  if (lanes <= 1) return f(Int<1>{});
-  if (lanes <= 4) return f(Int<4>{});
-  if (lanes <= 16) return f(Int<16>{});
-  return f(Int<64>{});
+  return launch_row_sum<T, I>(
+      "spmm_csr_heads_fp8", a, LPR, [&](dim3 grid, int64_t b0, const Planned& p) {
+        hipLaunchKernelGGL((spmm_heads_fp8_kernel<T, I, FMT, LPR, U, FAST, SCALED>), grid,
+                           dim3(kBlock), 0, a.s, static_cast<const I*>(a.rp),
+                           static_cast<const I*>(a.col), static_cast<const T*>(a.val),
+                           static_cast<const uint8_t*>(a.b), a.ldb,
+                           static_cast<const float*>(a.scale), a.k, static_cast<T*>(a.c), a.ldc,
+                           a.row_begin, a.nrows, a.heads * a.d, a.heads, a.d, p.chunk,
+                           p.wl.counters, p.wl.items, p.wl.order, static_cast<float*>(p.wl.part),
+                           b0, p.err);
+      });
 }
 
 template <typename T, typename I, int FMT>
-int fp8_typed(const Fp8Args& a) {
+int fp8_typed(const RowSumArgs& a) {
   const int64_t n = a.heads * a.d;
   // k == 0 (every column out of range, b_q may be empty) takes the general path: the fast one
   // loads unconditionally and needs a row 0 to read
@@ -296,11 +256,6 @@ int fp8_typed(const Fp8Args& a) {
   });
 }
 
-size_t fp8_ws_bytes(int64_t nrows, int64_t nnz, int64_t n, int64_t d,
-                    const ofx_spmm_options* opts) {
-  return plan::ws_layout(nrows, nnz, n, 4, resolve_schedule(d, opts)).total;
-}
-
 }  // namespace
 }  // namespace ofx
 
@@ -314,10 +269,10 @@ extern "C" int ofx_spmm_csr_heads_fp8_workspace_size(int idx_dtype, int val_dtyp
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_REQUIRE(bytes != nullptr, OFX_EINVAL, "spmm_csr_heads_fp8_workspace_size: bytes is NULL");
     OFX_READ_OPTIONS(opts, "spmm_csr_heads_fp8_workspace_size");
-    if (const int rc = fp8::check_fp8_args("spmm_csr_heads_fp8_workspace_size", idx_dtype,
-                                           val_dtype, b_format, m, k, heads, d, nnz, opts))
+    if (const int rc = check_heads_spmm_sizes("spmm_csr_heads_fp8_workspace_size", &b_format,
+                                              idx_dtype, val_dtype, m, k, heads, d, nnz, opts))
       return rc;
-    *bytes = fp8_ws_bytes(m, nnz, heads * d, d, opts);
+    *bytes = row_sum_ws_bytes(m, nnz, heads, d, val_dtype, opts);
     return OFX_OK;
   });
 }
@@ -332,23 +287,17 @@ extern "C" int ofx_spmm_csr_heads_fp8(void* stream, int idx_dtype, int val_dtype
   return ::ofx::guarded(__func__, [&]() -> int {
     OFX_TAKE_DEVICE_ERROR("spmm_csr_heads_fp8");  // an earlier launch's loud failure
     OFX_READ_OPTIONS(opts, "spmm_csr_heads_fp8");
-    int rc = fp8::check_fp8_args("spmm_csr_heads_fp8", idx_dtype, val_dtype, b_format, m, k, heads,
-                                 d, nnz, opts);
-    if (rc) return rc;
-    if ((rc = check_row_range("spmm_csr_heads_fp8", row_begin, row_end, m))) return rc;
-    const int64_t n = heads * d;
-    OFX_REQUIRE(ldb >= n && ldc >= n, OFX_EINVAL, "spmm_csr_heads_fp8: ldb=%lld / ldc=%lld < n=%lld",
-                (long long)ldb, (long long)ldc, (long long)n);
+    bool nothing = false;
+    int rc = check_heads_spmm("spmm_csr_heads_fp8", true, &b_format, idx_dtype, val_dtype, m, k,
+                              heads, d, nnz, row_ptr, col_idx, values, b_q, ldb, c, ldc, row_begin,
+                              row_end, opts, &nothing);
+    if (rc || nothing) return rc;
     const int64_t nrows = row_end - row_begin;
-    if (nrows == 0 || n == 0) return OFX_OK;  // nothing to write
-    OFX_REQUIRE(row_ptr && c, OFX_EINVAL, "spmm_csr_heads_fp8: NULL row_ptr or output");
-    OFX_REQUIRE(nnz == 0 || (col_idx && values && (b_q || k == 0)), OFX_EINVAL,
-                "spmm_csr_heads_fp8: NULL col_idx/values/b_q with nnz=%lld", (long long)nnz);
-    const size_t need = fp8_ws_bytes(nrows, nnz, n, d, opts);
+    const size_t need = row_sum_ws_bytes(nrows, nnz, heads, d, val_dtype, opts);
     if ((rc = check_workspace("spmm_csr_heads_fp8", workspace, workspace_bytes, need))) return rc;
-    const Fp8Args a{static_cast<hipStream_t>(stream), row_ptr, col_idx, values, b_q, b_scale, c,
-                    ldb, ldc, m, row_begin, nrows, heads, d, nnz, b_q ? k : 0, workspace,
-                    workspace_bytes, opts};
+    const RowSumArgs a{static_cast<hipStream_t>(stream), row_ptr, col_idx, values, b_q, b_scale, c,
+                       ldb, ldc, m, row_begin, nrows, heads, d, nnz, b_q ? k : 0, workspace,
+                       workspace_bytes, opts};
     return fp8::by_types(idx_dtype, val_dtype, [&](auto* tp, auto* ip) -> int {
       using T = std::remove_pointer_t<decltype(tp)>;
       using I = std::remove_pointer_t<decltype(ip)>;

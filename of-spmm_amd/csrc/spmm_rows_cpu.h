@@ -1,8 +1,9 @@
 // spmm_rows_cpu.h — the row templates of the kCPU SpMM and SDDMM kernels: one for the sum (ops
-// "spmm_csr", "fused_spmm_csr", "spmm_csr_heads") and one for the SDDMM ("sddmm_csr", its masked
-// form, "sddmm_csr_heads"), each over `heads` heads of width d.  The single-head ops are the
-// one-head case (heads = 1, d = n: the value stride is 1 and the column base 0), so every entry
-// adds and rounds in the same order, the contract's (spmm_common.h; DESIGN.md §3f for the heads).
+// "spmm_csr", "fused_spmm_csr", "spmm_csr_heads", "spmm_csr_heads_fp8") and one for the SDDMM
+// ("sddmm_csr", its masked form, "sddmm_csr_heads"), each over `heads` heads of width d.  The
+// single-head ops are the one-head case (heads = 1, d = n: the value stride is 1 and the column
+// base 0), so every entry adds and rounds in the same order, the contract's (spmm_common.h;
+// DESIGN.md §3f for the heads).
 // Host code of the *_cpu.cpp units, which are built with -fopenmp.
 #ifndef OFX_SPMM_ROWS_CPU_H_
 #define OFX_SPMM_ROWS_CPU_H_
@@ -16,22 +17,34 @@
 
 namespace ofx {
 
+// The source of B of the sum's row template: the value of a nonzero given its column (`in`: the
+// column lies in [0, k)) and element c of its gathered row.  The dense source: rows of T, the value
+// as it is.  The FP8 source is spmm_heads_fp8_cpu.cpp's (codes through a table, the value scaled).
+template <typename T>
+struct DenseRows {
+  using elem = T;
+  typename Num<T>::acc value(typename Num<T>::acc v, int64_t, bool) const { return v; }
+  typename Num<T>::acc at(const T* brow, int64_t c) const { return Num<T>::load(brow[c]); }
+};
+
 // Nonzeros [j0, j1) of one head: acc[c] = sum of mul(val[j*vs], B[col[j], c]) from +0, ascending.
 // A column outside [0, k): the reference CPU gather zero-fills the gathered row of an index >= the
 // table size (oneflow/user/kernels/gather_kernel_util.cpp:84-89), so the nonzero adds val * 0; a
 // negative index fails its CHECK_GE (:80), reported by the entries as OFX_EINVAL (`neg`).
-template <typename T, typename I>
-void row_sum(const I* col, const T* val, int64_t vs, const T* B, int64_t ldb, int64_t k, int64_t d,
-             int64_t j0, int64_t j1, typename Num<T>::acc* acc, bool* neg) {
+template <typename T, typename I, typename Src>
+void row_sum(const Src& src, const I* col, const T* val, int64_t vs, const typename Src::elem* B,
+             int64_t ldb, int64_t k, int64_t d, int64_t j0, int64_t j1, typename Num<T>::acc* acc,
+             bool* neg) {
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
   for (int64_t c = 0; c < d; ++c) acc[c] = A(0);
   for (int64_t j = j0; j < j1; ++j) {
-    const A v = Num<T>::load(val[j * vs]);
     const int64_t cj = (int64_t)col[j];
-    if (cj >= 0 && cj < k) {
-      const T* brow = B + cj * ldb;
-      for (int64_t c = 0; c < d; ++c) acc[c] = acc[c] + Num<T>::mul(v, Num<T>::load(brow[c]));
+    const bool in = cj >= 0 && cj < k;
+    const A v = src.value(Num<T>::load(val[j * vs]), cj, in);
+    if (in) {
+      const typename Src::elem* brow = B + cj * ldb;
+      for (int64_t c = 0; c < d; ++c) acc[c] = acc[c] + Num<T>::mul(v, src.at(brow, c));
     } else {  // the zero-filled gathered row
       if (cj < 0) *neg = true;
       for (int64_t c = 0; c < d; ++c) acc[c] = acc[c] + Num<T>::mul(v, A(0));
@@ -42,11 +55,13 @@ void row_sum(const I* col, const T* val, int64_t vs, const T* B, int64_t ldb, in
 // C[g, h*d + c] for rows [row_begin, row_end) and every head: a row of at most s.split nonzeros is
 // one in-order sum; a longer one is the in-order sum of its chunks' sums (num_chunks), then the
 // fused epilogue (none: one rounding to T).  val is [nnz, heads], B and C are [., heads * d], the
-// schedule that of ONE head's width.  OFX_EINVAL in `fn`'s name after a negative column.
-template <typename T, typename I>
+// schedule that of ONE head's width; `src` reads B (DenseRows: B is [., heads * d] of T).
+// OFX_EINVAL in `fn`'s name after a negative column.
+template <typename T, typename I, typename Src = DenseRows<T>>
 int cpu_spmm_rows(const char* fn, int nthreads, int64_t k, int64_t heads, int64_t d, const I* rp,
-                  const I* col, const T* val, const T* B, int64_t ldb, T* C, int64_t ldc,
-                  int64_t row_begin, int64_t row_end, const Schedule& s, const T* bias, int act) {
+                  const I* col, const T* val, const typename Src::elem* B, int64_t ldb, T* C,
+                  int64_t ldc, int64_t row_begin, int64_t row_end, const Schedule& s, const T* bias,
+                  int act, const Src& src = Src()) {
 #pragma clang fp contract(off)
   using A = typename Num<T>::acc;
   const int64_t rows = row_end - row_begin;
@@ -61,22 +76,29 @@ int cpu_spmm_rows(const char* fn, int nthreads, int64_t k, int64_t heads, int64_
       const int64_t j0 = (int64_t)rp[r], j1 = (int64_t)rp[r + 1];
       const int64_t len = j1 - j0;
       for (int64_t h = 0; h < heads; ++h) {
-        const T* vh = val + h;
-        const T* bh = B + h * d;
+        // NULL with nnz == 0 (and B with k == 0): never read, and no offset is formed from it
+        const T* vh = val != nullptr ? val + h : nullptr;
+        const typename Src::elem* bh = B != nullptr ? B + h * d : nullptr;
         if (len <= s.split) {
-          row_sum<T, I>(col, vh, heads, bh, ldb, k, d, j0, j1, acc.data(), &neg);
+          row_sum<T, I>(src, col, vh, heads, bh, ldb, k, d, j0, j1, acc.data(), &neg);
         } else {
           const int64_t nc = num_chunks(len, s.chunk);
           for (int64_t c = 0; c < d; ++c) acc[c] = A(0);
           for (int64_t q = 0; q < nc; ++q) {
             const int64_t a = j0 + q * s.chunk;
             const int64_t e = (q == nc - 1) ? j1 : a + s.chunk;
-            row_sum<T, I>(col, vh, heads, bh, ldb, k, d, a, e, part.data(), &neg);
+            row_sum<T, I>(src, col, vh, heads, bh, ldb, k, d, a, e, part.data(), &neg);
             for (int64_t c = 0; c < d; ++c) acc[c] = acc[c] + part[c];
           }
         }
         T* out = C + g * ldc + h * d;
-        for (int64_t c = 0; c < d; ++c) out[c] = epilogue<T>(acc[c], bias, h * d + c, act);
+        if (bias == nullptr && act == OFX_ACT_NONE) {
+          // the epilogue is the rounding alone; as a loop of its own it re-reads neither `bias`
+          // nor `act` per element (3 % of the FP8 entry's time at 4 x 32)
+          for (int64_t c = 0; c < d; ++c) out[c] = Num<T>::store(acc[c]);
+        } else {
+          for (int64_t c = 0; c < d; ++c) out[c] = epilogue<T>(acc[c], bias, h * d + c, act);
+        }
       }
     }
     any_neg = any_neg || neg;

@@ -57,9 +57,11 @@ def _csr_pair(row_ptr: torch.Tensor, col_idx: torch.Tensor):
     return _prep(row_ptr, "a_csr_row_ptr"), _prep(col_idx, "a_csr_col_idx")
 
 
-def desc(t: torch.Tensor) -> TensorDesc:
+def desc(t: torch.Tensor, dtype: int | None = None) -> TensorDesc:
+    """`dtype`: the code to describe `t` with where torch's dtype has none: an FP8 tensor travels
+    as its codes, kUInt8 (DataType has no 8-bit float; the format is attr b_format)."""
     d = TensorDesc()
-    d.dtype = dtype_code(t.dtype)
+    d.dtype = dtype_code(t.dtype) if dtype is None else dtype
     d.device = _device_index(t)
     d.ndim = t.dim()
     if d.ndim > 2:
@@ -462,20 +464,6 @@ def spmm_csr_heads(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
 FP8_FORMATS = {torch.float8_e4m3fn: _lib.FP8_E4M3, torch.float8_e5m2: _lib.FP8_E5M2}
 
 
-def _codes_desc(b_q: torch.Tensor) -> TensorDesc:
-    """The descriptor of an FP8 tensor as the op takes it: its codes as kUInt8 (DataType has no
-    8-bit float; the format travels in attr b_format)."""
-    d = TensorDesc()
-    d.dtype = _lib.DT_UINT8
-    d.device = _device_index(b_q)
-    d.ndim = b_q.dim()
-    for i in range(b_q.dim()):
-        d.shape[i] = b_q.shape[i]
-        d.stride[i] = b_q.stride(i)
-    d.data = b_q.data_ptr() if b_q.numel() > 0 else None
-    return d
-
-
 def spmm_csr_heads_fp8(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
                        a_csr_values: torch.Tensor, a_num_rows: int, a_num_cols: int,
                        b: torch.Tensor, b_scale: torch.Tensor | None = None, *,
@@ -518,8 +506,9 @@ def spmm_csr_heads_fp8(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     if out.numel() == 0:
         return out
     _two_phase(LIB.ofx_functional_spmm_csr_heads_fp8, vals,
-               _refs(rp, ci, vals) + (ctypes.byref(_codes_desc(bb)), r_scale, int(a_num_rows),
-                                      int(a_num_cols), FP8_FORMATS[bb.dtype]), _refs(out))
+               _refs(rp, ci, vals) + (ctypes.byref(desc(bb, _lib.DT_UINT8)), r_scale,
+                                      int(a_num_rows), int(a_num_cols), FP8_FORMATS[bb.dtype]),
+               _refs(out))
     return out
 
 

@@ -196,7 +196,6 @@ class _TransposeCache:
 
 
 TRANSPOSE_CACHE = _TransposeCache()
-_heads_grad_b = TRANSPOSE_CACHE.grad_b_heads  # the former name, for callers that still use it
 
 
 class SpmmCsrFunction(torch.autograd.Function):
@@ -299,6 +298,16 @@ class SddmmCsrHeadsFunction(torch.autograd.Function):
         return None, None, d_a, d_b
 
 
+def _out_2d(op, out, shape, what):
+    """The `out=` of a sum over heads as the [M, N] tensor the op writes (None without one): of
+    `shape`, and contiguous where that is [M, H, D]; `what` is the error's wording of it."""
+    if out is None:
+        return None
+    if tuple(out.shape) != shape or (len(shape) == 3 and not out.is_contiguous()):
+        raise RuntimeError(f"{op}: out must be {what}, got {tuple(out.shape)}")
+    return out.view(shape[0], shape[1] * shape[2]) if len(shape) == 3 else out
+
+
 def _spmm_heads(row_ptr, col_idx, values, m, k, b, out, reduce):
     """`spmm` with b [K, H, D]: values [nnz, H] -> [M, H, D]."""
     if reduce != "sum":
@@ -310,12 +319,7 @@ def _spmm_heads(row_ptr, col_idx, values, m, k, b, out, reduce):
     heads, d = b.shape[1], b.shape[2]
     if _recording("spmm", out, values, b):
         return SpmmCsrHeadsFunction.apply(row_ptr, col_idx, values, m, k, b)
-    out2 = None
-    if out is not None:
-        if tuple(out.shape) != (m, heads, d) or not out.is_contiguous():
-            raise RuntimeError(f"spmm: out must be a contiguous {(m, heads, d)} tensor, got "
-                               f"{tuple(out.shape)}")
-        out2 = out.view(m, heads * d)
+    out2 = _out_2d("spmm", out, (m, heads, d), f"a contiguous {(m, heads, d)} tensor")
     res = _C.spmm_csr_heads(row_ptr, col_idx, values, m, k, _heads_2d(b, "b"), out=out2)
     return out if out is not None else res.view(m, heads, d)
 
@@ -404,13 +408,8 @@ def spmm_fp8(row_ptr, col_idx, values, m, k, b_q, b_scale=None, *, out=None):
         raise RuntimeError(f"spmm_fp8: b_q should be [K, N] or [K, H, D], got {tuple(b_q.shape)}")
     if _recording("spmm_fp8", out, values):
         return SpmmFp8Function.apply(row_ptr, col_idx, vals, m, k, b2, b_scale, heads).view(shape)
-    out2 = None
-    if out is not None:
-        if tuple(out.shape) != shape or (len(shape) == 3 and not out.is_contiguous()):
-            raise RuntimeError(f"spmm_fp8: out must be a {shape} tensor"
-                               f"{' (contiguous)' if len(shape) == 3 else ''}, got "
-                               f"{tuple(out.shape)}")
-        out2 = out.view(m, -1) if len(shape) == 3 else out
+    out2 = _out_2d("spmm_fp8", out, shape,
+                   f"a {shape} tensor{' (contiguous)' if len(shape) == 3 else ''}")
     res = _C.spmm_csr_heads_fp8(row_ptr, col_idx, vals, m, k, b2, b_scale, out=out2)
     return out if out is not None else res.view(shape)
 

@@ -119,6 +119,24 @@ int main() {
                                 nullptr, 4, x, 4, 0, 1, &planned) == OFX_EINVAL, "planned accepted");
   EXPECT(ofx_sddmm_csr_heads_cpu(1, OFX_DT_INT32, OFX_DT_FLOAT, 1, 1, 1, 4096, 1, rp, rp, x, 4096,
                                  x, 4096, x, 0, 1) == OFX_EUNSUPPORTED, "d > 2048 accepted");
+  // nnz == 0 with NULL col_idx / values (and b): every row is +0 and no per-head base is formed
+  // from a NULL pointer (UBSan's pointer-overflow check stops at `NULL + h`)
+  const int32_t rp0[4] = {0, 0, 0, 0};
+  const float b4[4 * 15] = {};
+  for (const int64_t k : {(int64_t)0, (int64_t)4}) {
+    float out[3 * 15];
+    for (float& o : out) o = -77.0f;
+    const int rc = ofx_spmm_csr_heads_cpu(2, OFX_DT_INT32, OFX_DT_FLOAT, 3, k, 3, 5, 0, rp0,
+                                          nullptr, nullptr, k ? b4 : nullptr, 15, out, 15, 0, 3,
+                                          nullptr);
+    EXPECT(rc == OFX_OK, "nnz == 0, NULL bases, k=%lld rc=%d: %s", (long long)k, rc,
+           ofx_last_error());
+    for (const float o : out) {
+      uint32_t bits;
+      memcpy(&bits, &o, sizeof bits);
+      EXPECT(bits == 0u, "nnz == 0, k=%lld: element %g is not +0", (long long)k, (double)o);
+    }
+  }
   if (g_failures) {
     fprintf(stderr, "%d failures\n", g_failures);
     return 1;

@@ -500,7 +500,7 @@ def check_op_layer(dev):
     # the op's own inference (the functional entry, past the binding's checks)
     size = ctypes.c_size_t(0)
     descs = [ctypes.byref(_C.desc(t)) for t in (d_rp, d_ci, d_vals)]
-    bdesc = ctypes.byref(_C._codes_desc(bq))
+    bdesc = ctypes.byref(_C.desc(bq, _lib.DT_UINT8))
     for kw, word in ((dict(fmt=7), "b_format"), (dict(k=K + 1), "a_num_cols rows"),
                      (dict(scale=d_scale[:-1]), "b_scale")):
         sc = kw.get("scale", d_scale)
