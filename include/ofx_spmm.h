@@ -870,6 +870,37 @@ int ofx_sample_neighbors_cpu(int num_threads, int idx_dtype, int64_t m, int64_t 
                              int fanout, uint64_t seed, void* out_row_ptr, void* out_col_idx,
                              void* out_edge_ids /* may be NULL */, int64_t* out_nnz);
 
+/* ---- block compaction: unique and relabel over node ids -----------------------
+ * Turns the seeds and the sampled columns of a mini-batch into a block the ops train on:
+ *   out_src       the distinct values of seeds ∪ cols in ascending order (idx_dtype), *out_count of
+ *                 them (device int64 scalar; host int64* for the CPU version);
+ *   out_seed_pos  [n_seeds] int64: the position of seeds[i] in out_src;
+ *   out_col_local [n_cols] idx_dtype: the position of cols[j] in out_src.
+ * That is unique(concat(seeds, cols)) and the two searchsorted calls, without a sort: the ids live
+ * in [0, num_nodes), so a bitmap over the node ids (32-bit words, 128-bit granules, tiles of 32,768
+ * bits), the number of set bits in front of each granule and a population count give out_src in
+ * order and every position in O(1).  Integers only: HIP kernels and kCPU kernel give the same
+ * arrays for both index dtypes, and the kCPU kernel's do not depend on num_threads.
+ * seeds and cols share idx_dtype; either may be empty (its pointers may then be NULL).  out_src
+ * must hold min(n_seeds + n_cols, num_nodes) entries (the upper bound).  0 <= num_nodes < 2^31 and
+ * n_seeds + n_cols < 2^31, else OFX_EINVAL and nothing is launched.  An id outside [0, num_nodes)
+ * is bad and is never used as an address: the device version sets bad_flag (device uint32, may be
+ * NULL) non-zero, the CPU version returns OFX_EINVAL; the outputs are then unspecified.
+ * Device version: asynchronous on `stream`, no allocation, no host synchronisation.  Its workspace
+ * (bitmap, ranks, tile counts, the scan's scratch, the flag) grows with num_nodes, about
+ * num_nodes * 5 / 32 bytes, and must be 16-byte aligned (the bitmap is read in 16-byte granules),
+ * else OFX_EWORKSPACE.                                                                           */
+int ofx_compact_ids_workspace_size(int idx_dtype, int64_t num_nodes, int64_t n_seeds,
+                                   int64_t n_cols, size_t* bytes);
+int ofx_compact_ids(void* stream, int idx_dtype, int64_t num_nodes, int64_t n_seeds,
+                    const void* seeds, int64_t n_cols, const void* cols, void* out_src,
+                    void* out_seed_pos /* int64 */, void* out_col_local,
+                    void* out_count /* device int64 */, void* bad_flag, void* workspace,
+                    size_t workspace_bytes);
+int ofx_compact_ids_cpu(int num_threads, int idx_dtype, int64_t num_nodes, int64_t n_seeds,
+                        const void* seeds, int64_t n_cols, const void* cols, void* out_src,
+                        void* out_seed_pos /* int64 */, void* out_col_local, int64_t* out_count);
+
 /* ---- fused-epilogue backward ------------------------------------------
  * For y = relu?(A @ b + bias?):  dx = relu ? (y > 0 ? dy : 0) : dy   (ReluGrad from the output,
  * oneflow/core/autograd/gradient_funcs/activation.cpp:195-205) and d_bias[j] = sum_i dx[i, j]

@@ -262,6 +262,9 @@ def _load():
         "ofx_sample_neighbors": ([p, i32, i64, i64, p, p, p, i32, u64, p, p, p, p, p, p, sz], i32),
         "ofx_sample_neighbors_cpu": ([i32, i32, i64, i64, p, p, p, i32, u64, p, p, p,
                                       ctypes.POINTER(i64)], i32),
+        "ofx_compact_ids_workspace_size": ([i32, i64, i64, i64, ctypes.POINTER(sz)], i32),
+        "ofx_compact_ids": ([p, i32, i64, i64, p, i64, p, p, p, p, p, p, p, sz], i32),
+        "ofx_compact_ids_cpu": ([i32, i32, i64, i64, p, i64, p, p, p, p, ctypes.POINTER(i64)], i32),
         "ofx_balanced_range": ([i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "ofx_csr_row_slice": ([p, i32, p, i64, i64, p], i32),
         "ofx_csr_row_slice_host": ([i32, p, i64, i64, p, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),

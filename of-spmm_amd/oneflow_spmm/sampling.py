@@ -1,6 +1,7 @@
-"""Neighbour sampling over CSR: the step that makes a mini-batch.  HIP kernels on
-GPU tensors (csrc/sample_neighbors.hip), the kCPU kernel on CPU tensors
-(csrc/sample_neighbors_cpu.cpp); integers only, the same arrays from both.
+"""Neighbour sampling over CSR and block compaction: the steps that make a mini-batch (DESIGN.md
+§3k, §3l).  HIP kernels on GPU tensors (csrc/sample_neighbors.hip, csrc/compact_ids.hip), the kCPU
+kernels on CPU tensors (csrc/sample_neighbors_cpu.cpp, csrc/compact_ids_cpu.cpp); integers only,
+the same arrays from both.
 
 The sampled CSR feeds the ops as it is: its rows are the seeds, its columns stay global node ids,
 so `spmm(rp_s, ci_s, vals, S, K, b)` runs on the full feature table (FP8 tables included) and the
@@ -74,6 +75,54 @@ def sample_neighbors(row_ptr: torch.Tensor, col_idx: torch.Tensor, seeds: torch.
     return out_rp, out_ci[:n_out], (out_eid[:n_out] if out_eid is not None else None)
 
 
+def compact_block(seeds: torch.Tensor, cols: torch.Tensor, num_nodes: int, *, num_threads: int = 0):
+    """Returns (src, col_local, seed_pos) for node ids in [0, num_nodes): src holds the distinct
+    values of seeds ∪ cols in ascending order, col_local[j] is the position of cols[j] in src (both
+    in the input dtype) and seed_pos[i] the position of seeds[i] (int64): what
+    `torch.unique(torch.cat((seeds, cols)))` and two `torch.searchsorted` calls give, from a bitmap
+    over the node ids with rank and select instead of a sort.  seeds and cols are 1-D, share one
+    index dtype (int32 or int64) and one device, which chooses the kernel; either may be empty.
+    0 <= num_nodes < 2^31 and len(seeds) + len(cols) < 2^31.  An id outside [0, num_nodes) raises
+    RuntimeError ("outside"); it is never used as an address.  num_threads is the kCPU kernel's
+    (0: OpenMP's own count) and does not change the result."""
+    for name, t in (("seeds", seeds), ("cols", cols)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise RuntimeError(f"compact_block: {name} must be a 1-D tensor")
+    if seeds.dtype != cols.dtype:
+        raise TypeError("compact_block: seeds and cols must have the same index dtype")
+    if seeds.device != cols.device:
+        raise RuntimeError("compact_block: seeds and cols must be on one device")
+    seeds, cols = seeds.contiguous(), cols.contiguous()
+    it, dev = seeds.dtype, seeds.device
+    idt = dtype_code(it)
+    num_nodes, s, e = int(num_nodes), seeds.numel(), cols.numel()
+    ws_bytes = ctypes.c_size_t(0)
+    if dev.type != "cpu":  # refuses bad sizes before anything is allocated
+        check(LIB.ofx_compact_ids_workspace_size(idt, num_nodes, s, e, ctypes.byref(ws_bytes)),
+              "compact_block")
+    src = torch.empty(max(min(s + e, num_nodes), 0), dtype=it, device=dev)
+    col_local = torch.empty(e, dtype=it, device=dev)
+    seed_pos = torch.empty(s, dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
+    if dev.type == "cpu":
+        cnt = ctypes.c_int64(0)
+        check(LIB.ofx_compact_ids_cpu(int(num_threads), idt, num_nodes, s, ptr(seeds), e, ptr(cols),
+                                      ptr(src), ptr(seed_pos), ptr(col_local), ctypes.byref(cnt)),
+              "compact_block")
+        count = cnt.value
+    else:
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+        scalars = torch.zeros(2, dtype=torch.int64, device=dev)  # [count, bad flag]
+        check(LIB.ofx_compact_ids(current_stream_handle(seeds), idt, num_nodes, s, ptr(seeds), e,
+                                  ptr(cols), ptr(src), ptr(seed_pos), ptr(col_local),
+                                  scalars.data_ptr(), scalars.data_ptr() + 8, ws.data_ptr(),
+                                  ws_bytes.value), "compact_block")
+        count, bad = (int(x) for x in scalars.tolist())
+        if bad:
+            raise RuntimeError(f"compact_block: an id outside [0, {num_nodes})")
+    return src[:count], col_local, seed_pos
+
+
 def sample_blocks(row_ptr: torch.Tensor, col_idx: torch.Tensor, seeds: torch.Tensor, fanouts, *,
                   seed: int = 0):
     """The blocks of a multi-layer mini-batch, input layer first.  `fanouts` is given input layer
@@ -84,15 +133,23 @@ def sample_blocks(row_ptr: torch.Tensor, col_idx: torch.Tensor, seeds: torch.Ten
       col_local the block's columns as positions in src; seed_pos the block's seeds likewise
     so that one layer is `spmm(row_ptr_s, col_local, vals, len(seed_pos), len(src), h_src)` with
     h_src the features of src, and the next layer's h_src is that result (its rows are this block's
-    seeds, which are the next block's src).  Plain torch around `sample_neighbors`."""
+    seeds, which are the next block's src).  `sample_neighbors`, then `compact_block` over the
+    graph's rows.  A non-square CSR whose columns reach past its row count has ids that
+    `compact_block` refuses: such a layer takes the torch route (`unique` and `searchsorted`), which
+    gives the same arrays without a bound on the ids."""
     blocks = []
     cur = seeds
     fanouts = list(fanouts)
     for layer in reversed(range(len(fanouts))):  # from the output layer outwards
         rp_s, ci_s, eid = sample_neighbors(row_ptr, col_idx, cur, fanouts[layer], seed=seed + layer)
-        src = torch.unique(torch.cat((cur, ci_s)))
-        col_local = torch.searchsorted(src, ci_s).to(ci_s.dtype)
-        seed_pos = torch.searchsorted(src, cur)
+        try:
+            src, col_local, seed_pos = compact_block(cur, ci_s, row_ptr.numel() - 1)
+        except RuntimeError as err:
+            if "outside" not in str(err):
+                raise
+            src = torch.unique(torch.cat((cur, ci_s)))
+            col_local = torch.searchsorted(src, ci_s).to(ci_s.dtype)
+            seed_pos = torch.searchsorted(src, cur)
         blocks.append((rp_s, col_local, eid, src, seed_pos))
         cur = src
     return blocks[::-1]
