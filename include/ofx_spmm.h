@@ -901,6 +901,62 @@ int ofx_compact_ids_cpu(int num_threads, int idx_dtype, int64_t num_nodes, int64
                         const void* seeds, int64_t n_cols, const void* cols, void* out_src,
                         void* out_seed_pos /* int64 */, void* out_col_local, int64_t* out_count);
 
+/* ---- induced subgraph of a node set over CSR ---------------------------------
+ * The subgraph a ClusterGCN / GraphSAINT / ShaDow batch trains on: the rows of the chosen nodes
+ * restricted to the columns that were also chosen, both relabelled.  With m rows, nnz entries and
+ * `nodes` [n_nodes] (any order, repeats allowed, may be empty):
+ *   out_src       the distinct values of nodes in ascending order (idx_dtype), C of them;
+ *   out_node_pos  [n_nodes] int64: the position of nodes[i] in out_src (as ofx_compact_ids);
+ *   output row r  belongs to node out_src[r] and holds, in ascending j, the entries j of
+ *                 [row_ptr[src[r]], row_ptr[src[r] + 1]) whose col_idx[j] is a member of out_src (a
+ *                 sorted row stays sorted, duplicate columns are kept): out_edge_ids[p] = j (may be
+ *                 NULL), out_col_local[p] = the position of col_idx[j] in out_src;
+ *   out_row_ptr   [C + 1]: the scan of the row lengths, nnz_s its last entry.
+ * out_edge_ids is ascending over the whole output, so values[edge_ids] selects any per-edge tensor
+ * and the ops take (out_row_ptr, out_col_local) with m = k = C.  A column outside [0, m) (a
+ * non-square CSR) is no member and is dropped; it is range-checked before it touches the bitmap.
+ * Integers only: HIP kernels and kCPU kernel give the same arrays for both index dtypes, and the
+ * kCPU kernel's do not depend on num_threads.  All index arrays share idx_dtype.
+ * 0 <= m < 2^31, 0 <= nnz < 2^31 and n_nodes < 2^31, else OFX_EINVAL from every entry, the
+ * workspace-size query included, before anything is launched.  Bad and never used as an address: an
+ * id in nodes outside [0, m), a selected row whose degree is outside [0, 2^31) or whose entry range
+ * leaves [0, nnz) (and selected rows whose degrees sum past nnz).  The device version sets bad_flag
+ * (device uint32, may be NULL) non-zero, the CPU version returns OFX_EINVAL; the outputs are then
+ * unspecified.
+ * Two entries around the caller's one read-back, since the output sizes depend on the data:
+ *   count  writes out_src (min(n_nodes, m) slots, the upper bound), out_node_pos and
+ *          out_counts = {C, nnz_s} (device int64[2]; host for the CPU version) and leaves both
+ *          bitmaps and their ranks in the workspace;
+ *   fill   takes C and nnz_s as the caller read them, out_src as `src` and the same workspace, and
+ *          writes out_row_ptr [C + 1], out_col_local [nnz_s] and out_edge_ids [nnz_s]: no output
+ *          is nnz-sized.  It must follow its count on the same stream with the same m, nnz, n_nodes.
+ * Device version: asynchronous on `stream`, no allocation, no host synchronisation.  The workspace
+ * is a function of (idx_dtype, m, nnz, n_nodes) alone: the block compaction's over m, a bitmap with
+ * ranks over the nnz entries (about nnz * 5 / 32 bytes), 8 bytes per selected node and the scans'
+ * scratch; it must be 16-byte aligned, else OFX_EWORKSPACE.
+ * The CPU count entry also writes out_row_ptr (min(n_nodes, m) + 1 slots), which its fill entry
+ * reads back as row_ptr_s.                                                                       */
+int ofx_node_subgraph_workspace_size(int idx_dtype, int64_t m, int64_t nnz, int64_t n_nodes,
+                                     size_t* bytes);
+int ofx_node_subgraph_count(void* stream, int idx_dtype, int64_t m, int64_t nnz, int64_t n_nodes,
+                            const void* row_ptr, const void* col_idx, const void* nodes,
+                            void* out_src, void* out_node_pos /* int64 */,
+                            void* out_counts /* device int64[2] */, void* bad_flag, void* workspace,
+                            size_t workspace_bytes);
+int ofx_node_subgraph_fill(void* stream, int idx_dtype, int64_t m, int64_t nnz, int64_t n_nodes,
+                           int64_t count, int64_t nnz_s, const void* row_ptr, const void* col_idx,
+                           const void* src, void* out_row_ptr, void* out_col_local,
+                           void* out_edge_ids /* may be NULL */, void* workspace,
+                           size_t workspace_bytes);
+int ofx_node_subgraph_count_cpu(int num_threads, int idx_dtype, int64_t m, int64_t nnz,
+                                int64_t n_nodes, const void* row_ptr, const void* col_idx,
+                                const void* nodes, void* out_src, void* out_node_pos /* int64 */,
+                                void* out_row_ptr, int64_t* out_counts /* [2] */);
+int ofx_node_subgraph_fill_cpu(int num_threads, int idx_dtype, int64_t m, int64_t nnz,
+                               int64_t n_nodes, int64_t count, int64_t nnz_s, const void* row_ptr,
+                               const void* col_idx, const void* src, const void* row_ptr_s,
+                               void* out_col_local, void* out_edge_ids /* may be NULL */);
+
 /* ---- fused-epilogue backward ------------------------------------------
  * For y = relu?(A @ b + bias?):  dx = relu ? (y > 0 ? dy : 0) : dy   (ReluGrad from the output,
  * oneflow/core/autograd/gradient_funcs/activation.cpp:195-205) and d_bias[j] = sum_i dx[i, j]

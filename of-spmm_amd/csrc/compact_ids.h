@@ -85,6 +85,15 @@ static inline int check_compact_args(const char* fn, int idx_dtype, int64_t num_
   return OFX_OK;
 }
 
+#if defined(__HIPCC__) || defined(__HIP__)
+// What compact_ids.hip gives another device unit that stands on its bitmap (node_subgraph.hip):
+// where a compaction over num_nodes leaves the bitmap and the granule ranks in its workspace, and
+// the tile-count launch over any bitmap of this layout.  Host functions: the kernels stay where
+// they are.
+int compact_ws_layout(int64_t num_nodes, size_t* bitmap_off, size_t* rank_off, size_t* total);
+int launch_tile_counts(hipStream_t s, const uint4* bitmap, int64_t tiles, int* tile_count);
+#endif
+
 }  // namespace cid
 }  // namespace ofx
 

@@ -206,6 +206,23 @@ int compact(hipStream_t s, int64_t num_nodes, int64_t n_seeds, const I* seeds, i
 }
 
 }  // namespace
+
+int cid::compact_ws_layout(int64_t num_nodes, size_t* bitmap_off, size_t* rank_off, size_t* total) {
+  CompactWs w;
+  const int rc = compact_ws(num_nodes, &w);
+  *bitmap_off = w.bitmap;
+  *rank_off = w.rank;
+  *total = w.total;
+  return rc;
+}
+
+int cid::launch_tile_counts(hipStream_t s, const uint4* bitmap, int64_t tiles, int* tile_count) {
+  hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, s, bitmap,
+                     tile_count);
+  OFX_HIP_CHECK(hipGetLastError());
+  return OFX_OK;
+}
+
 }  // namespace ofx
 
 using namespace ofx;

@@ -265,6 +265,12 @@ def _load():
         "ofx_compact_ids_workspace_size": ([i32, i64, i64, i64, ctypes.POINTER(sz)], i32),
         "ofx_compact_ids": ([p, i32, i64, i64, p, i64, p, p, p, p, p, p, p, sz], i32),
         "ofx_compact_ids_cpu": ([i32, i32, i64, i64, p, i64, p, p, p, p, ctypes.POINTER(i64)], i32),
+        "ofx_node_subgraph_workspace_size": ([i32, i64, i64, i64, ctypes.POINTER(sz)], i32),
+        "ofx_node_subgraph_count": ([p, i32, i64, i64, i64, p, p, p, p, p, p, p, p, sz], i32),
+        "ofx_node_subgraph_fill": ([p, i32, i64, i64, i64, i64, i64, p, p, p, p, p, p, p, sz], i32),
+        "ofx_node_subgraph_count_cpu": ([i32, i32, i64, i64, i64, p, p, p, p, p, p,
+                                         ctypes.POINTER(i64)], i32),
+        "ofx_node_subgraph_fill_cpu": ([i32, i32, i64, i64, i64, i64, i64, p, p, p, p, p, p], i32),
         "ofx_balanced_range": ([i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "ofx_csr_row_slice": ([p, i32, p, i64, i64, p], i32),
         "ofx_csr_row_slice_host": ([i32, p, i64, i64, p, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),

@@ -1,7 +1,8 @@
-"""Neighbour sampling over CSR and block compaction: the steps that make a mini-batch (DESIGN.md
-§3k, §3l).  HIP kernels on GPU tensors (csrc/sample_neighbors.hip, csrc/compact_ids.hip), the kCPU
-kernels on CPU tensors (csrc/sample_neighbors_cpu.cpp, csrc/compact_ids_cpu.cpp); integers only,
-the same arrays from both.
+"""Neighbour sampling over CSR, block compaction and the subgraph induced by a node set: the steps
+that make a mini-batch.  HIP kernels on GPU tensors
+(csrc/sample_neighbors.hip, csrc/compact_ids.hip, csrc/node_subgraph.hip), the kCPU kernels on CPU
+tensors (csrc/sample_neighbors_cpu.cpp, csrc/compact_ids_cpu.cpp, csrc/node_subgraph_cpu.cpp);
+integers only, the same arrays from both.
 
 The sampled CSR feeds the ops as it is: its rows are the seeds, its columns stay global node ids,
 so `spmm(rp_s, ci_s, vals, S, K, b)` runs on the full feature table (FP8 tables included) and the
@@ -121,6 +122,75 @@ def compact_block(seeds: torch.Tensor, cols: torch.Tensor, num_nodes: int, *, nu
         if bad:
             raise RuntimeError(f"compact_block: an id outside [0, {num_nodes})")
     return src[:count], col_local, seed_pos
+
+
+def node_subgraph(row_ptr: torch.Tensor, col_idx: torch.Tensor, nodes: torch.Tensor, *,
+                  return_edge_ids: bool = True, num_threads: int = 0):
+    """The subgraph induced by a node set (ClusterGCN, GraphSAINT's node sampler, ShaDow batches).
+    Returns (src, row_ptr_s, col_local, edge_ids, node_pos): src holds the distinct values of
+    `nodes` in ascending order; row r of the CSR (row_ptr_s [C+1], col_local) belongs to node
+    src[r] and keeps, in their order, the entries of that row of the input whose column is a member
+    of src, as positions in src; edge_ids holds their places in col_idx (ascending over the whole
+    output, None with return_edge_ids=False) and node_pos[i] (int64) is the position of nodes[i] in
+    src.  So `spmm(row_ptr_s, col_local, values[edge_ids], C, C, h[src])` is a layer on the batch.
+    The other outputs are in the input dtype.  `nodes` is 1-D, in any order, may repeat and may be
+    empty; row_ptr, col_idx and nodes share one index dtype (int32 or int64) and one device, which
+    chooses the kernel.  A column outside [0, M) (a non-square CSR) is no member and is dropped.  An
+    id in nodes outside [0, M), or a selected row whose entry range is no row's, raises RuntimeError
+    ("outside"); neither is ever used as an address.  M, nnz and len(nodes) are below 2^31.
+    num_threads is the kCPU kernel's (0: OpenMP's own count) and does not change the result."""
+    for name, t in (("row_ptr", row_ptr), ("col_idx", col_idx), ("nodes", nodes)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise RuntimeError(f"node_subgraph: {name} must be a 1-D tensor")
+    if row_ptr.numel() < 1:
+        raise RuntimeError("node_subgraph: row_ptr must hold at least one entry")
+    if not (row_ptr.dtype == col_idx.dtype == nodes.dtype):
+        raise TypeError("node_subgraph: row_ptr, col_idx and nodes must have the same index dtype")
+    if not (row_ptr.device == col_idx.device == nodes.device):
+        raise RuntimeError("node_subgraph: row_ptr, col_idx and nodes must be on one device")
+    row_ptr, col_idx, nodes = row_ptr.contiguous(), col_idx.contiguous(), nodes.contiguous()
+    it, dev = row_ptr.dtype, row_ptr.device
+    idt = dtype_code(it)
+    m, nnz, s = row_ptr.numel() - 1, col_idx.numel(), nodes.numel()
+    ws_bytes = ctypes.c_size_t(0)
+    if dev.type != "cpu":  # refuses bad sizes before anything is allocated
+        check(LIB.ofx_node_subgraph_workspace_size(idt, m, nnz, s, ctypes.byref(ws_bytes)),
+              "node_subgraph")
+    src = torch.empty(min(s, m), dtype=it, device=dev)
+    node_pos = torch.empty(s, dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    new = lambda n: torch.empty(n, dtype=it, device=dev)  # noqa: E731
+    if dev.type == "cpu":
+        counts = (ctypes.c_int64 * 2)(0, 0)
+        rp_s = new(min(s, m) + 1)
+        check(LIB.ofx_node_subgraph_count_cpu(int(num_threads), idt, m, nnz, s, ptr(row_ptr),
+                                              ptr(col_idx), ptr(nodes), ptr(src), ptr(node_pos),
+                                              ptr(rp_s), counts), "node_subgraph")
+        count, nnz_s = counts[0], counts[1]
+        src, rp_s = src[:count], rp_s[:count + 1]
+        col_local, eid = new(nnz_s), (new(nnz_s) if return_edge_ids else None)
+        check(LIB.ofx_node_subgraph_fill_cpu(int(num_threads), idt, m, nnz, s, count, nnz_s,
+                                             ptr(row_ptr), ptr(col_idx), ptr(src), ptr(rp_s),
+                                             ptr(col_local), ptr(eid)), "node_subgraph")
+        return src, rp_s, col_local, eid, node_pos
+    stream = current_stream_handle(row_ptr)
+    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+    scalars = torch.zeros(3, dtype=torch.int64, device=dev)  # [C, nnz_s, bad flag]
+    check(LIB.ofx_node_subgraph_count(stream, idt, m, nnz, s, ptr(row_ptr), ptr(col_idx), ptr(nodes),
+                                      ptr(src), ptr(node_pos), scalars.data_ptr(),
+                                      scalars.data_ptr() + 16, ws.data_ptr(), ws_bytes.value),
+          "node_subgraph")
+    count, nnz_s, bad = (int(x) for x in scalars.tolist())  # the one read-back
+    if bad:
+        raise RuntimeError(f"node_subgraph: a node outside [0, {m}), or a selected row whose "
+                           f"degree is outside [0, 2^31) or whose entries are outside [0, {nnz})")
+    src = src[:count]
+    rp_s, col_local = new(count + 1), new(nnz_s)
+    eid = new(nnz_s) if return_edge_ids else None
+    check(LIB.ofx_node_subgraph_fill(stream, idt, m, nnz, s, count, nnz_s, ptr(row_ptr), ptr(col_idx),
+                                     ptr(src), ptr(rp_s), ptr(col_local), ptr(eid), ws.data_ptr(),
+                                     ws_bytes.value), "node_subgraph")
+    return src, rp_s, col_local, eid, node_pos
 
 
 def sample_blocks(row_ptr: torch.Tensor, col_idx: torch.Tensor, seeds: torch.Tensor, fanouts, *,
