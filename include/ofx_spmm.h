@@ -957,6 +957,48 @@ int ofx_node_subgraph_fill_cpu(int num_threads, int idx_dtype, int64_t m, int64_
                                const void* col_idx, const void* src, const void* row_ptr_s,
                                void* out_col_local, void* out_edge_ids /* may be NULL */);
 
+/* ---- random walks over CSR, uniform and node2vec ------------------------------
+ * num_walks walks of `length` steps over the m-row, nnz-entry CSR: out_walks [num_walks, length + 1]
+ * and out_edge_ids [num_walks, length] (may be NULL), row-major, in idx_dtype.  GraphSAINT's
+ * random-walk batches, PinSAGE neighbourhoods, DeepWalk and node2vec corpora.
+ *   walks[i, 0] = starts[i].  Step t = 1..length stands on v = walks[i, t-1].  The walk has ended if
+ *   v is no row (-1, or a column outside [0, m) of a non-square CSR) or deg(v) == 0: then
+ *   walks[i, t] = -1 and edge_ids[i, t-1] = -1.  Otherwise attempts a = 0, 1, ... are made:
+ *     (w0, w1, ., .) = philox4x32_10(counter = (i & 0xffffffff, i >> 32, t, a),
+ *                                    key = (seed & 0xffffffff, seed >> 32)),
+ *     r = (w0 * deg) >> 32,  e = row_ptr[v] + r,  x = col_idx[e].
+ *   At t == 1 attempt 0 is accepted.  At t >= 2, with u = walks[i, t-2], x is a *return* if x == u,
+ *   else *common* if the lower bound of x over row u finds it (lo = begin_u, hi = end_u; while
+ *   lo < hi: mid = lo + (hi - lo) / 2; col_idx[mid] < x ? lo = mid + 1 : hi = mid; found iff
+ *   lo < end_u && col_idx[lo] == x), else *out*; the attempt is accepted iff w1 < thr[class].
+ *   Attempt 255 is accepted whatever its class.  Then walks[i, t] = x, edge_ids[i, t-1] = e.
+ *   thr: with w = (1/p, 1, 1/q) for (return, common, out) in double and mx = max(w), thr_c = 2^32 if
+ *   w_c == mx, else floor((w_c / mx) * 4294967296.0), held as uint64.  p == q == 1 accepts every
+ *   attempt 0: the uniform walk.
+ * The counter holds the walk's index i, not the node: repeated starts give different walks, and a
+ * walk depends on (seed, i, starts[i]) alone.  The search is right for rows with ascending columns
+ * (what ofx_coo_to_csr emits; duplicates allowed); on other rows the result is still the loop
+ * above, stays inside the row and is the same on CPU and GPU.  Bias: the multiply-shift draw is off
+ * by at most deg / 2^32, and forcing attempt 255 moves at most (1 - min(thr) / 2^32)^256 of a
+ * step's probability (7e-8 at a ratio of 16 between the largest and the smallest weight).
+ * Integers only: HIP kernels and kCPU kernel give the same arrays for both index dtypes, and the
+ * kCPU kernel's do not depend on num_threads.  All index arrays share idx_dtype; output offsets are
+ * computed in 64 bits.
+ * 1 <= length <= 65535; m, nnz and num_walks in [0, 2^31); p and q finite and > 0: else OFX_EINVAL
+ * and nothing is launched.  Bad and never used as an address: a start outside [0, m), and a row a
+ * walk stands on whose degree is outside [0, 2^31) or whose entry range leaves [0, nnz); the walk
+ * ends there.  The device version sets bad_flag (device uint32, may be NULL; cleared first, also for
+ * num_walks == 0) non-zero, the CPU version returns OFX_EINVAL.
+ * Device version: asynchronous on `stream`, no workspace, no allocation, no host synchronisation. */
+int ofx_random_walk(void* stream, int idx_dtype, int64_t m, int64_t nnz, int64_t num_walks,
+                    const void* row_ptr, const void* col_idx, const void* starts, int length,
+                    double p, double q, uint64_t seed, void* out_walks,
+                    void* out_edge_ids /* may be NULL */, void* bad_flag);
+int ofx_random_walk_cpu(int num_threads, int idx_dtype, int64_t m, int64_t nnz, int64_t num_walks,
+                        const void* row_ptr, const void* col_idx, const void* starts, int length,
+                        double p, double q, uint64_t seed, void* out_walks,
+                        void* out_edge_ids /* may be NULL */);
+
 /* ---- fused-epilogue backward ------------------------------------------
  * For y = relu?(A @ b + bias?):  dx = relu ? (y > 0 ? dy : 0) : dy   (ReluGrad from the output,
  * oneflow/core/autograd/gradient_funcs/activation.cpp:195-205) and d_bias[j] = sum_i dx[i, j]

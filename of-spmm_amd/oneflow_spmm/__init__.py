@@ -30,6 +30,9 @@ and its block: the distinct ids of seeds and columns in order, and both relabell
     src, col_local, seed_pos = flow_spmm.compact_block(seeds, ci_s, num_nodes)
 The subgraph induced by a node set (ClusterGCN, GraphSAINT, ShaDow batches), relabelled to the set:
     src, rp_s, col_local, eid, node_pos = flow_spmm.node_subgraph(row_ptr, col_idx, nodes)
+Random walks, uniform or with node2vec's p and q, and the subgraph they induce (GraphSAINT-RW):
+    walks, eid = flow_spmm.random_walk(row_ptr, col_idx, starts, length, p=1.0, q=1.0, seed=0)
+    src, rp_s, col_local, eid, node_pos = flow_spmm.random_walk_subgraph(row_ptr, col_idx, starts, 2)
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 
@@ -42,8 +45,9 @@ from .autograd import (csr_transpose, edge_softmax, fused_spmm, gat_attention, g
                        gatv2_attention, gatv2_scores, gatv2_softmax, graph_attention,
                        quantize_rows_fp8, sddmm, spmm, spmm_fp8, spmm_reduce)
 from .build import coo_to_csr
-from .sampling import compact_block, node_subgraph, sample_blocks, sample_neighbors
+from .sampling import (compact_block, node_subgraph, random_walk, random_walk_subgraph,
+                       sample_blocks, sample_neighbors)
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "sampling", "_C"]
+__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "random_walk", "random_walk_subgraph", "sampling", "_C"]

@@ -1,8 +1,8 @@
-"""Neighbour sampling over CSR, block compaction and the subgraph induced by a node set: the steps
-that make a mini-batch.  HIP kernels on GPU tensors
-(csrc/sample_neighbors.hip, csrc/compact_ids.hip, csrc/node_subgraph.hip), the kCPU kernels on CPU
-tensors (csrc/sample_neighbors_cpu.cpp, csrc/compact_ids_cpu.cpp, csrc/node_subgraph_cpu.cpp);
-integers only, the same arrays from both.
+"""Neighbour sampling over CSR, block compaction, the subgraph induced by a node set and random
+walks: the steps that make a mini-batch.  HIP kernels on GPU tensors
+(csrc/sample_neighbors.hip, csrc/compact_ids.hip, csrc/node_subgraph.hip, csrc/random_walk.hip),
+the kCPU kernels on CPU tensors (csrc/sample_neighbors_cpu.cpp, csrc/compact_ids_cpu.cpp,
+csrc/node_subgraph_cpu.cpp, csrc/random_walk_cpu.cpp); integers only, the same arrays from both.
 
 The sampled CSR feeds the ops as it is: its rows are the seeds, its columns stay global node ids,
 so `spmm(rp_s, ci_s, vals, S, K, b)` runs on the full feature table (FP8 tables included) and the
@@ -191,6 +191,69 @@ def node_subgraph(row_ptr: torch.Tensor, col_idx: torch.Tensor, nodes: torch.Ten
                                      ptr(src), ptr(rp_s), ptr(col_local), ptr(eid), ws.data_ptr(),
                                      ws_bytes.value), "node_subgraph")
     return src, rp_s, col_local, eid, node_pos
+
+
+def random_walk(row_ptr: torch.Tensor, col_idx: torch.Tensor, starts: torch.Tensor, length: int, *,
+                p: float = 1.0, q: float = 1.0, seed: int = 0, return_edge_ids: bool = False,
+                num_threads: int = 0):
+    """Returns (walks [S, length + 1], edge_ids [S, length] or None): walks[i, 0] = starts[i] and
+    every further entry a neighbour of the one before, drawn uniformly (p == q == 1) or with
+    node2vec's bias against the node two steps back: weight 1/p for returning to it, 1 for one of
+    its neighbours, 1/q for any other node, by rejection over philox4x32-10 keyed by `seed` (taken
+    mod 2^64) and counted by the walk's index i, the step and the attempt.  edge_ids holds each
+    step's place in col_idx.  A walk that reaches a node without a row or without entries ends:
+    the rest of its row is -1 in both outputs.  `starts` may repeat (every walk is its own) and may
+    be empty; a walk depends on (seed, i, starts[i]) alone, and the CPU and the GPU give the same
+    arrays.  1 <= length <= 65535; p and q finite and > 0.  The three index tensors are 1-D and share
+    one dtype (int32 or int64) and one device, which chooses the kernel; the outputs have both.  A
+    start outside [0, M), or a row a walk reads whose degree is outside [0, 2^31) or whose entries
+    are outside [0, nnz), raises RuntimeError ("outside"); neither is ever used as an address.  The
+    neighbour test assumes rows with ascending columns (what `coo_to_csr` emits).  num_threads is
+    the kCPU kernel's (0: OpenMP's own count) and does not change the result."""
+    for name, t in (("row_ptr", row_ptr), ("col_idx", col_idx), ("starts", starts)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise RuntimeError(f"random_walk: {name} must be a 1-D tensor")
+    if row_ptr.numel() < 1:
+        raise RuntimeError("random_walk: row_ptr must hold at least one entry")
+    if not (row_ptr.dtype == col_idx.dtype == starts.dtype):
+        raise TypeError("random_walk: row_ptr, col_idx and starts must have the same index dtype")
+    if not (row_ptr.device == col_idx.device == starts.device):
+        raise RuntimeError("random_walk: row_ptr, col_idx and starts must be on one device")
+    row_ptr, col_idx, starts = row_ptr.contiguous(), col_idx.contiguous(), starts.contiguous()
+    it, dev = row_ptr.dtype, row_ptr.device
+    idt = dtype_code(it)
+    m, nnz, s = row_ptr.numel() - 1, col_idx.numel(), starts.numel()
+    length = int(length)
+    steps = min(max(length, 0), 65535)  # the entry refuses a length outside [1, 65535]
+    seed = ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+    walks = torch.empty((s, steps + 1), dtype=it, device=dev)
+    eid = torch.empty((s, steps), dtype=it, device=dev) if return_edge_ids else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    if dev.type == "cpu":
+        check(LIB.ofx_random_walk_cpu(int(num_threads), idt, m, nnz, s, ptr(row_ptr), ptr(col_idx),
+                                      ptr(starts), length, float(p), float(q), seed, ptr(walks),
+                                      ptr(eid)), "random_walk")
+        return walks, eid
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.ofx_random_walk(current_stream_handle(row_ptr), idt, m, nnz, s, ptr(row_ptr),
+                              ptr(col_idx), ptr(starts), length, float(p), float(q), seed,
+                              ptr(walks), ptr(eid), bad.data_ptr()), "random_walk")
+    if int(bad.item()):  # the one read-back
+        raise RuntimeError(f"random_walk: a start outside [0, {m}), or a walk read a row whose "
+                           f"degree is outside [0, 2^31) or whose entries are outside [0, {nnz})")
+    return walks, eid
+
+
+def random_walk_subgraph(row_ptr: torch.Tensor, col_idx: torch.Tensor, starts: torch.Tensor,
+                         length: int, *, p: float = 1.0, q: float = 1.0, seed: int = 0,
+                         return_edge_ids: bool = True, num_threads: int = 0):
+    """GraphSAINT's random-walk batch: `node_subgraph` of the nodes the walks of `random_walk`
+    visit (the entries >= 0 of `walks`, flattened), with its five outputs."""
+    walks, _ = random_walk(row_ptr, col_idx, starts, length, p=p, q=q, seed=seed,
+                           num_threads=num_threads)
+    nodes = walks.reshape(-1)
+    return node_subgraph(row_ptr, col_idx, nodes[nodes >= 0], return_edge_ids=return_edge_ids,
+                         num_threads=num_threads)
 
 
 def sample_blocks(row_ptr: torch.Tensor, col_idx: torch.Tensor, seeds: torch.Tensor, fanouts, *,
