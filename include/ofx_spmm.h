@@ -999,6 +999,40 @@ int ofx_random_walk_cpu(int num_threads, int idx_dtype, int64_t m, int64_t nnz, 
                         double p, double q, uint64_t seed, void* out_walks,
                         void* out_edge_ids /* may be NULL */);
 
+/* ---- per-row top-k selection over CSR ------------------------------------------
+ * Output row i keeps min(deg_i, k) entries of row i of the m-row, nnz-entry input: those with the
+ * largest keys (largest != 0) or the smallest (largest == 0), reported in ascending position order
+ * (a sorted row stays sorted): out_edge_ids[p] = j (may be NULL), out_col_idx[p] = col_idx[j],
+ * out_row_ptr [m + 1] the scan of the row lengths, out_nnz its last entry (device int64 scalar;
+ * host int64* for the CPU version).  The caller takes the kept values as values[edge_ids].
+ * Sparse attention (top-k scores between SDDMM and the edge softmax), kNN graphs, pruned diffusion
+ * matrices, TopKPooling (rows: the graphs of a batch), Gumbel top-k weighted sampling.
+ *   key: `values` [nnz] of val_dtype (float, double, float16, bfloat16) is read as unsigned
+ *   integers of its width; key = ~bits if the sign bit is set, else bits ^ sign bit; with
+ *   largest == 0 the key is complemented.  Keys compare as unsigned integers: -0 < +0, a NaN with
+ *   the sign clear is above +inf, one with the sign set below -inf.  Among equal keys the lower
+ *   position wins.  A row with deg <= k is copied whole.
+ * Every output is a function of the input bits alone: HIP kernels and kCPU kernel give the same
+ * arrays for every value and index dtype, and the kCPU kernel's do not depend on num_threads.
+ * All index arrays share idx_dtype.  The outputs must hold min(nnz, m * k) entries.
+ * k >= 1 (no upper bound), m and nnz in [0, 2^31): else OFX_EINVAL and nothing is launched.  A row
+ * whose degree is outside [0, 2^31) or whose entry range leaves [0, nnz) is bad and is never used
+ * as an address: the device version sets bad_flag (device uint32, may be NULL; cleared first)
+ * non-zero and writes no entry at all, the CPU version returns OFX_EINVAL.
+ * Device version: asynchronous on `stream`, no allocation, no host synchronisation.  The workspace
+ * is a function of (idx_dtype, m, nnz) alone: two row lists (at most nnz / 65 + nnz / 513 ints),
+ * the scan's scratch and the flag.                                                              */
+int ofx_row_topk_workspace_size(int idx_dtype, int64_t m, int64_t nnz, size_t* bytes);
+int ofx_row_topk(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t nnz,
+                 const void* row_ptr, const void* col_idx, const void* values, int64_t k,
+                 int largest, void* out_row_ptr, void* out_col_idx,
+                 void* out_edge_ids /* may be NULL */, void* out_nnz /* device int64 */,
+                 void* bad_flag, void* workspace, size_t workspace_bytes);
+int ofx_row_topk_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t nnz,
+                     const void* row_ptr, const void* col_idx, const void* values, int64_t k,
+                     int largest, void* out_row_ptr, void* out_col_idx,
+                     void* out_edge_ids /* may be NULL */, int64_t* out_nnz);
+
 /* ---- fused-epilogue backward ------------------------------------------
  * For y = relu?(A @ b + bias?):  dx = relu ? (y > 0 ? dy : 0) : dy   (ReluGrad from the output,
  * oneflow/core/autograd/gradient_funcs/activation.cpp:195-205) and d_bias[j] = sum_i dx[i, j]

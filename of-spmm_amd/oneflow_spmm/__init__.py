@@ -33,6 +33,8 @@ The subgraph induced by a node set (ClusterGCN, GraphSAINT, ShaDow batches), rel
 Random walks, uniform or with node2vec's p and q, and the subgraph they induce (GraphSAINT-RW):
     walks, eid = flow_spmm.random_walk(row_ptr, col_idx, starts, length, p=1.0, q=1.0, seed=0)
     src, rp_s, col_local, eid, node_pos = flow_spmm.random_walk_subgraph(row_ptr, col_idx, starts, 2)
+The k largest (or smallest) entries of every row, as a CSR the ops take (sparse attention, kNN graphs):
+    rp_s, ci_s, eid = flow_spmm.row_topk(row_ptr, col_idx, scores, k)                # scores[eid]
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 
@@ -45,9 +47,9 @@ from .autograd import (csr_transpose, edge_softmax, fused_spmm, gat_attention, g
                        gatv2_attention, gatv2_scores, gatv2_softmax, graph_attention,
                        quantize_rows_fp8, sddmm, spmm, spmm_fp8, spmm_reduce)
 from .build import coo_to_csr
-from .sampling import (compact_block, node_subgraph, random_walk, random_walk_subgraph,
+from .sampling import (compact_block, node_subgraph, random_walk, random_walk_subgraph, row_topk,
                        sample_blocks, sample_neighbors)
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "random_walk", "random_walk_subgraph", "sampling", "_C"]
+__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "random_walk", "random_walk_subgraph", "row_topk", "sampling", "_C"]

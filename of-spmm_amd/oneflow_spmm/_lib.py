@@ -275,6 +275,10 @@ def _load():
                              u64, p, p, p], i32),
         "ofx_random_walk_cpu": ([i32, i32, i64, i64, i64, p, p, p, i32, ctypes.c_double,
                                  ctypes.c_double, u64, p, p], i32),
+        "ofx_row_topk_workspace_size": ([i32, i64, i64, ctypes.POINTER(sz)], i32),
+        "ofx_row_topk": ([p, i32, i32, i64, i64, p, p, p, i64, i32, p, p, p, p, p, p, sz], i32),
+        "ofx_row_topk_cpu": ([i32, i32, i32, i64, i64, p, p, p, i64, i32, p, p, p,
+                              ctypes.POINTER(i64)], i32),
         "ofx_balanced_range": ([i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "ofx_csr_row_slice": ([p, i32, p, i64, i64, p], i32),
         "ofx_csr_row_slice_host": ([i32, p, i64, i64, p, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),

@@ -1,8 +1,9 @@
-"""Neighbour sampling over CSR, block compaction, the subgraph induced by a node set and random
-walks: the steps that make a mini-batch.  HIP kernels on GPU tensors
-(csrc/sample_neighbors.hip, csrc/compact_ids.hip, csrc/node_subgraph.hip, csrc/random_walk.hip),
-the kCPU kernels on CPU tensors (csrc/sample_neighbors_cpu.cpp, csrc/compact_ids_cpu.cpp,
-csrc/node_subgraph_cpu.cpp, csrc/random_walk_cpu.cpp); integers only, the same arrays from both.
+"""Neighbour sampling over CSR, block compaction, the subgraph induced by a node set, random walks
+and per-row top-k selection: the steps that make a mini-batch or prune a graph (DESIGN.md §3k, §3l,
+§3m, §3n, §3o).  HIP kernels on GPU tensors (csrc/sample_neighbors.hip, csrc/compact_ids.hip,
+csrc/node_subgraph.hip, csrc/random_walk.hip, csrc/row_topk.hip), the kCPU kernels on CPU tensors
+(csrc/sample_neighbors_cpu.cpp, csrc/compact_ids_cpu.cpp, csrc/node_subgraph_cpu.cpp,
+csrc/random_walk_cpu.cpp, csrc/row_topk_cpu.cpp); integers only, the same arrays from both.
 
 The sampled CSR feeds the ops as it is: its rows are the seeds, its columns stay global node ids,
 so `spmm(rp_s, ci_s, vals, S, K, b)` runs on the full feature table (FP8 tables included) and the
@@ -254,6 +255,72 @@ def random_walk_subgraph(row_ptr: torch.Tensor, col_idx: torch.Tensor, starts: t
     nodes = walks.reshape(-1)
     return node_subgraph(row_ptr, col_idx, nodes[nodes >= 0], return_edge_ids=return_edge_ids,
                          num_threads=num_threads)
+
+
+def row_topk(row_ptr: torch.Tensor, col_idx: torch.Tensor, values: torch.Tensor, k: int, *,
+             largest: bool = True, num_threads: int = 0):
+    """Returns (row_ptr_s [M+1], col_idx_s [nnz_s], edge_ids [nnz_s]): row i keeps the min(deg, k)
+    entries of row i with the largest values (the smallest with largest=False), in ascending
+    position order (a sorted CSR stays sorted and the ops take the result as it is); edge_ids holds
+    their places in col_idx, col_idx_s = col_idx[edge_ids], and the kept values are
+    `values[edge_ids]`, which carries the gradient.  Sparse attention between `sddmm` and
+    `edge_softmax`, kNN graphs, pruned diffusion matrices, TopKPooling.  Weighted sampling without
+    replacement of `fanout` neighbours is Gumbel top-k:
+        g = -torch.log(-torch.log(torch.rand_like(w)))
+        rp_s, ci_s, eid = row_topk(row_ptr, col_idx, torch.log(w) + g, fanout)
+    The order is that of the bit pattern: -0 < +0, a NaN with the sign clear ranks above +inf
+    (where torch.topk puts it), equal values go to the lower position: every output is a function
+    of the input bits, and the CPU and the GPU give the same arrays.  `values` is 1-D [nnz] in
+    float32, float64, float16 or bfloat16; row_ptr and col_idx share one index dtype (int32 or
+    int64); all three share one device, which chooses the kernel.  k >= 1, without an upper bound;
+    a row with deg <= k is copied whole.  M and nnz are below 2^31.  A row whose degree is outside
+    [0, 2^31) or whose entries are outside [0, nnz) raises RuntimeError ("outside"); it is never
+    used as an address.  num_threads is the kCPU kernel's (0: OpenMP's own count) and does not
+    change the result."""
+    for name, t in (("row_ptr", row_ptr), ("col_idx", col_idx), ("values", values)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise RuntimeError(f"row_topk: {name} must be a 1-D tensor")
+    if row_ptr.numel() < 1:
+        raise RuntimeError("row_topk: row_ptr must hold at least one entry")
+    if row_ptr.dtype != col_idx.dtype:
+        raise TypeError("row_topk: row_ptr and col_idx must have the same index dtype")
+    if not (row_ptr.device == col_idx.device == values.device):
+        raise RuntimeError("row_topk: row_ptr, col_idx and values must be on one device")
+    if values.numel() != col_idx.numel():
+        raise RuntimeError(f"row_topk: {values.numel()} values for {col_idx.numel()} entries")
+    k = int(k)
+    if k < 1:
+        raise RuntimeError(f"row_topk: k {k} is not >= 1")
+    row_ptr, col_idx, values = row_ptr.contiguous(), col_idx.contiguous(), values.detach().contiguous()
+    it, dev = row_ptr.dtype, row_ptr.device
+    idt, vdt = dtype_code(it), dtype_code(values.dtype)
+    m, nnz = row_ptr.numel() - 1, col_idx.numel()
+    ws_bytes = ctypes.c_size_t(0)
+    if dev.type != "cpu":  # refuses bad sizes before anything is allocated
+        check(LIB.ofx_row_topk_workspace_size(idt, m, nnz, ctypes.byref(ws_bytes)), "row_topk")
+    bound = min(nnz, m * k)
+    out_rp = torch.empty(m + 1, dtype=it, device=dev)
+    out_ci = torch.empty(bound, dtype=it, device=dev)
+    out_eid = torch.empty(bound, dtype=it, device=dev)
+    ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
+    if dev.type == "cpu":
+        cnt = ctypes.c_int64(0)
+        check(LIB.ofx_row_topk_cpu(int(num_threads), idt, vdt, m, nnz, ptr(row_ptr), ptr(col_idx),
+                                   ptr(values), k, int(bool(largest)), ptr(out_rp), ptr(out_ci),
+                                   ptr(out_eid), ctypes.byref(cnt)), "row_topk")
+        n_out = cnt.value
+    else:
+        ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+        scalars = torch.zeros(2, dtype=torch.int64, device=dev)  # [nnz_s, bad flag]
+        check(LIB.ofx_row_topk(current_stream_handle(row_ptr), idt, vdt, m, nnz, ptr(row_ptr),
+                               ptr(col_idx), ptr(values), k, int(bool(largest)), ptr(out_rp),
+                               ptr(out_ci), ptr(out_eid), scalars.data_ptr(),
+                               scalars.data_ptr() + 8, ws.data_ptr(), ws_bytes.value), "row_topk")
+        n_out, bad = (int(x) for x in scalars.tolist())  # the one read-back
+        if bad:
+            raise RuntimeError("row_topk: a row whose degree is outside [0, 2^31) or whose "
+                               f"entries are outside [0, {nnz})")
+    return out_rp, out_ci[:n_out], out_eid[:n_out]
 
 
 def sample_blocks(row_ptr: torch.Tensor, col_idx: torch.Tensor, seeds: torch.Tensor, fanouts, *,
