@@ -1033,6 +1033,67 @@ int ofx_row_topk_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, i
                      int largest, void* out_row_ptr, void* out_col_idx,
                      void* out_edge_ids /* may be NULL */, int64_t* out_nnz);
 
+/* ---- CSR x CSR -> CSR ----------------------------------------------------------
+ * C = A * B for A [m, k] with nnz_a entries and B [k, n] with nnz_b entries, both CSR: two-hop and
+ * metapath adjacencies, the powers of a diffusion matrix between row top-k steps, the composition
+ * of mini-batch blocks, coarsening S^T * A * S.
+ *   structure   output row i holds the distinct columns c for which some entry p of A's row i and
+ *               some entry q of B's row col_a[p] have col_b[q] == c, strictly ascending (the output
+ *               is a valid B).  An entry whose products cancel is kept: the structure does not
+ *               depend on the values.  out_row_ptr [m + 1] is the scan of the row lengths, nnz_c its
+ *               last entry.
+ *   values      ((+0 + t_1) + t_2) + ... over ascending p, then ascending q, of t = a_p * b_q rounded
+ *               to val_dtype (float, double, float16, bfloat16); summed in float (double for double)
+ *               and rounded once; no FMA.  Every output element is its own chain.
+ *   A           rows in any order, columns may repeat.  A column at or above k selects a zero row:
+ *               no product and no structural entry.  A negative column is bad.
+ *   B           rows strictly ascending with columns in [0, n) (what ofx_coo_to_csr emits with
+ *               merge_duplicates, and what this op emits); anything else is bad.
+ * Every output is a function of the input bits alone: HIP kernels and kCPU kernel give the same
+ * arrays for every value and index dtype, the kCPU kernel's do not depend on num_threads, and the
+ * device path's row classes change no bit.  All index arrays share idx_dtype.
+ * m, k, n, nnz_a, nnz_b in [0, 2^31), else OFX_EINVAL from every entry, the workspace-size query
+ * included, before anything is launched; nnz_c must be below 2^31 (the caller checks out_nnz).  Bad
+ * and never used as an address: a row of A or B whose degree is outside [0, 2^31) or whose entry
+ * range leaves [0, nnz), a negative column of A, a column of B outside [0, n), a row of B that is not
+ * strictly ascending.  The device version sets bad_flag (device uint32, may be NULL; cleared first):
+ * bit 0 for "outside", bit 1 for "not ascending"; the outputs are then zeros.  The CPU version returns
+ * OFX_EINVAL with "outside" or "ascending" in its message.
+ * Two entries around the caller's one read-back, since nnz_c depends on the data:
+ *   count  writes out_row_ptr [m + 1] and out_nnz (device int64; host for the CPU version) and
+ *          leaves the row classes' lists in the workspace;
+ *   fill   takes nnz_c as the caller read it and out_row_ptr as row_ptr_c, and writes out_col_idx
+ *          [nnz_c] and out_values [nnz_c].  va, vb and out_values all NULL: pattern only.  It must
+ *          follow its count on the same stream with the same arguments and workspace.
+ * Device version: asynchronous on `stream`, no allocation, no host synchronisation.  The workspace
+ * is a function of the size query's arguments alone: 8 bytes per row of A for the counts, four row
+ * lists of min(m, nnz_a) ints and the scan's scratch; nothing in it is sized by the number of
+ * products, and there is no hash table in global memory.  It must be 16-byte aligned, else
+ * OFX_EWORKSPACE.                                                                                 */
+int ofx_spgemm_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                              int64_t nnz_a, int64_t nnz_b, size_t* bytes);
+int ofx_spgemm_count(void* stream, int idx_dtype, int64_t m, int64_t k, int64_t n, int64_t nnz_a,
+                     int64_t nnz_b, const void* row_ptr_a, const void* col_idx_a,
+                     const void* row_ptr_b, const void* col_idx_b, void* out_row_ptr /* [m+1] */,
+                     void* out_nnz /* device int64 */, void* bad_flag, void* workspace,
+                     size_t workspace_bytes);
+int ofx_spgemm_fill(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                    int64_t nnz_a, int64_t nnz_b, int64_t nnz_c, const void* row_ptr_a,
+                    const void* col_idx_a, const void* values_a, const void* row_ptr_b,
+                    const void* col_idx_b, const void* values_b, const void* row_ptr_c,
+                    void* out_col_idx, void* out_values /* NULL: pattern only */, void* workspace,
+                    size_t workspace_bytes);
+int ofx_spgemm_count_cpu(int num_threads, int idx_dtype, int64_t m, int64_t k, int64_t n,
+                         int64_t nnz_a, int64_t nnz_b, const void* row_ptr_a,
+                         const void* col_idx_a, const void* row_ptr_b, const void* col_idx_b,
+                         void* out_row_ptr /* [m+1] */, int64_t* out_nnz);
+int ofx_spgemm_fill_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                        int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t nnz_c,
+                        const void* row_ptr_a, const void* col_idx_a, const void* values_a,
+                        const void* row_ptr_b, const void* col_idx_b, const void* values_b,
+                        const void* row_ptr_c, void* out_col_idx,
+                        void* out_values /* NULL: pattern only */);
+
 /* ---- fused-epilogue backward ------------------------------------------
  * For y = relu?(A @ b + bias?):  dx = relu ? (y > 0 ? dy : 0) : dy   (ReluGrad from the output,
  * oneflow/core/autograd/gradient_funcs/activation.cpp:195-205) and d_bias[j] = sum_i dx[i, j]

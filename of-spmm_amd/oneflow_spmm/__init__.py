@@ -35,6 +35,8 @@ Random walks, uniform or with node2vec's p and q, and the subgraph they induce (
     src, rp_s, col_local, eid, node_pos = flow_spmm.random_walk_subgraph(row_ptr, col_idx, starts, 2)
 The k largest (or smallest) entries of every row, as a CSR the ops take (sparse attention, kNN graphs):
     rp_s, ci_s, eid = flow_spmm.row_topk(row_ptr, col_idx, scores, k)                # scores[eid]
+The product of two CSR matrices as a CSR with ascending rows (two-hop and metapath graphs, diffusion):
+    rp_c, ci_c, v_c = flow_spmm.spgemm(rp_a, ci_a, v_a, rp_b, ci_b, v_b, n)          # A [M, K] @ B [K, n]
 Graph mode (UserKernel's CUDA-graph branch) is the compiled job's native hipGraph executable:
 `ccl.SpmmJob(..., graph=True)` over `ofx_spmm_job_set_graph`.
 
@@ -46,10 +48,10 @@ from ._lib import OfxError
 from .autograd import (csr_transpose, edge_softmax, fused_spmm, gat_attention, gat_softmax,
                        gatv2_attention, gatv2_scores, gatv2_softmax, graph_attention,
                        quantize_rows_fp8, sddmm, spmm, spmm_fp8, spmm_reduce)
-from .build import coo_to_csr
+from .build import coo_to_csr, spgemm
 from .sampling import (compact_block, node_subgraph, random_walk, random_walk_subgraph, row_topk,
                        sample_blocks, sample_neighbors)
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "random_walk", "random_walk_subgraph", "row_topk", "sampling", "_C"]
+__all__ = ["spmm", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "spgemm", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "random_walk", "random_walk_subgraph", "row_topk", "sampling", "_C"]

@@ -279,6 +279,14 @@ def _load():
         "ofx_row_topk": ([p, i32, i32, i64, i64, p, p, p, i64, i32, p, p, p, p, p, p, sz], i32),
         "ofx_row_topk_cpu": ([i32, i32, i32, i64, i64, p, p, p, i64, i32, p, p, p,
                               ctypes.POINTER(i64)], i32),
+        "ofx_spgemm_workspace_size": ([i32, i32, i64, i64, i64, i64, i64, ctypes.POINTER(sz)], i32),
+        "ofx_spgemm_count": ([p, i32, i64, i64, i64, i64, i64, p, p, p, p, p, p, p, p, sz], i32),
+        "ofx_spgemm_fill": ([p, i32, i32, i64, i64, i64, i64, i64, i64, p, p, p, p, p, p, p, p, p,
+                             p, sz], i32),
+        "ofx_spgemm_count_cpu": ([i32, i32, i64, i64, i64, i64, i64, p, p, p, p, p,
+                                  ctypes.POINTER(i64)], i32),
+        "ofx_spgemm_fill_cpu": ([i32, i32, i32, i64, i64, i64, i64, i64, i64, p, p, p, p, p, p, p,
+                                 p, p], i32),
         "ofx_balanced_range": ([i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "ofx_csr_row_slice": ([p, i32, p, i64, i64, p], i32),
         "ofx_csr_row_slice_host": ([i32, p, i64, i64, p, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
