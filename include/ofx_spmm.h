@@ -821,6 +821,90 @@ int ofx_spmm_csr_heads_fp8_cpu(int num_threads, int idx_dtype, int val_dtype, in
                                int64_t ldc, int64_t row_begin, int64_t row_end,
                                const ofx_spmm_options* opts);
 
+/* ---- SpMM over per-edge feature vectors (ops "spmm_csr_edge" / "_grad_e" / "_grad_b"; DESIGN.md
+ * §3q) ----------------------------------------------------------------------------------------
+ *   out[r, n] = sum over the row's nonzeros j of act(b[col_idx[j], n] op e[j, n])
+ * with a feature vector per edge: op = OFX_EDGE_MUL (CFConv / MPNN messages, DGL's u_mul_e) or
+ * OFX_EDGE_ADD (GINE with act = OFX_ACT_RELU, DGL's u_add_e), act = OFX_ACT_NONE or OFX_ACT_RELU.
+ * b T[k, n] with ldb, e and de T[nnz, n] row-major contiguous, c T[rows, n] with ldc, dy with lddy;
+ * `a` is the accumulation type (f64 for f64, else f32).
+ *
+ * Forward, for nonzero j of row r with column c = col_idx[j] and feature n:
+ *   1. z = load(b[c, n]) op load(e[j, n]): one operation in `a`, no FMA.  A column outside [0, k)
+ *      reads b = +0 and the same arithmetic proceeds.
+ *   2. t = z rounded to T as a step of its own (for mul: the rounding ofx_spmm_csr gives its
+ *      product).
+ *   3. relu: t = (t <= 0) ? +0 : t; NaN stays NaN, -0 becomes +0.
+ *   4. c[r, n] = the sum of t over ascending j from +0 in `a`, rounded once to T, under the hub
+ *      rule of resolve_schedule(n, opts) as ofx_spmm_csr applies it: a row of more than `split`
+ *      nonzeros is summed per chunk from +0 and the partials are added in chunk order.  An empty
+ *      row writes +0.  So with op = mul, no activation and e[j, :] = values[j] the output has
+ *      exactly the bits of ofx_spmm_csr.
+ *
+ * Gradients, from the upstream dy T[rows, n]; t is formed again by steps 1-2 and the relu's mask
+ * is (t > 0) (a NaN masks):
+ *   1. ofx_spmm_csr_edge_grad_e: de[j, n] = store(load(dy[r, n]) * load(b[c, n])) for mul, dy[r, n]
+ *      for add; +0 where masked.  Every de row of the range's nonzeros is written.
+ *   2. ofx_spmm_csr_edge_grad_b, on the transposed CSR of ofx_csr_transpose (row_ptr_t [k+1],
+ *      col_idx_t [nnz] = the rows of A, perm [nnz]): with G[j, n] = store(load(dy[r, n]) *
+ *      load(e[j, n])) for mul, dy[r, n] for add, +0 where masked, db has exactly the bits of
+ *      ofx_spmm_csr on (row_ptr_t, unit values) over the rows G[perm]: entries ascending, the hub
+ *      rule of resolve_schedule(n, opts).  G is never written.  The transpose dropped the columns
+ *      >= k, consistent with the forward's +0.
+ *
+ * Row range [row_begin, row_end): c and dy (d(e)), respectively b and db (d(b): rows of A^T), hold
+ * the rows from row_begin on; e and de are addressed at the global nonzero positions, d(b)'s dy is
+ * the whole [m, n].  Offsets are formed in 64 bits.  rows == 0 or n == 0 writes nothing; nnz == 0
+ * writes +0 rows (d(e): nothing).  `planned` and `variant` are refused (OFX_EINVAL).  Device
+ * versions: asynchronous on `stream`, no atomics, no allocation, no host synchronisation,
+ * capturable in a graph.  Workspace: the forward's and d(b)'s from their size entries (d(b)'s for
+ * the k rows of A^T); d(e)'s is ofx_sddmm_csr_heads_workspace_size's for (m, nnz) (its work items).
+ * OFX_EWORKSPACE when it is too small.  OFX_EINVAL: a negative size, a bad row range, an unknown
+ * op or activation code, a leading dimension below n, a NULL pointer, an output that overlaps an
+ * input; OFX_EUNSUPPORTED: a dtype.  Nothing is launched on an error.  HIP kernels and kCPU
+ * kernels give the same bits; the kCPU kernels' bits do not depend on num_threads.              */
+#define OFX_EDGE_MUL 0
+#define OFX_EDGE_ADD 1
+int ofx_spmm_csr_edge_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                                     int64_t nnz, const ofx_spmm_options* opts, size_t* bytes);
+int ofx_spmm_csr_edge(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                      int64_t nnz, const void* row_ptr, const void* col_idx,
+                      const void* e /* [nnz, n] */, const void* b, int64_t ldb, int op, int act,
+                      void* c, int64_t ldc, int64_t row_begin, int64_t row_end, void* workspace,
+                      size_t workspace_bytes, const ofx_spmm_options* opts);
+int ofx_spmm_csr_edge_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                          int64_t n, int64_t nnz, const void* row_ptr, const void* col_idx,
+                          const void* e, const void* b, int64_t ldb, int op, int act, void* c,
+                          int64_t ldc, int64_t row_begin, int64_t row_end,
+                          const ofx_spmm_options* opts);
+int ofx_spmm_csr_edge_grad_e(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                             int64_t n, int64_t nnz, const void* row_ptr, const void* col_idx,
+                             const void* e, const void* b, int64_t ldb, int op, int act,
+                             const void* dy, int64_t lddy, void* de /* [nnz, n] */,
+                             int64_t row_begin, int64_t row_end, void* workspace,
+                             size_t workspace_bytes);
+int ofx_spmm_csr_edge_grad_e_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                 int64_t k, int64_t n, int64_t nnz, const void* row_ptr,
+                                 const void* col_idx, const void* e, const void* b, int64_t ldb,
+                                 int op, int act, const void* dy, int64_t lddy, void* de,
+                                 int64_t row_begin, int64_t row_end);
+int ofx_spmm_csr_edge_grad_b_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                            int64_t n, int64_t nnz, const ofx_spmm_options* opts,
+                                            size_t* bytes);
+int ofx_spmm_csr_edge_grad_b(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                             int64_t n, int64_t nnz, const void* row_ptr_t,
+                             const void* col_idx_t, const void* perm, const void* e,
+                             const void* b, int64_t ldb, int op, int act, const void* dy,
+                             int64_t lddy, void* db, int64_t lddb, int64_t row_begin,
+                             int64_t row_end, void* workspace, size_t workspace_bytes,
+                             const ofx_spmm_options* opts);
+int ofx_spmm_csr_edge_grad_b_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m,
+                                 int64_t k, int64_t n, int64_t nnz, const void* row_ptr_t,
+                                 const void* col_idx_t, const void* perm, const void* e,
+                                 const void* b, int64_t ldb, int op, int act, const void* dy,
+                                 int64_t lddy, void* db, int64_t lddb, int64_t row_begin,
+                                 int64_t row_end, const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -1559,6 +1643,29 @@ int ofx_functional_spmm_csr_heads_fp8(void* stream, const ofx_tensor_desc* row_p
                                       const ofx_tensor_desc* b_scale, int64_t a_num_rows,
                                       int64_t a_num_cols, int64_t b_format, ofx_tensor_desc* out,
                                       void* tmp, size_t tmp_bytes, size_t* tmp_size_out);
+/* functional::SpmmCsrEdge / SpmmCsrEdgeGradE / SpmmCsrEdgeGradB: ops "spmm_csr_edge" (row_ptr
+ * [M+1], col_idx [nnz], e [nnz, N], b [K, N]; attrs a_num_rows, a_num_cols, op = OFX_EDGE_*, act =
+ * OFX_ACT_* -> out [M, N]), "spmm_csr_edge_grad_e" (+ dy [M, N] -> de [nnz, N]) and
+ * "spmm_csr_edge_grad_b" (the transposed CSR row_ptr_t [K+1], col_idx_t [nnz], perm [nnz]; e, b,
+ * dy [M, N] -> db [K, N]) of oneflow/user/ops/spmm_edge_op.cpp through the op-registry dispatch;
+ * the contract of ofx_spmm_csr_edge(_grad_e, _grad_b).  tmp_size_out != NULL: only the tmp size
+ * is computed.                                                                                   */
+int ofx_functional_spmm_csr_edge(void* stream, const ofx_tensor_desc* row_ptr,
+                                 const ofx_tensor_desc* col_idx, const ofx_tensor_desc* e,
+                                 const ofx_tensor_desc* b, int64_t a_num_rows, int64_t a_num_cols,
+                                 int64_t op, int64_t act, ofx_tensor_desc* out, void* tmp,
+                                 size_t tmp_bytes, size_t* tmp_size_out);
+int ofx_functional_spmm_csr_edge_grad_e(void* stream, const ofx_tensor_desc* row_ptr,
+                                        const ofx_tensor_desc* col_idx, const ofx_tensor_desc* e,
+                                        const ofx_tensor_desc* b, const ofx_tensor_desc* dy,
+                                        int64_t op, int64_t act, ofx_tensor_desc* de, void* tmp,
+                                        size_t tmp_bytes, size_t* tmp_size_out);
+int ofx_functional_spmm_csr_edge_grad_b(void* stream, const ofx_tensor_desc* row_ptr_t,
+                                        const ofx_tensor_desc* col_idx_t,
+                                        const ofx_tensor_desc* perm, const ofx_tensor_desc* e,
+                                        const ofx_tensor_desc* b, const ofx_tensor_desc* dy,
+                                        int64_t op, int64_t act, ofx_tensor_desc* db, void* tmp,
+                                        size_t tmp_bytes, size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

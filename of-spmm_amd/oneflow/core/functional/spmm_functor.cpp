@@ -924,6 +924,68 @@ extern "C" int ofx_functional_spmm_csr_heads_fp8(
   });
 }
 
+// ---- functional::SpmmCsrEdge and its gradient functors -------------------------------------------
+// Ops "spmm_csr_edge", "spmm_csr_edge_grad_e" and "spmm_csr_edge_grad_b"
+// (oneflow/user/ops/spmm_edge_op.cpp) through the same op-registry dispatch;
+// op and act are the ops' int64 attrs (OFX_EDGE_*, OFX_ACT_*).
+extern "C" int ofx_functional_spmm_csr_edge(void* stream, const ofx_tensor_desc* row_ptr,
+                                            const ofx_tensor_desc* col_idx,
+                                            const ofx_tensor_desc* e, const ofx_tensor_desc* b,
+                                            int64_t a_num_rows, int64_t a_num_cols, int64_t op,
+                                            int64_t act, ofx_tensor_desc* out, void* tmp,
+                                            size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(e != nullptr && b != nullptr, OFX_EINVAL, "spmm_csr_edge: NULL input e or b");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_edge");
+    return ToStatus(RunUserOp("spmm_csr_edge",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"e", e},
+                               {"b", b}},
+                              {{"out", out}},
+                              {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols}, {"op", op},
+                               {"act", act}},
+                              stream, tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
+extern "C" int ofx_functional_spmm_csr_edge_grad_e(void* stream, const ofx_tensor_desc* row_ptr,
+                                                   const ofx_tensor_desc* col_idx,
+                                                   const ofx_tensor_desc* e,
+                                                   const ofx_tensor_desc* b,
+                                                   const ofx_tensor_desc* dy, int64_t op,
+                                                   int64_t act, ofx_tensor_desc* de, void* tmp,
+                                                   size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(e != nullptr && b != nullptr && dy != nullptr, OFX_EINVAL,
+                "spmm_csr_edge_grad_e: NULL input e, b or dy");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_edge_grad_e");
+    return ToStatus(RunUserOp("spmm_csr_edge_grad_e",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx}, {"e", e},
+                               {"b", b}, {"dy", dy}},
+                              {{"de", de}}, {{"op", op}, {"act", act}}, stream, tmp, tmp_bytes,
+                              tmp_size_out));
+  });
+}
+
+extern "C" int ofx_functional_spmm_csr_edge_grad_b(void* stream, const ofx_tensor_desc* row_ptr_t,
+                                                   const ofx_tensor_desc* col_idx_t,
+                                                   const ofx_tensor_desc* perm,
+                                                   const ofx_tensor_desc* e,
+                                                   const ofx_tensor_desc* b,
+                                                   const ofx_tensor_desc* dy, int64_t op,
+                                                   int64_t act, ofx_tensor_desc* db, void* tmp,
+                                                   size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(perm != nullptr && e != nullptr && b != nullptr && dy != nullptr, OFX_EINVAL,
+                "spmm_csr_edge_grad_b: NULL input perm, e, b or dy");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_edge_grad_b");
+    return ToStatus(RunUserOp("spmm_csr_edge_grad_b",
+                              {{"a_csr_row_ptr", row_ptr_t}, {"a_csr_col_idx", col_idx_t},
+                               {"perm", perm}, {"e", e}, {"b", b}, {"dy", dy}},
+                              {{"db", db}}, {{"op", op}, {"act", act}}, stream, tmp, tmp_bytes,
+                              tmp_size_out));
+  });
+}
+
 // ---- functional::GraphAttentionCsrHeads ----------------------------------------------------------
 // Op "graph_attention_csr_heads" (oneflow/user/ops/graph_attention_heads_op.cpp) through the same
 // op-registry dispatch; two outputs.

@@ -434,3 +434,78 @@ def OneFlow_SpmmCsrHeadsFp8Op : OneFlow_BaseOp<"spmm_csr_heads_fp8", [NoSideEffe
   let has_data_type_infer_fn = 1;
   let has_input_arg_modify_fn = 1;
 }
+
+// The SpMM over per-edge feature vectors: e [nnz, N], b [K, N];
+// out[r, n] = sum over the row's nonzeros j of act(b[col[j], n] op e[j, n]) with op 0 = mul,
+// 1 = add and act 0 = none, 1 = relu, each message rounded to the dtype before the sum.
+// SBP: all-broadcast.
+def OneFlow_SpmmCsrEdgeOp : OneFlow_BaseOp<"spmm_csr_edge", [NoSideEffect, DeclareOpInterfaceMethods<UserOpCompatibleInterface>]> {
+  let input = (ins
+    OneFlow_Tensor:$a_csr_row_ptr,
+    OneFlow_Tensor:$a_csr_col_idx,
+    OneFlow_Tensor:$e,
+    OneFlow_Tensor:$b
+  );
+  let output = (outs
+    OneFlow_Tensor:$out
+  );
+  let attrs = (ins
+    DefaultValuedAttr<SI64Attr, "0">:$a_num_rows,
+    DefaultValuedAttr<SI64Attr, "0">:$a_num_cols,
+    DefaultValuedAttr<SI64Attr, "0">:$op,
+    DefaultValuedAttr<SI64Attr, "0">:$act
+  );
+  let has_logical_tensor_desc_infer_fn = 1;
+  let has_physical_tensor_desc_infer_fn = 1;
+  let has_get_sbp_fn = 1;
+  let has_data_type_infer_fn = 1;
+  let has_input_arg_modify_fn = 1;
+}
+
+// Its gradient in e from the upstream dy [M, N]: de [nnz, N].
+def OneFlow_SpmmCsrEdgeGradEOp : OneFlow_BaseOp<"spmm_csr_edge_grad_e", [NoSideEffect, DeclareOpInterfaceMethods<UserOpCompatibleInterface>]> {
+  let input = (ins
+    OneFlow_Tensor:$a_csr_row_ptr,
+    OneFlow_Tensor:$a_csr_col_idx,
+    OneFlow_Tensor:$e,
+    OneFlow_Tensor:$b,
+    OneFlow_Tensor:$dy
+  );
+  let output = (outs
+    OneFlow_Tensor:$de
+  );
+  let attrs = (ins
+    DefaultValuedAttr<SI64Attr, "0">:$op,
+    DefaultValuedAttr<SI64Attr, "0">:$act
+  );
+  let has_logical_tensor_desc_infer_fn = 1;
+  let has_physical_tensor_desc_infer_fn = 1;
+  let has_get_sbp_fn = 1;
+  let has_data_type_infer_fn = 1;
+  let has_input_arg_modify_fn = 1;
+}
+
+// Its gradient in b: db [K, N], summed over the transposed CSR (a_csr_row_ptr [K+1], a_csr_col_idx
+// = the rows of A, perm: csr_transpose's outputs) with the bits of spmm_csr on unit values.
+def OneFlow_SpmmCsrEdgeGradBOp : OneFlow_BaseOp<"spmm_csr_edge_grad_b", [NoSideEffect, DeclareOpInterfaceMethods<UserOpCompatibleInterface>]> {
+  let input = (ins
+    OneFlow_Tensor:$a_csr_row_ptr,
+    OneFlow_Tensor:$a_csr_col_idx,
+    OneFlow_Tensor:$perm,
+    OneFlow_Tensor:$e,
+    OneFlow_Tensor:$b,
+    OneFlow_Tensor:$dy
+  );
+  let output = (outs
+    OneFlow_Tensor:$db
+  );
+  let attrs = (ins
+    DefaultValuedAttr<SI64Attr, "0">:$op,
+    DefaultValuedAttr<SI64Attr, "0">:$act
+  );
+  let has_logical_tensor_desc_infer_fn = 1;
+  let has_physical_tensor_desc_infer_fn = 1;
+  let has_get_sbp_fn = 1;
+  let has_data_type_infer_fn = 1;
+  let has_input_arg_modify_fn = 1;
+}

@@ -725,6 +725,86 @@ def gatv2_scores_csr_heads_grad(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torc
     return d_x, (p if with_att else None)
 
 
+EDGE_OPS = {"mul": 0, "add": 1}  # OFX_EDGE_MUL / OFX_EDGE_ADD
+EDGE_ACTS = {None: 0, "relu": 1}  # OFX_ACT_NONE / OFX_ACT_RELU
+
+
+def _edge_inputs(name, rp, ci, e, b, op, act, dy=None, m=None):
+    """The prepared inputs of the edge-feature SpMM ops after the checks they share: e [nnz, N]
+    contiguous, b [K, N] (a row-strided view in place), dy [m, N]; the op and act codes."""
+    if op not in EDGE_OPS:
+        raise ValueError(f"{name}: op should be 'mul' or 'add', got {op!r}")
+    if act not in EDGE_ACTS:
+        raise ValueError(f"{name}: act should be None or 'relu', got {act!r}")
+    e, b = _prep(e, "e"), _prep(b, "b", matrix=True)
+    named = [("e", e), ("b", b)]
+    if dy is not None:
+        dy = _prep(dy, "dy", matrix=True)
+        named.append(("dy", dy))
+    _check_inputs(name, rp, ci, named, 2, "b", False)
+    if e.shape[0] != ci.numel() or e.shape[1] != b.shape[1]:
+        raise RuntimeError(f"{name}: e should be [nnz, N] = ({ci.numel()}, {b.shape[1]}), got "
+                           f"shape {tuple(e.shape)}")
+    if dy is not None and tuple(dy.shape) != (m, b.shape[1]):
+        raise RuntimeError(f"{name}: dy should be ({m}, {b.shape[1]}), got {tuple(dy.shape)}")
+    for t_name, t in named:
+        if t.device != b.device:
+            raise RuntimeError(f"{name}: expected all tensors on the same device, got {t_name} "
+                               f"on {t.device} and b on {b.device}")
+    return e, b, dy, EDGE_OPS[op], EDGE_ACTS[act]
+
+
+def spmm_csr_edge(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor, e: torch.Tensor,
+                  a_num_rows: int, a_num_cols: int, b: torch.Tensor, op: str = "mul",
+                  act: str | None = None, *, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "spmm_csr_edge": out[M, N] with out[r, :] = sum over the row's nonzeros j of
+    act(b[a_csr_col_idx[j], :] op e[j, :]) for e [nnz, N], b [K, N], op "mul" / "add", act None /
+    "relu"; every message is rounded to the dtype before the sum (contract in
+    include/ofx_spmm.h)."""
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
+    e, bb, _, opc, actc = _edge_inputs("spmm_csr_edge", rp, ci, e, b, op, act)
+    out = _check_out("spmm_csr_edge", out, (int(a_num_rows), bb.shape[1]), bb)
+    if out.numel() == 0:
+        return out
+    _two_phase(LIB.ofx_functional_spmm_csr_edge, bb,
+               _refs(rp, ci, e, bb) + (int(a_num_rows), int(a_num_cols), opc, actc), _refs(out))
+    return out
+
+
+def spmm_csr_edge_grad_e(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                         e: torch.Tensor, b: torch.Tensor, dy: torch.Tensor, op: str = "mul",
+                         act: str | None = None) -> torch.Tensor:
+    """Op "spmm_csr_edge_grad_e": de [nnz, N], the gradient of spmm_csr_edge in e from the
+    upstream dy [M, N]."""
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
+    e, bb, dy, opc, actc = _edge_inputs("spmm_csr_edge_grad_e", rp, ci, e, b, op, act, dy,
+                                        rp.numel() - 1)
+    de = torch.empty_like(e)
+    if de.numel():
+        _two_phase(LIB.ofx_functional_spmm_csr_edge_grad_e, bb,
+                   _refs(rp, ci, e, bb, dy) + (opc, actc), _refs(de))
+    return de
+
+
+def spmm_csr_edge_grad_b(at_row_ptr: torch.Tensor, at_col_idx: torch.Tensor, perm: torch.Tensor,
+                         e: torch.Tensor, b: torch.Tensor, dy: torch.Tensor, op: str = "mul",
+                         act: str | None = None) -> torch.Tensor:
+    """Op "spmm_csr_edge_grad_b": db [K, N], the gradient of spmm_csr_edge in b from the upstream
+    dy [M, N], summed over the transposed CSR (`csr_transpose`'s outputs) without atomics."""
+    rp, ci = _csr_pair(at_row_ptr, at_col_idx)
+    perm = _prep(perm, "perm")
+    if perm.dtype != rp.dtype or perm.shape != ci.shape:
+        raise RuntimeError("spmm_csr_edge_grad_b: perm should have the dtype and shape of "
+                           f"at_col_idx, got {perm.dtype} {tuple(perm.shape)}")
+    e, bb, dy, opc, actc = _edge_inputs("spmm_csr_edge_grad_b", rp, ci, e, b, op, act, dy,
+                                        dy.shape[0] if dy.dim() == 2 else None)
+    db = torch.empty((bb.shape[0], bb.shape[1]), dtype=bb.dtype, device=bb.device)
+    if db.numel():
+        _two_phase(LIB.ofx_functional_spmm_csr_edge_grad_b, bb,
+                   _refs(rp, ci, perm, e, bb, dy) + (opc, actc), _refs(db))
+    return db
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

@@ -246,6 +246,28 @@ def _load():
                                         i64, p, p, i64, i64, i64, popt], i32),
         "ofx_functional_spmm_csr_heads_fp8": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64, i64, i64,
                                                pdesc, p, sz, ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_edge_workspace_size": ([i32, i32, i64, i64, i64, i64, popt,
+                                              ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_edge": ([p, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, i32, i32, p, i64,
+                               i64, i64, p, sz, popt], i32),
+        "ofx_spmm_csr_edge_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, i32, i32, p,
+                                   i64, i64, i64, popt], i32),
+        "ofx_spmm_csr_edge_grad_e": ([p, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, i32, i32, p,
+                                      i64, p, i64, i64, p, sz], i32),
+        "ofx_spmm_csr_edge_grad_e_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, i32,
+                                          i32, p, i64, p, i64, i64], i32),
+        "ofx_spmm_csr_edge_grad_b_workspace_size": ([i32, i32, i64, i64, i64, i64, popt,
+                                                     ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_edge_grad_b": ([p, i32, i32, i64, i64, i64, i64, p, p, p, p, p, i64, i32, i32,
+                                      p, i64, p, i64, i64, i64, p, sz, popt], i32),
+        "ofx_spmm_csr_edge_grad_b_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, p, p, i64,
+                                          i32, i32, p, i64, p, i64, i64, i64, popt], i32),
+        "ofx_functional_spmm_csr_edge": ([p, pdesc, pdesc, pdesc, pdesc, i64, i64, i64, i64, pdesc,
+                                          p, sz, ctypes.POINTER(sz)], i32),
+        "ofx_functional_spmm_csr_edge_grad_e": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64, i64,
+                                                 pdesc, p, sz, ctypes.POINTER(sz)], i32),
+        "ofx_functional_spmm_csr_edge_grad_b": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, pdesc, i64,
+                                                 i64, pdesc, p, sz, ctypes.POINTER(sz)], i32),
         "ofx_graph_attention_csr_heads_workspace_size": ([i32, i32, i64, i64, i64, i64, i64, popt,
                                                           ctypes.POINTER(sz)], i32),
         "ofx_graph_attention_csr_heads": ([p, i32, i32, i64, i64, i64, i64, i64, p, p, p, i64, p,

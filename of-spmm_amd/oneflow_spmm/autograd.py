@@ -324,6 +324,64 @@ def _spmm_heads(row_ptr, col_idx, values, m, k, b, out, reduce):
     return out if out is not None else res.view(m, heads, d)
 
 
+class SpmmCsrEdgeFunction(torch.autograd.Function):
+    """out [M, N] = sum over each row's nonzeros of act(b[col] op e) through op "spmm_csr_edge",
+    differentiable in e [nnz, N] and b [K, N].  The inputs are saved (no per-nonzero tensor is);
+    d(e) is one launch of op "spmm_csr_edge_grad_e" and d(b) one of "spmm_csr_edge_grad_b" on the
+    cached transpose (deterministic, no atomics), each only when its input needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, e, m, k, b, op, act):
+        e = e.contiguous()
+        out = _C.spmm_csr_edge(row_ptr, col_idx, e, m, k, b, op, act)
+        ctx.save_for_backward(row_ptr, col_idx, e, b)
+        ctx.k, ctx.op, ctx.act = k, op, act
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        row_ptr, col_idx, e, b = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_e = d_b = None
+        if ctx.needs_input_grad[2]:
+            d_e = _C.spmm_csr_edge_grad_e(row_ptr, col_idx, e, b, d_out, ctx.op, ctx.act)
+        if ctx.needs_input_grad[5]:
+            rp_t, ci_t, perm = TRANSPOSE_CACHE.get(row_ptr, col_idx, ctx.k)
+            d_b = _C.spmm_csr_edge_grad_b(rp_t, ci_t, perm, e, b, d_out, ctx.op, ctx.act)
+        return None, None, d_e, None, None, d_b, None, None
+
+
+def spmm_edge(a_csr_row_ptr, a_csr_col_idx, e, a_num_rows, a_num_cols, b, op="mul", act=None, *,
+              out=None):
+    """Aggregation with a feature vector per edge:
+        out[r, :] = sum over r's nonzeros j of act(b[col[j], :] op e[j, :])
+    for e [nnz, N] and b [K, N] of one dtype (float32, float64, bfloat16, float16), op "mul"
+    (SchNet's CFConv, MPNN, CGConv-style messages; DGL's u_mul_e + sum) or "add" (with act="relu":
+    GINE; DGL's u_add_e), act None or "relu".  e [nnz, H, D] with b [K, H, D] is flattened and gives
+    out [M, H, D].  One launch: the [nnz, N] messages are never written.  Every message is rounded to
+    the dtype before it is summed in `spmm`'s order, so op="mul" without an activation on
+    e = values[:, None].expand(nnz, N) has exactly the bits of `spmm`; CPU and GPU tensors give the
+    same bits.  A column index outside [0, K) reads b as +0.  Differentiable in e and b (one launch
+    each, each built only when it is needed; d(b) on the cached transpose).  `out=` only when no
+    gradient is being recorded."""
+    if not (isinstance(e, torch.Tensor) and isinstance(b, torch.Tensor)) or e.dim() != b.dim() \
+            or b.dim() not in (2, 3) or e.shape[1:] != b.shape[1:]:
+        raise RuntimeError("spmm_edge: e [nnz, N] with b [K, N] (or e [nnz, H, D] with b "
+                           f"[K, H, D]) is expected, got {tuple(getattr(e, 'shape', ()))} and "
+                           f"{tuple(getattr(b, 'shape', ()))}")
+    m, k = int(a_num_rows), int(a_num_cols)
+    shape = (m,) + tuple(b.shape[1:])
+    if b.dim() == 3:
+        e, b = _heads_2d(e, "e"), _heads_2d(b, "b")
+    if _recording("spmm_edge", out, e, b):
+        return SpmmCsrEdgeFunction.apply(a_csr_row_ptr, a_csr_col_idx, e, m, k, b, op,
+                                         act).view(shape)
+    out2 = _out_2d("spmm_edge", out, shape,
+                   f"a {shape} tensor{' (contiguous)' if len(shape) == 3 else ''}")
+    res = _C.spmm_csr_edge(a_csr_row_ptr, a_csr_col_idx, e, m, k, b, op, act, out=out2)
+    return out if out is not None else res.view(shape)
+
+
 FP8_MAX = {torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
 
 
@@ -863,4 +921,4 @@ __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm",
            "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax", "SpmmCsrHeadsFunction",
            "SddmmCsrHeadsFunction", "EdgeSoftmaxHeadsFunction", "GatSoftmaxFunction", "gat_softmax",
            "gat_attention", "Gatv2ScoresFunction", "gatv2_scores", "gatv2_softmax",
-           "gatv2_attention"]
+           "gatv2_attention", "SpmmCsrEdgeFunction", "spmm_edge"]

@@ -247,6 +247,79 @@ def spmm_csr_heads(row_ptr, col_idx, values, b, m, k, heads, *, out=None, row_be
     return out
 
 
+def spmm_csr_edge(row_ptr, col_idx, e, b, m, k, op=0, act=0, *, out=None, row_begin=0,
+                  row_end=None, options: Options | None = None, num_threads: int = 0,
+                  workspace_bytes: int | None = None):
+    """The SpMM over per-edge feature vectors at the C-ABI (ofx_spmm_csr_edge on device tensors,
+    the kCPU kernel ofx_spmm_csr_edge_cpu on host tensors): e [nnz, N] contiguous, b [K, N] with
+    unit column stride, op / act the OFX_EDGE_* / OFX_ACT_* codes -> out [row_end - row_begin, N].
+    workspace_bytes: the device workspace to pass instead of the query's size (tests)."""
+    row_end = m if row_end is None else row_end
+    n, nnz = b.shape[1], col_idx.numel()
+    if out is None:
+        out = torch.empty((row_end - row_begin, n), dtype=b.dtype, device=b.device)
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(b.dtype)
+    popt = ctypes.byref(options) if options else None
+    body = (idt, vdt, m, k, n, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(e), _nz(b), b.stride(0),
+            int(op), int(act), _nz(out), out.stride(0), row_begin, row_end)
+    if b.device.type == "cpu":
+        check(LIB.ofx_spmm_csr_edge_cpu(int(num_threads), *body, popt), "spmm_csr_edge_cpu")
+        return out
+    wbuf, ws = _workspace(b.device, "spmm_csr_edge", LIB.ofx_spmm_csr_edge_workspace_size, idt,
+                          vdt, m, k, n, nnz, popt, workspace_bytes=workspace_bytes)
+    check(LIB.ofx_spmm_csr_edge(current_stream_handle(b), *body, wbuf.data_ptr(), ws, popt),
+          "spmm_csr_edge")
+    return out
+
+
+def spmm_csr_edge_grad_e(row_ptr, col_idx, e, b, dy, m, k, op=0, act=0, *, out=None, row_begin=0,
+                         row_end=None, num_threads: int = 0):
+    """d(e) of spmm_csr_edge at the C-ABI: dy [row_end - row_begin, N] with unit column stride ->
+    de [nnz, N] contiguous (`out`: the tensor to write the range's nonzeros into)."""
+    row_end = m if row_end is None else row_end
+    n, nnz = b.shape[1], col_idx.numel()
+    de = torch.empty_like(e) if out is None else out
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(b.dtype)
+    body = (idt, vdt, m, k, n, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(e), _nz(b), b.stride(0),
+            int(op), int(act), _nz(dy), dy.stride(0), _nz(de), row_begin, row_end)
+    if b.device.type == "cpu":
+        check(LIB.ofx_spmm_csr_edge_grad_e_cpu(int(num_threads), *body), "spmm_csr_edge_grad_e_cpu")
+        return de
+    # d(e) runs over the narrow SDDMM's work items: that entry's workspace
+    wbuf, ws = _workspace(b.device, "spmm_csr_edge_grad_e", LIB.ofx_sddmm_csr_heads_workspace_size,
+                          idt, vdt, m, 1, n, nnz)
+    check(LIB.ofx_spmm_csr_edge_grad_e(current_stream_handle(b), *body, wbuf.data_ptr(), ws),
+          "spmm_csr_edge_grad_e")
+    return de
+
+
+def spmm_csr_edge_grad_b(at_row_ptr, at_col_idx, perm, e, b, dy, m, k, op=0, act=0, *, out=None,
+                         row_begin=0, row_end=None, options: Options | None = None,
+                         num_threads: int = 0, workspace_bytes: int | None = None):
+    """d(b) of spmm_csr_edge at the C-ABI, on the transposed CSR (at_row_ptr [K+1], at_col_idx,
+    perm: ofx_csr_transpose's outputs): b holds rows [row_begin, row_end) of the [K, N] operand,
+    dy is the whole [M, N] -> db [row_end - row_begin, N]."""
+    row_end = k if row_end is None else row_end
+    n, nnz = b.shape[1], at_col_idx.numel()
+    if out is None:
+        out = torch.empty((row_end - row_begin, n), dtype=b.dtype, device=b.device)
+    idt, vdt = dtype_code(at_row_ptr.dtype), dtype_code(b.dtype)
+    popt = ctypes.byref(options) if options else None
+    body = (idt, vdt, m, k, n, nnz, at_row_ptr.data_ptr(), _nz(at_col_idx), _nz(perm), _nz(e),
+            _nz(b), b.stride(0), int(op), int(act), _nz(dy), dy.stride(0), _nz(out), out.stride(0),
+            row_begin, row_end)
+    if b.device.type == "cpu":
+        check(LIB.ofx_spmm_csr_edge_grad_b_cpu(int(num_threads), *body, popt),
+              "spmm_csr_edge_grad_b_cpu")
+        return out
+    wbuf, ws = _workspace(b.device, "spmm_csr_edge_grad_b",
+                          LIB.ofx_spmm_csr_edge_grad_b_workspace_size, idt, vdt, m, k, n, nnz, popt,
+                          workspace_bytes=workspace_bytes)
+    check(LIB.ofx_spmm_csr_edge_grad_b(current_stream_handle(b), *body, wbuf.data_ptr(), ws, popt),
+          "spmm_csr_edge_grad_b")
+    return out
+
+
 def spmm_csr_heads_fp8(row_ptr, col_idx, values, b_q, b_scale, m, k, heads, *, b_format=None,
                        val_dtype=None, out=None, row_begin=0, row_end=None,
                        options: Options | None = None, num_threads: int = 0,
