@@ -905,6 +905,59 @@ int ofx_spmm_csr_edge_grad_b_cpu(int num_threads, int idx_dtype, int val_dtype, 
                                  int64_t lddy, void* db, int64_t lddb, int64_t row_begin,
                                  int64_t row_end, const ofx_spmm_options* opts);
 
+/* ---- Multi-aggregator SpMM (op "spmm_csr_multi") --------------------------------
+ * Several aggregators of the same messages from one walk of the CSR and one gather of b:
+ * Principal Neighbourhood Aggregation (PNAConv, DGN), PyG's MultiAggregation, pooled GraphSAGE.
+ * aggr_mask is a non-empty OR of OFX_AGGR_*; the requested aggregators are written as slices in
+ * ascending bit order (sum, mean, max, min, var, std): slice a, row r, column n is
+ * c[a * slice_stride + r * ldc + n].  With `a` the accumulation type (f64 for f64, else f32), no
+ * FMA anywhere, and p_j[n] = mul(values[j], b[col_idx[j], n]) rounded to T as in ofx_spmm_csr (a
+ * column outside [0, k) reads a zero row):
+ *   s1 = sum_j load(p_j), s2 = sum_j load(p_j) * load(p_j), the square formed in `a` and not
+ *     rounded to T; both in ofx_spmm_csr's order: nonzeros ascending, a row of more than `split`
+ *     nonzeros (resolve_schedule(n, opts)) summed per chunk from +0 and the chunk partials added
+ *     in chunk order into +0.
+ *   sum  = store(s1): the bits of ofx_spmm_csr.
+ *   mean = store(load(sum) / a(deg)), +0 for deg = 0: the bits of OFX_REDUCE_MEAN.
+ *   max / min: the strict walk of ofx_spmm_csr_reduce (the lowest j wins ties, +0 and -0 tie, the
+ *     first NaN wins and is stored canonical), +0 for an empty row: the bits of OFX_REDUCE_MAX /
+ *     OFX_REDUCE_MIN.  arg_max / arg_min ([rows, n] of the index dtype with ldarg; each may be
+ *     NULL, and must be without its aggregator in the mask) hold the winning global j, -1 for an
+ *     empty row, as ofx_spmm_csr_reduce's arg.
+ *   var, deg > 0: mu = s1 / a(deg); v = s2 / a(deg) - mu * mu; var = (v < 0) ? +0 : v, so a NaN
+ *     propagates (stored canonical); the result is store(var).  deg = 0: +0.  This is PyG's and
+ *     DGL's E[p^2] - E[p]^2: it cancels where the mean is large against the spread, the relative
+ *     error of var growing like u * (s2 / deg + mu^2) / var.
+ *   std = store(sqrt(var + a(eps))) from the unrounded var, eps converted once to `a`; deg = 0:
+ *     store(sqrt(a(eps))).  sqrt and / are the correctly rounded IEEE operations.
+ * eps must be finite and >= 0.  Row range, offsets, empty launches, workspace, schedule options
+ * and errors as ofx_spmm_csr_reduce; OFX_EINVAL also for an empty or unknown aggr_mask, a bad eps
+ * and a slice stride below n.  The device version is asynchronous on `stream`, without atomics,
+ * allocation or host synchronisation; with no valid plan every requested output is filled with
+ * the canonical NaN (args -1) and the next entry returns OFX_EPLAN.  The HIP kernels and the kCPU
+ * kernel give the same bits; the kCPU kernel's bits do not depend on num_threads.              */
+#define OFX_AGGR_SUM 1
+#define OFX_AGGR_MEAN 2
+#define OFX_AGGR_MAX 4
+#define OFX_AGGR_MIN 8
+#define OFX_AGGR_VAR 16
+#define OFX_AGGR_STD 32
+int ofx_spmm_csr_multi_workspace_size(int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                                      int64_t n, int64_t nnz, int aggr_mask,
+                                      const ofx_spmm_options* opts, size_t* bytes);
+int ofx_spmm_csr_multi(void* stream, int idx_dtype, int val_dtype, int64_t m, int64_t k, int64_t n,
+                       int64_t nnz, const void* row_ptr, const void* col_idx, const void* values,
+                       const void* b, int64_t ldb, int aggr_mask, double eps, void* c, int64_t ldc,
+                       int64_t slice_stride, void* arg_max, void* arg_min, int64_t ldarg,
+                       int64_t row_begin, int64_t row_end, void* workspace, size_t workspace_bytes,
+                       const ofx_spmm_options* opts);
+int ofx_spmm_csr_multi_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t m, int64_t k,
+                           int64_t n, int64_t nnz, const void* row_ptr, const void* col_idx,
+                           const void* values, const void* b, int64_t ldb, int aggr_mask,
+                           double eps, void* c, int64_t ldc, int64_t slice_stride, void* arg_max,
+                           void* arg_min, int64_t ldarg, int64_t row_begin, int64_t row_end,
+                           const ofx_spmm_options* opts);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -1666,6 +1719,18 @@ int ofx_functional_spmm_csr_edge_grad_b(void* stream, const ofx_tensor_desc* row
                                         const ofx_tensor_desc* b, const ofx_tensor_desc* dy,
                                         int64_t op, int64_t act, ofx_tensor_desc* db, void* tmp,
                                         size_t tmp_bytes, size_t* tmp_size_out);
+/* functional::SpmmCsrMulti: op "spmm_csr_multi" (row_ptr [M+1], col_idx [nnz], values [nnz],
+ * b [K, N]; attrs a_num_rows, a_num_cols, aggr_mask = an OR of OFX_AGGR_*, eps -> out [M, A*N]: the
+ * A requested aggregators as column blocks of width N in ascending bit order; arg_max / arg_min
+ * [M, N] in the index dtype, empty [0, N] tensors without max / min) of
+ * oneflow/user/ops/spmm_multi_op.cpp through the op-registry dispatch; the contract of
+ * ofx_spmm_csr_multi.  tmp_size_out != NULL: only the tmp size is computed.                     */
+int ofx_functional_spmm_csr_multi(void* stream, const ofx_tensor_desc* row_ptr,
+                                  const ofx_tensor_desc* col_idx, const ofx_tensor_desc* values,
+                                  int64_t a_num_rows, int64_t a_num_cols, const ofx_tensor_desc* b,
+                                  int64_t aggr_mask, double eps, ofx_tensor_desc* out,
+                                  ofx_tensor_desc* arg_max, ofx_tensor_desc* arg_min, void* tmp,
+                                  size_t tmp_bytes, size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

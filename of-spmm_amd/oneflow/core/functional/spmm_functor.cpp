@@ -986,6 +986,33 @@ extern "C" int ofx_functional_spmm_csr_edge_grad_b(void* stream, const ofx_tenso
   });
 }
 
+// ---- functional::SpmmCsrMulti ---------------------------------------------------------------------
+// Op "spmm_csr_multi" (oneflow/user/ops/spmm_multi_op.cpp) through the same op-registry dispatch
+// (INTEGRATION.md §15b); three outputs, the args empty without their aggregator.
+extern "C" int ofx_functional_spmm_csr_multi(void* stream, const ofx_tensor_desc* row_ptr,
+                                             const ofx_tensor_desc* col_idx,
+                                             const ofx_tensor_desc* values, int64_t a_num_rows,
+                                             int64_t a_num_cols, const ofx_tensor_desc* b,
+                                             int64_t aggr_mask, double eps, ofx_tensor_desc* out,
+                                             ofx_tensor_desc* arg_max, ofx_tensor_desc* arg_min,
+                                             void* tmp, size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(values != nullptr && b != nullptr, OFX_EINVAL,
+                "spmm_csr_multi: NULL input values or b");
+    // an earlier launch's loud failure comes back here as OFX_EPLAN (as for spmm_csr)
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("spmm_csr_multi");
+    std::vector<Arg> outs;
+    if (tmp_size_out == nullptr) outs = {{"out", out}, {"arg_max", arg_max}, {"arg_min", arg_min}};
+    return ToStatus(RunUserOp("spmm_csr_multi",
+                              {{"a_csr_row_ptr", row_ptr}, {"a_csr_col_idx", col_idx},
+                               {"a_csr_values", values}, {"b", b}},
+                              outs,
+                              {{"a_num_rows", a_num_rows}, {"a_num_cols", a_num_cols},
+                               {"aggr_mask", aggr_mask}, {"eps", user_op::AttrBits<double>(eps)}},
+                              stream, tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
 // ---- functional::GraphAttentionCsrHeads ----------------------------------------------------------
 // Op "graph_attention_csr_heads" (oneflow/user/ops/graph_attention_heads_op.cpp) through the same
 // op-registry dispatch; two outputs.

@@ -509,3 +509,33 @@ def OneFlow_SpmmCsrEdgeGradBOp : OneFlow_BaseOp<"spmm_csr_edge_grad_b", [NoSideE
   let has_data_type_infer_fn = 1;
   let has_input_arg_modify_fn = 1;
 }
+
+// The multi-aggregator SpMM: the aggregators of aggr_mask (bit 0 sum, 1 mean, 2 max, 3 min, 4 var,
+// 5 std) of the messages values[j] * b[col[j], :] of every row, from one walk of the CSR, as column
+// blocks of width N of out [M, A*N] in ascending bit order; arg_max / arg_min [M, N] (empty without
+// max / min) hold the winning global nonzero index.  var = E[p^2] - E[p]^2 clamped at 0 in the
+// accumulation type, std = sqrt(var + eps).  SBP: the row split of spmm_csr_reduce.
+def OneFlow_SpmmCsrMultiOp : OneFlow_BaseOp<"spmm_csr_multi", [NoSideEffect, DeclareOpInterfaceMethods<UserOpCompatibleInterface>]> {
+  let input = (ins
+    OneFlow_Tensor:$a_csr_row_ptr,
+    OneFlow_Tensor:$a_csr_col_idx,
+    OneFlow_Tensor:$a_csr_values,
+    OneFlow_Tensor:$b
+  );
+  let output = (outs
+    OneFlow_Tensor:$out,
+    OneFlow_Tensor:$arg_max,
+    OneFlow_Tensor:$arg_min
+  );
+  let attrs = (ins
+    DefaultValuedAttr<SI64Attr, "0">:$a_num_rows,
+    DefaultValuedAttr<SI64Attr, "0">:$a_num_cols,
+    DefaultValuedAttr<SI64Attr, "0">:$aggr_mask,
+    DefaultValuedAttr<F64Attr, "1e-5">:$eps
+  );
+  let has_logical_tensor_desc_infer_fn = 1;
+  let has_physical_tensor_desc_infer_fn = 1;
+  let has_get_sbp_fn = 1;
+  let has_data_type_infer_fn = 1;
+  let has_input_arg_modify_fn = 1;
+}

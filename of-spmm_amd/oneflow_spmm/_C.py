@@ -805,6 +805,49 @@ def spmm_csr_edge_grad_b(at_row_ptr: torch.Tensor, at_col_idx: torch.Tensor, per
     return db
 
 
+AGGR_BITS = {"sum": 1, "mean": 2, "max": 4, "min": 8, "var": 16, "std": 32}  # OFX_AGGR_*
+
+
+def aggr_mask(aggrs) -> int:
+    """The OFX_AGGR_* mask of a non-empty sequence of distinct aggregator names."""
+    names = (aggrs,) if isinstance(aggrs, str) else tuple(aggrs)
+    if not names or len(set(names)) != len(names) or any(a not in AGGR_BITS for a in names):
+        raise ValueError(f"spmm_multi: aggrs should be a non-empty sequence of distinct names from "
+                         f"{list(AGGR_BITS)}, got {aggrs!r}")
+    return sum(AGGR_BITS[a] for a in names)
+
+
+def aggr_slices(aggrs) -> list:
+    """The slice of out [M, A, N] that holds each name of `aggrs`: the requested aggregators are
+    stored in ascending bit order (sum, mean, max, min, var, std)."""
+    names = (aggrs,) if isinstance(aggrs, str) else tuple(aggrs)
+    stored = sorted(names, key=AGGR_BITS.__getitem__)
+    return [stored.index(a) for a in names]
+
+
+def spmm_csr_multi(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
+                   a_csr_values: torch.Tensor, a_num_rows: int, a_num_cols: int, b: torch.Tensor,
+                   mask: int, eps: float = 1e-5):
+    """Op "spmm_csr_multi": (out [M, A, N], arg_max, arg_min) with the aggregators of `mask` (an OR
+    of the OFX_AGGR_* bits) of the messages values[j] * b[col_idx[j], :] of every row in ascending
+    bit order, from one walk of the CSR (contract in include/ofx_spmm.h).  arg_max / arg_min [M, N]
+    hold the winning global nonzero index (-1 for an empty row) and are empty [0, N] tensors
+    without max / min in the mask."""
+    rp, ci = _csr_pair(a_csr_row_ptr, a_csr_col_idx)
+    vals = _prep(a_csr_values, "a_csr_values")
+    bb = _prep(b, "b", matrix=True)
+    m, n = int(a_num_rows), bb.shape[1] if bb.dim() == 2 else 0
+    slices = bin(int(mask) & 63).count("1")
+    out = torch.empty((m, slices * n), dtype=bb.dtype, device=bb.device)
+    arg_max = torch.empty((m if mask & 4 else 0, n), dtype=rp.dtype, device=bb.device)
+    arg_min = torch.empty((m if mask & 8 else 0, n), dtype=rp.dtype, device=bb.device)
+    head = (*_refs(rp, ci, vals), m, int(a_num_cols), *_refs(bb), int(mask), float(eps))
+    if out.numel():
+        _two_phase(LIB.ofx_functional_spmm_csr_multi, bb, head, _refs(out, arg_max, arg_min),
+                   what="spmm_csr_multi")
+    return out.view(m, slices, n), arg_max, arg_min
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

@@ -96,6 +96,7 @@ def _load():
             "There is no CPU/torch fallback for the HIP path.")
     lib = ctypes.CDLL(LIB_PATH)
     i32, i64, u64, p, sz = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t
+    f64 = ctypes.c_double
     popt = ctypes.POINTER(Options)
     pdesc = ctypes.POINTER(TensorDesc)
     ppl = ctypes.POINTER(Placement)
@@ -262,6 +263,14 @@ def _load():
                                       p, i64, p, i64, i64, i64, p, sz, popt], i32),
         "ofx_spmm_csr_edge_grad_b_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, p, p, i64,
                                           i32, i32, p, i64, p, i64, i64, i64, popt], i32),
+        "ofx_spmm_csr_multi_workspace_size": ([i32, i32, i64, i64, i64, i64, i32, popt,
+                                               ctypes.POINTER(sz)], i32),
+        "ofx_spmm_csr_multi": ([p, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, i32, f64, p, i64,
+                                i64, p, p, i64, i64, i64, p, sz, popt], i32),
+        "ofx_spmm_csr_multi_cpu": ([i32, i32, i32, i64, i64, i64, i64, p, p, p, p, i64, i32, f64, p,
+                                    i64, i64, p, p, i64, i64, i64, popt], i32),
+        "ofx_functional_spmm_csr_multi": ([p, pdesc, pdesc, pdesc, i64, i64, pdesc, i64, f64, pdesc,
+                                           pdesc, pdesc, p, sz, ctypes.POINTER(sz)], i32),
         "ofx_functional_spmm_csr_edge": ([p, pdesc, pdesc, pdesc, pdesc, i64, i64, i64, i64, pdesc,
                                           p, sz, ctypes.POINTER(sz)], i32),
         "ofx_functional_spmm_csr_edge_grad_e": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64, i64,

@@ -848,6 +848,111 @@ def spmm_reduce(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_co
                               b, reduce, out=out)
 
 
+def _plus(a, b):
+    """a + b where either may be None (an absent term)."""
+    return b if a is None else a if b is None else a + b
+
+
+class SpmmCsrMultiFunction(torch.autograd.Function):
+    """out [M, A, N] = the aggregators of `mask` (op "spmm_csr_multi", ascending bit order),
+    differentiable in `a_csr_values` and `b` through the existing gradient ops, no backward kernel
+    of its own.  With g the upstream gradient per slice, deg the row degrees, v the variance:
+        g_v = g_var + g_std / (2 std) where v > 0, else 0 (clamped or zero variance)
+        G1  = g_sum + g_mean / deg - 2 g_v mean / deg,   G2 = 2 g_v / deg    (0 on empty rows)
+        d(b)      = A^T G1 + b * (A^T with values^2) G2 + the max / min selections
+        d(values) = sddmm(G1, b) + values * sddmm(G2, b * b) + the max / min masked SDDMMs
+    on the cached transpose, with the forward's args.  mean and var are the saved slices, or one
+    more walk of the op when they were not requested.  Only the requested terms are computed."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_idx, values, m, k, b, mask, eps):
+        out, arg_max, arg_min = _C.spmm_csr_multi(row_ptr, col_idx, values, m, k, b, mask, eps)
+        ctx.save_for_backward(row_ptr, col_idx, values, b, out, arg_max, arg_min)
+        ctx.m, ctx.k, ctx.mask, ctx.eps = m, k, mask, eps
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        row_ptr, col_idx, values, b, out, arg_max, arg_min = ctx.saved_tensors
+        m, k = ctx.m, ctx.k
+        values, b = values.detach(), b.detach()
+        stored = [a for a, bit in _C.AGGR_BITS.items() if ctx.mask & bit]  # ascending bit order
+        acc = torch.float64 if out.dtype == torch.float64 else torch.float32
+        g = {a: d_out[:, i, :].to(acc) for i, a in enumerate(stored)}
+        y = {a: out[:, i, :].to(acc) for i, a in enumerate(stored)}
+        deg = (row_ptr[1:] - row_ptr[:-1]).to(acc).unsqueeze(1)
+        inv = torch.where(deg > 0, 1 / deg.clamp(min=1), torch.zeros_like(deg))
+        g1 = g.get("sum")
+        if "mean" in g:
+            g1 = _plus(g1, g["mean"] * inv)
+        g2 = None
+        if "var" in g or "std" in g:
+            if "mean" in y and "var" in y:
+                mean, var = y["mean"], y["var"]
+            else:
+                st = _C.spmm_csr_multi(row_ptr, col_idx, values, m, k, b,
+                                       _C.AGGR_BITS["mean"] | _C.AGGR_BITS["var"], ctx.eps)[0]
+                mean, var = st[:, 0, :].to(acc), st[:, 1, :].to(acc)
+            g_v = g.get("var")
+            if "std" in g:
+                g_v = _plus(g_v, g["std"] / (2 * y["std"]))
+            g_v = torch.where(var > 0, g_v, torch.zeros_like(g_v))
+            g1 = _plus(g1, -2 * g_v * mean * inv)
+            g2 = (2 * g_v * inv).to(out.dtype)
+        if g1 is not None:
+            g1 = g1.to(out.dtype).contiguous()
+        ext = [(a, arg, d_out[:, stored.index(a), :].contiguous())
+               for a, arg in (("max", arg_max), ("min", arg_min)) if a in g]
+        d_values = d_b = None
+        if ctx.needs_input_grad[2]:
+            if g1 is not None:
+                d_values = _C.sddmm_csr(row_ptr, col_idx, g1, b, m, k)
+            if g2 is not None:
+                d_values = _plus(d_values, values * _C.sddmm_csr(row_ptr, col_idx, g2, b * b, m, k))
+            for _, arg, gy in ext:
+                d_values = _plus(d_values, _C.spmm_csr_reduce_grad_values(row_ptr, col_idx, arg,
+                                                                          gy, b, m, k))
+        if ctx.needs_input_grad[5]:
+            if g1 is not None:
+                d_b = TRANSPOSE_CACHE.grad_b(row_ptr, col_idx, values, m, k, g1)
+            if g2 is not None:
+                d_b = _plus(d_b, b * TRANSPOSE_CACHE.grad_b(row_ptr, col_idx, values * values, m,
+                                                            k, g2))
+            if ext:
+                rp_t, ci_t, perm = TRANSPOSE_CACHE.get(row_ptr, col_idx, k)
+                for _, arg, gy in ext:
+                    d_b = _plus(d_b, _C.spmm_csr_reduce_grad_b(rp_t, ci_t, perm, values, arg, gy,
+                                                               m, k))
+        return None, None, d_values, None, None, d_b, None, None
+
+
+def spmm_multi(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b,
+               aggrs=("mean", "max", "min", "std"), eps=1e-5):
+    """Several aggregators of the same messages in one launch (Principal Neighbourhood Aggregation,
+    PyG's MultiAggregation, pooled GraphSAGE): out [M, A, N] with out[:, a, :] the aggregator
+    aggrs[a] over r's nonzeros j of values[j] * b[col[j], :], for a non-empty tuple of distinct names
+    from "sum", "mean", "max", "min", "var", "std"; out.flatten(1) is PyG's concatenation.  Each B row
+    is gathered once and feeds every statistic.  sum / mean / max / min have the bits of `spmm` with
+    that reduce; var = E[p^2] - E[p]^2 in the accumulation type, clamped at 0 (PyG's and DGL's
+    formula), +0 for an empty row; std = sqrt(var + eps).  b [K, H, D] is taken as N = H*D.  CPU and
+    GPU tensors give the same bits.  Differentiable in a_csr_values and b.  The aggregators are
+    stored in the order sum, mean, max, min, var, std: `aggrs` in another order costs a copy."""
+    mask = _C.aggr_mask(aggrs)
+    eps = float(eps)
+    if not 0.0 <= eps < float("inf"):
+        raise ValueError(f"spmm_multi: eps should be finite and >= 0, got {eps}")
+    if isinstance(b, torch.Tensor) and b.dim() == 3:
+        b = _heads_2d(b, "b")
+    m, k = int(a_num_rows), int(a_num_cols)
+    if _recording("spmm_multi", None, a_csr_values, b):
+        out = SpmmCsrMultiFunction.apply(a_csr_row_ptr, a_csr_col_idx, a_csr_values, m, k, b, mask,
+                                         eps)
+    else:
+        out = _C.spmm_csr_multi(a_csr_row_ptr, a_csr_col_idx, a_csr_values, m, k, b, mask, eps)[0]
+    order = _C.aggr_slices(aggrs)
+    return out if order == sorted(order) else out[:, order, :]
+
+
 def spmm(a_csr_row_ptr, a_csr_col_idx, a_csr_values, a_num_rows, a_num_cols, b, *, out=None,
          static_csr=0, reduce="sum"):
     """`oneflow.spmm` with autograd: differentiable in `a_csr_values` and `b`.
@@ -921,4 +1026,5 @@ __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm",
            "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax", "SpmmCsrHeadsFunction",
            "SddmmCsrHeadsFunction", "EdgeSoftmaxHeadsFunction", "GatSoftmaxFunction", "gat_softmax",
            "gat_attention", "Gatv2ScoresFunction", "gatv2_scores", "gatv2_softmax",
-           "gatv2_attention", "SpmmCsrEdgeFunction", "spmm_edge"]
+           "gatv2_attention", "SpmmCsrEdgeFunction", "spmm_edge", "SpmmCsrMultiFunction",
+           "spmm_multi"]

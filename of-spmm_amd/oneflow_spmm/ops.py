@@ -320,6 +320,41 @@ def spmm_csr_edge_grad_b(at_row_ptr, at_col_idx, perm, e, b, dy, m, k, op=0, act
     return out
 
 
+def spmm_csr_multi(row_ptr, col_idx, values, b, m, k, aggr_mask, eps=1e-5, *, out=None,
+                   arg_max=None, arg_min=None, with_args=True, row_begin=0, row_end=None,
+                   options: Options | None = None, num_threads: int = 0,
+                   workspace_bytes: int | None = None):
+    """The multi-aggregator SpMM at the C-ABI (ofx_spmm_csr_multi on device tensors, the kCPU
+    kernel ofx_spmm_csr_multi_cpu on host tensors): aggr_mask an OR of the OFX_AGGR_* bits (1 sum,
+    2 mean, 4 max, 8 min, 16 var, 32 std) -> (out [rows, A, N] with the requested aggregators in
+    ascending bit order, arg_max, arg_min [rows, N] or None).  `out`: a [rows, A, N] tensor with
+    unit column stride (its row and slice strides are passed on); with_args=False leaves the args
+    out.  workspace_bytes: the device workspace to pass instead of the query's size (tests)."""
+    row_end = m if row_end is None else row_end
+    rows, n, nnz = row_end - row_begin, b.shape[1], col_idx.numel()
+    mask = int(aggr_mask)
+    if out is None:
+        out = torch.empty((rows, bin(mask & 63).count("1"), n), dtype=b.dtype, device=b.device)
+    if with_args and arg_max is None and mask & 4:
+        arg_max = torch.empty((rows, n), dtype=row_ptr.dtype, device=b.device)
+    if with_args and arg_min is None and mask & 8:
+        arg_min = torch.empty((rows, n), dtype=row_ptr.dtype, device=b.device)
+    ldarg = next((a.stride(0) for a in (arg_max, arg_min) if a is not None), 0)
+    idt, vdt = dtype_code(row_ptr.dtype), dtype_code(b.dtype)
+    popt = ctypes.byref(options) if options else None
+    body = (idt, vdt, m, k, n, nnz, row_ptr.data_ptr(), _nz(col_idx), _nz(values), _nz(b),
+            b.stride(0), mask, float(eps), _nz(out), out.stride(0), out.stride(1), _nz(arg_max),
+            _nz(arg_min), ldarg, row_begin, row_end)
+    if b.device.type == "cpu":
+        check(LIB.ofx_spmm_csr_multi_cpu(int(num_threads), *body, popt), "spmm_csr_multi_cpu")
+        return out, arg_max, arg_min
+    wbuf, ws = _workspace(b.device, "spmm_csr_multi", LIB.ofx_spmm_csr_multi_workspace_size, idt,
+                          vdt, m, k, n, nnz, mask, popt, workspace_bytes=workspace_bytes)
+    check(LIB.ofx_spmm_csr_multi(current_stream_handle(b), *body, wbuf.data_ptr(), ws, popt),
+          "spmm_csr_multi")
+    return out, arg_max, arg_min
+
+
 def spmm_csr_heads_fp8(row_ptr, col_idx, values, b_q, b_scale, m, k, heads, *, b_format=None,
                        val_dtype=None, out=None, row_begin=0, row_end=None,
                        options: Options | None = None, num_threads: int = 0,
