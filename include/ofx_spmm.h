@@ -958,6 +958,70 @@ int ofx_spmm_csr_multi_cpu(int num_threads, int idx_dtype, int val_dtype, int64_
                            void* arg_min, int64_t ldarg, int64_t row_begin, int64_t row_end,
                            const ofx_spmm_options* opts);
 
+/* ---- Segment matmul: a typed linear transform over sorted rows (ops "segment_matmul" /
+ * "segment_matmul_grad_w") -------------------------------------------------------
+ *   out[i, :] = x[row(i), :] @ W[t]      for seg_ptr[t] <= i < seg_ptr[t+1],
+ *   row(i) = idx != NULL ? idx[i] : i
+ * the transform of RGCN / HGT / HeteroLinear layers (PyG's segment_matmul, DGL's segment_mm), and
+ * with idx = the columns of type-sorted edges the edge-typed message x[col[j]] @ W[etype[j]]
+ * without the gathered copy.  x T[r, f_in] with ldx; w T[t, f_in, f_out] contiguous, or with
+ * trans_w != 0 T[t, f_out, f_in] read as its transpose (no copy: the x-gradient is the forward on
+ * dy with trans_w); seg_ptr idx_dtype[t+1], non-decreasing from 0 to s; idx idx_dtype[s] or NULL
+ * (then s == r); out T[s, f_out] with ldo.  T is float, float16 or bfloat16 (double:
+ * OFX_EUNSUPPORTED).  t >= 1, f_in >= 1, f_out >= 1; s == 0, r == 0 and empty segments are fine.
+ * An idx[i] outside [0, r) is never used as an address: the row reads as +0.
+ *
+ * The w-gradient: dw[t] = sum over the segment's i of x[row(i), :]^T dy[i, :], T[t, f_in, f_out]
+ * contiguous from dy T[s, f_out] with lddy; an empty segment gives +0.
+ *
+ * Numeric contract.  Every product is formed in f32 and the sums are accumulated in f32; the
+ * result is rounded once to T, to nearest even.  The ORDER of a sum is the matrix instructions' on
+ * the device and ascending k (w-gradient: ascending i) in the kCPU kernels, so, unlike every other
+ * entry of this header, the HIP and the kCPU kernels do NOT promise the same bits.  In its place,
+ * against the exact (float64) result ref, with n the length of the sum and p = 24 / 8 / 11 for
+ * float / bfloat16 / float16:
+ *     |got - ref| <= 2 n 2^-24 sum_k |a_k| |b_k| + 2^-p |ref|
+ * (the gamma_n bound of an f32 dot product in any order, plus the output rounding).  Where every
+ * partial sum is exactly representable in f32 the result is the float64 result rounded to T, bit
+ * for bit.  Two calls on the same inputs give the same bits: there are no float atomics, and the
+ * w-gradient adds the partial sums of its row parts in ascending part order.  NaN and inf
+ * propagate; denormal inputs are not covered.
+ *
+ * Device versions: asynchronous on `stream`, no allocation, and nothing is read back: the grid and
+ * the workspace are functions of (s, t, f_in, f_out, dtype[, parts]) alone, so the calls are
+ * capturable in a graph.  A malformed seg_ptr cannot produce an address outside the operands
+ * (every bound is clamped into [0, s]); which rows are then written is undefined.  The kCPU
+ * entries check seg_ptr (OFX_EINVAL: not starting at 0, decreasing, not ending at s).  `parts`:
+ * the contiguous row parts the w-gradient is cut into, 0 = chosen from the shapes; the workspace
+ * is (parts + t) * f_in * f_out * 4 bytes, OFX_EWORKSPACE when smaller.  The forward needs no
+ * workspace (its query answers 0).  ofx_segment_matmul_tiles: the forward's block (bm rows x bn
+ * columns) and the slab of the contraction (bk elements of the dtype) the kernels tile with; the
+ * w-gradient's block is bn x bn of dw[t] over slabs of bk rows.  OFX_EINVAL: a bad size, s != r
+ * without idx, a leading dimension below the width, a NULL pointer, an output that overlaps an
+ * input.  Nothing is launched on an error.                                                      */
+int ofx_segment_matmul_tiles(int val_dtype, int64_t* bm, int64_t* bn, int64_t* bk);
+int ofx_segment_matmul_workspace_size(int idx_dtype, int val_dtype, int64_t r, int64_t s, int64_t t,
+                                      int64_t f_in, int64_t f_out, size_t* bytes);
+int ofx_segment_matmul(void* stream, int idx_dtype, int val_dtype, int64_t r, int64_t s, int64_t t,
+                       int64_t f_in, int64_t f_out, const void* x, int64_t ldx, const void* w,
+                       int trans_w, const void* seg_ptr, const void* idx, void* out, int64_t ldo,
+                       void* workspace, size_t workspace_bytes);
+int ofx_segment_matmul_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t r, int64_t s,
+                           int64_t t, int64_t f_in, int64_t f_out, const void* x, int64_t ldx,
+                           const void* w, int trans_w, const void* seg_ptr, const void* idx,
+                           void* out, int64_t ldo);
+int ofx_segment_matmul_grad_w_workspace_size(int idx_dtype, int val_dtype, int64_t r, int64_t s,
+                                             int64_t t, int64_t f_in, int64_t f_out, int64_t parts,
+                                             size_t* bytes);
+int ofx_segment_matmul_grad_w(void* stream, int idx_dtype, int val_dtype, int64_t r, int64_t s,
+                              int64_t t, int64_t f_in, int64_t f_out, const void* x, int64_t ldx,
+                              const void* dy, int64_t lddy, const void* seg_ptr, const void* idx,
+                              void* dw, int64_t parts, void* workspace, size_t workspace_bytes);
+int ofx_segment_matmul_grad_w_cpu(int num_threads, int idx_dtype, int val_dtype, int64_t r,
+                                  int64_t s, int64_t t, int64_t f_in, int64_t f_out, const void* x,
+                                  int64_t ldx, const void* dy, int64_t lddy, const void* seg_ptr,
+                                  const void* idx, void* dw);
+
 /* ---- COO (edge_index) -> CSR -----------------------------------------
  * Canonical CSR from COO pairs: rows ascending, columns ascending; with merge_duplicates != 0,
  * equal (row, col) entries become one whose value is their sum in input order (fp32 accumulation
@@ -1731,6 +1795,21 @@ int ofx_functional_spmm_csr_multi(void* stream, const ofx_tensor_desc* row_ptr,
                                   int64_t aggr_mask, double eps, ofx_tensor_desc* out,
                                   ofx_tensor_desc* arg_max, ofx_tensor_desc* arg_min, void* tmp,
                                   size_t tmp_bytes, size_t* tmp_size_out);
+/* functional::SegmentMatmul / SegmentMatmulGradW: ops "segment_matmul" (x [R, F_in], w the
+ * [T, F_in, F_out] stack viewed [T*F_in, F_out], or with trans_w != 0 the [T, F_out, F_in] stack
+ * viewed [T*F_out, F_in]; seg_ptr [T+1]; idx [S] or NULL -> out [S, F_out]) and
+ * "segment_matmul_grad_w" (x, dy [S, F_out], seg_ptr, idx or NULL; attr parts -> dw
+ * [T*F_in, F_out]) of oneflow/user/ops/segment_matmul_op.cpp through the op-registry dispatch; the
+ * contract of ofx_segment_matmul(_grad_w).  tmp_size_out != NULL: only the tmp size is computed. */
+int ofx_functional_segment_matmul(void* stream, const ofx_tensor_desc* x, const ofx_tensor_desc* w,
+                                  const ofx_tensor_desc* seg_ptr, const ofx_tensor_desc* idx,
+                                  int64_t trans_w, ofx_tensor_desc* out, void* tmp,
+                                  size_t tmp_bytes, size_t* tmp_size_out);
+int ofx_functional_segment_matmul_grad_w(void* stream, const ofx_tensor_desc* x,
+                                         const ofx_tensor_desc* dy, const ofx_tensor_desc* seg_ptr,
+                                         const ofx_tensor_desc* idx, int64_t parts,
+                                         ofx_tensor_desc* dw, void* tmp, size_t tmp_bytes,
+                                         size_t* tmp_size_out);
 /* The op's registered SBP signatures and no-grad inputs, as text (tests / introspection). */
 int ofx_op_spmm_csr_sbp_signatures(char* buf, size_t len);
 /* Same for any registered op; optional_inputs = comma-separated optional inputs present.   */

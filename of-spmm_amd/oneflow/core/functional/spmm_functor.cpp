@@ -1013,6 +1013,45 @@ extern "C" int ofx_functional_spmm_csr_multi(void* stream, const ofx_tensor_desc
   });
 }
 
+// ---- functional::SegmentMatmul and SegmentMatmulGradW ----------------------------------------------
+// Ops "segment_matmul" and "segment_matmul_grad_w" (oneflow/user/ops/segment_matmul_op.cpp) through
+// the same op-registry dispatch; `idx` may be NULL (the optional input is
+// then absent); w and dw are the [T, ., .] stacks viewed 2-D.
+extern "C" int ofx_functional_segment_matmul(void* stream, const ofx_tensor_desc* x,
+                                             const ofx_tensor_desc* w,
+                                             const ofx_tensor_desc* seg_ptr,
+                                             const ofx_tensor_desc* idx, int64_t trans_w,
+                                             ofx_tensor_desc* out, void* tmp, size_t tmp_bytes,
+                                             size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(x != nullptr && w != nullptr && seg_ptr != nullptr, OFX_EINVAL,
+                "segment_matmul: NULL input x, w or seg_ptr");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("segment_matmul");
+    std::vector<Arg> ins = {{"x", x}, {"w", w}, {"seg_ptr", seg_ptr}};
+    if (idx != nullptr) ins.push_back({"idx", idx});
+    return ToStatus(RunUserOp("segment_matmul", ins, {{"out", out}},
+                              {{"trans_w", trans_w != 0 ? 1 : 0}}, stream, tmp, tmp_bytes,
+                              tmp_size_out));
+  });
+}
+
+extern "C" int ofx_functional_segment_matmul_grad_w(void* stream, const ofx_tensor_desc* x,
+                                                    const ofx_tensor_desc* dy,
+                                                    const ofx_tensor_desc* seg_ptr,
+                                                    const ofx_tensor_desc* idx, int64_t parts,
+                                                    ofx_tensor_desc* dw, void* tmp,
+                                                    size_t tmp_bytes, size_t* tmp_size_out) {
+  return ::ofx::guarded(__func__, [&]() -> int {
+    OFX_REQUIRE(x != nullptr && dy != nullptr && seg_ptr != nullptr, OFX_EINVAL,
+                "segment_matmul_grad_w: NULL input x, dy or seg_ptr");
+    if (tmp_size_out == nullptr) OFX_TAKE_DEVICE_ERROR("segment_matmul_grad_w");
+    std::vector<Arg> ins = {{"x", x}, {"dy", dy}, {"seg_ptr", seg_ptr}};
+    if (idx != nullptr) ins.push_back({"idx", idx});
+    return ToStatus(RunUserOp("segment_matmul_grad_w", ins, {{"dw", dw}}, {{"parts", parts}},
+                              stream, tmp, tmp_bytes, tmp_size_out));
+  });
+}
+
 // ---- functional::GraphAttentionCsrHeads ----------------------------------------------------------
 // Op "graph_attention_csr_heads" (oneflow/user/ops/graph_attention_heads_op.cpp) through the same
 // op-registry dispatch; two outputs.

@@ -539,3 +539,51 @@ def OneFlow_SpmmCsrMultiOp : OneFlow_BaseOp<"spmm_csr_multi", [NoSideEffect, Dec
   let has_data_type_infer_fn = 1;
   let has_input_arg_modify_fn = 1;
 }
+
+// The segment matmul: out[i, :] = x[row(i), :] @ W[t] for seg_ptr[t] <= i < seg_ptr[t+1], with
+// row(i) = idx[i] (optional input) or i: the typed linear transform of RGCN / HGT / HeteroLinear
+// over rows sorted by type.  w is the [T, F_in, F_out] stack viewed [T*F_in, F_out]; with trans_w
+// the [T, F_out, F_in] stack viewed [T*F_out, F_in], read as its transpose.  f32 products and sums,
+// one rounding; float, float16, bfloat16.  SBP: all-broadcast.
+def OneFlow_SegmentMatmulOp : OneFlow_BaseOp<"segment_matmul", [NoSideEffect, DeclareOpInterfaceMethods<UserOpCompatibleInterface>]> {
+  let input = (ins
+    OneFlow_Tensor:$x,
+    OneFlow_Tensor:$w,
+    OneFlow_Tensor:$seg_ptr,
+    Optional<OneFlow_Tensor>:$idx
+  );
+  let output = (outs
+    OneFlow_Tensor:$out
+  );
+  let attrs = (ins
+    DefaultValuedAttr<SI64Attr, "0">:$trans_w
+  );
+  let has_logical_tensor_desc_infer_fn = 1;
+  let has_physical_tensor_desc_infer_fn = 1;
+  let has_get_sbp_fn = 1;
+  let has_data_type_infer_fn = 1;
+  let has_input_arg_modify_fn = 1;
+}
+
+// Its gradient in w from the upstream dy [S, F_out]: dw[t] = the sum over the segment's rows of
+// x[row(i), :]^T dy[i, :], as [T*F_in, F_out]; parts: the row parts of the launch (0 = from the
+// shapes), whose partial sums are added in ascending order.
+def OneFlow_SegmentMatmulGradWOp : OneFlow_BaseOp<"segment_matmul_grad_w", [NoSideEffect, DeclareOpInterfaceMethods<UserOpCompatibleInterface>]> {
+  let input = (ins
+    OneFlow_Tensor:$x,
+    OneFlow_Tensor:$dy,
+    OneFlow_Tensor:$seg_ptr,
+    Optional<OneFlow_Tensor>:$idx
+  );
+  let output = (outs
+    OneFlow_Tensor:$dw
+  );
+  let attrs = (ins
+    DefaultValuedAttr<SI64Attr, "0">:$parts
+  );
+  let has_logical_tensor_desc_infer_fn = 1;
+  let has_physical_tensor_desc_infer_fn = 1;
+  let has_get_sbp_fn = 1;
+  let has_data_type_infer_fn = 1;
+  let has_input_arg_modify_fn = 1;
+}

@@ -848,6 +848,94 @@ def spmm_csr_multi(a_csr_row_ptr: torch.Tensor, a_csr_col_idx: torch.Tensor,
     return out.view(m, slices, n), arg_max, arg_min
 
 
+def segment_matmul_tiles(dtype: torch.dtype) -> tuple[int, int, int]:
+    """(BM, BN, BK) of the segment matmul's HIP kernels for `dtype` (ofx_segment_matmul_tiles): the
+    forward's block is BM rows x BN columns over slabs of BK along F_in, the w-gradient's BN x BN
+    of dw[t] over slabs of BK rows."""
+    bm, bn, bk = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(LIB.ofx_segment_matmul_tiles(dtype_code(dtype), ctypes.byref(bm), ctypes.byref(bn),
+                                       ctypes.byref(bk)), "segment_matmul_tiles")
+    return bm.value, bn.value, bk.value
+
+
+def _segment_inputs(name, x, other, other_name, seg_ptr, idx):
+    """The prepared inputs of the segment matmul ops after the checks they share: x [R, F] and
+    dy [S, F] may be row-strided views; (x, other, seg_ptr, idx, T, S)."""
+    x = _prep(x, "x", matrix=True)
+    other = _prep(other, other_name, matrix=other_name == "dy")
+    seg_ptr = _prep(seg_ptr, "seg_ptr")
+    for t_name, t in (("x", x), (other_name, other)):
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"{name}: {t_name} should be float32, float16 or bfloat16, got "
+                            f"{t.dtype} (float64 is not supported)")
+    if other.dtype != x.dtype:
+        raise TypeError(f"{name}: {other_name} datatype should be equal to x ({other.dtype} vs "
+                        f"{x.dtype})")
+    if seg_ptr.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: seg_ptr should be int32 or int64, got {seg_ptr.dtype}")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise RuntimeError(f"{name}: x should be 2-D [R, F_in >= 1], got shape {tuple(x.shape)}")
+    if seg_ptr.dim() != 1 or seg_ptr.numel() < 2:
+        raise RuntimeError(f"{name}: seg_ptr should be 1-D with T + 1 >= 2 elements, got shape "
+                           f"{tuple(seg_ptr.shape)}")
+    s = x.shape[0]
+    if idx is not None:
+        idx = _prep(idx, "idx")
+        if idx.dtype != seg_ptr.dtype:
+            raise TypeError(f"{name}: idx should have the dtype of seg_ptr ({idx.dtype} vs "
+                            f"{seg_ptr.dtype})")
+        if idx.dim() != 1:
+            raise RuntimeError(f"{name}: idx should be 1-D [S], got shape {tuple(idx.shape)}")
+        s = idx.numel()
+    for t_name, t in ((other_name, other), ("seg_ptr", seg_ptr), ("idx", idx)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{name}: expected all tensors on the same device, got {t_name} on "
+                               f"{t.device} and x on {x.device}")
+    return x, other, seg_ptr, idx, seg_ptr.numel() - 1, s
+
+
+def segment_matmul(x: torch.Tensor, w: torch.Tensor, seg_ptr: torch.Tensor,
+                   idx: torch.Tensor | None = None, trans_w: bool = False, *,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """Op "segment_matmul": out [S, F_out] with out[i, :] = x[idx[i] or i, :] @ w[t] for the rows i
+    of segment t (seg_ptr [T+1]); w [T, F_in, F_out], or with trans_w [T, F_out, F_in] read as its
+    transpose.  f32 products and sums, one rounding (contract in include/ofx_spmm.h)."""
+    name = "segment_matmul"
+    x, w, seg_ptr, idx, t, s = _segment_inputs(name, x, w, "w", seg_ptr, idx)
+    if w.dim() != 3 or w.shape[0] != t:
+        raise RuntimeError(f"{name}: w should be 3-D [T, F_in, F_out] with T = {t} as seg_ptr, got "
+                           f"shape {tuple(w.shape)}")
+    f_in, f_out = (w.shape[2], w.shape[1]) if trans_w else (w.shape[1], w.shape[2])
+    if x.shape[1] != f_in or f_out < 1:
+        raise RuntimeError(f"{name}: x should have F_in = {f_in} columns as w"
+                           f"{' (trans_w)' if trans_w else ''}, got shape {tuple(x.shape)} and w "
+                           f"{tuple(w.shape)}")
+    out = _check_out(name, out, (s, f_out), x)
+    if out.numel() == 0:
+        return out
+    _two_phase(LIB.ofx_functional_segment_matmul, x,
+               _refs(x, w.view(-1, w.shape[2]), seg_ptr)
+               + (_refs(idx)[0] if idx is not None else None, 1 if trans_w else 0), _refs(out))
+    return out
+
+
+def segment_matmul_grad_w(x: torch.Tensor, dy: torch.Tensor, seg_ptr: torch.Tensor,
+                          idx: torch.Tensor | None = None, parts: int = 0) -> torch.Tensor:
+    """Op "segment_matmul_grad_w": dw [T, F_in, F_out], dw[t] = the sum over segment t's rows i of
+    x[idx[i] or i, :]^T dy[i, :]; an empty segment gives zeros.  parts: the row parts of the
+    launch, whose partial sums are added in ascending order (0: chosen from the shapes)."""
+    name = "segment_matmul_grad_w"
+    x, dy, seg_ptr, idx, t, s = _segment_inputs(name, x, dy, "dy", seg_ptr, idx)
+    if dy.dim() != 2 or dy.shape[0] != s or dy.shape[1] < 1:
+        raise RuntimeError(f"{name}: dy should be [S, F_out >= 1] with S = {s}, got shape "
+                           f"{tuple(dy.shape)}")
+    dw = torch.empty((t, x.shape[1], dy.shape[1]), dtype=x.dtype, device=x.device)
+    _two_phase(LIB.ofx_functional_segment_matmul_grad_w, x,
+               _refs(x, dy, seg_ptr) + (_refs(idx)[0] if idx is not None else None, int(parts)),
+               _refs(dw.view(-1, dy.shape[1])))
+    return dw
+
+
 def row_scale_by_degree(a_csr_row_ptr: torch.Tensor, x: torch.Tensor, *,
                         out: torch.Tensor | None = None) -> torch.Tensor:
     """out[r, :] = x[r, :] / deg_r in x's accumulation type, rounded once (deg_r = 0: +0): the

@@ -29,6 +29,8 @@ A feature vector per edge (e [nnz, N]; GINE with op="add", act="relu"; CFConv / 
 Several aggregators of the same messages from one gather (PNA, PyG's MultiAggregation):
     out = flow_spmm.spmm_multi(row_ptr, col_idx, values, M, K, b,
                                aggrs=("mean", "max", "min", "std"), eps=1e-5)        # [M, A, N]
+A typed linear transform over rows sorted by type (RGCN, HGT, HeteroLinear; idx gathers the rows):
+    out = flow_spmm.segment_matmul(x, w, seg_ptr, idx=None, trans_w=False)           # [S, F_out]
 A mini-batch: at most `fanout` sampled in-neighbours of each seed node, as a CSR the ops above take:
     rp_s, ci_s, eid = flow_spmm.sample_neighbors(row_ptr, col_idx, seeds, fanout, seed=0)
 and its block: the distinct ids of seeds and columns in order, and both relabelled to positions in it:
@@ -52,12 +54,12 @@ from ._C import spmm_csr, spmm_csr_reduce
 from ._lib import OfxError
 from .autograd import (csr_transpose, edge_softmax, fused_spmm, gat_attention, gat_softmax,
                        gatv2_attention, gatv2_scores, gatv2_softmax, graph_attention,
-                       quantize_rows_fp8, sddmm, spmm, spmm_edge, spmm_fp8, spmm_multi,
-                       spmm_reduce)
+                       quantize_rows_fp8, sddmm, segment_matmul, spmm, spmm_edge, spmm_fp8,
+                       spmm_multi, spmm_reduce)
 from .build import coo_to_csr, spgemm
 from .sampling import (compact_block, node_subgraph, random_walk, random_walk_subgraph, row_topk,
                        sample_blocks, sample_neighbors)
 
 __version__ = _lib.LIB.ofx_version().decode()
 
-__all__ = ["spmm", "spmm_edge", "spmm_multi", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "spgemm", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "random_walk", "random_walk_subgraph", "row_topk", "sampling", "_C"]
+__all__ = ["spmm", "segment_matmul", "spmm_edge", "spmm_multi", "spmm_fp8", "quantize_rows_fp8", "spmm_reduce", "edge_softmax", "graph_attention", "gat_softmax", "gat_attention", "gatv2_scores", "gatv2_softmax", "gatv2_attention", "fused_spmm", "spmm_csr", "spmm_csr_reduce", "sddmm", "csr_transpose", "OfxError", "ops", "synth", "autograd", "coo_to_csr", "spgemm", "sample_neighbors", "sample_blocks", "compact_block", "node_subgraph", "random_walk", "random_walk_subgraph", "row_topk", "sampling", "_C"]

@@ -271,6 +271,24 @@ def _load():
                                     i64, i64, p, p, i64, i64, i64, popt], i32),
         "ofx_functional_spmm_csr_multi": ([p, pdesc, pdesc, pdesc, i64, i64, pdesc, i64, f64, pdesc,
                                            pdesc, pdesc, p, sz, ctypes.POINTER(sz)], i32),
+        "ofx_segment_matmul_tiles": ([i32, ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                      ctypes.POINTER(i64)], i32),
+        "ofx_segment_matmul_workspace_size": ([i32, i32, i64, i64, i64, i64, i64,
+                                               ctypes.POINTER(sz)], i32),
+        "ofx_segment_matmul": ([p, i32, i32, i64, i64, i64, i64, i64, p, i64, p, i32, p, p, p, i64,
+                                p, sz], i32),
+        "ofx_segment_matmul_cpu": ([i32, i32, i32, i64, i64, i64, i64, i64, p, i64, p, i32, p, p, p,
+                                    i64], i32),
+        "ofx_segment_matmul_grad_w_workspace_size": ([i32, i32, i64, i64, i64, i64, i64, i64,
+                                                      ctypes.POINTER(sz)], i32),
+        "ofx_segment_matmul_grad_w": ([p, i32, i32, i64, i64, i64, i64, i64, p, i64, p, i64, p, p,
+                                       p, i64, p, sz], i32),
+        "ofx_segment_matmul_grad_w_cpu": ([i32, i32, i32, i64, i64, i64, i64, i64, p, i64, p, i64,
+                                           p, p, p], i32),
+        "ofx_functional_segment_matmul": ([p, pdesc, pdesc, pdesc, pdesc, i64, pdesc, p, sz,
+                                           ctypes.POINTER(sz)], i32),
+        "ofx_functional_segment_matmul_grad_w": ([p, pdesc, pdesc, pdesc, pdesc, i64, pdesc, p, sz,
+                                                  ctypes.POINTER(sz)], i32),
         "ofx_functional_spmm_csr_edge": ([p, pdesc, pdesc, pdesc, pdesc, i64, i64, i64, i64, pdesc,
                                           p, sz, ctypes.POINTER(sz)], i32),
         "ofx_functional_spmm_csr_edge_grad_e": ([p, pdesc, pdesc, pdesc, pdesc, pdesc, i64, i64,

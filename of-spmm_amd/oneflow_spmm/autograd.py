@@ -382,6 +382,61 @@ def spmm_edge(a_csr_row_ptr, a_csr_col_idx, e, a_num_rows, a_num_cols, b, op="mu
     return out if out is not None else res.view(shape)
 
 
+class SegmentMatmulFunction(torch.autograd.Function):
+    """out [S, F_out] = x[idx or arange] @ w[type] through op "segment_matmul", differentiable in x
+    and w.  d(w) is one launch of op "segment_matmul_grad_w"; d(x) is the op itself on dy with
+    trans_w (no copy of w) and, with idx, the sum of those rows over equal idx as `spmm` with unit
+    values over the CSR of (idx, arange(S)): deterministic, no atomics, entries of idx outside
+    [0, R) dropped.  Each is built only when its input needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, seg_ptr, idx, trans_w):
+        out = _C.segment_matmul(x, w, seg_ptr, idx, trans_w)
+        ctx.save_for_backward(x, w, seg_ptr, idx)
+        ctx.trans_w = trans_w
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from .build import coo_to_csr
+        x, w, seg_ptr, idx = ctx.saved_tensors
+        d_x = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_x = _C.segment_matmul(d_out, w, seg_ptr, None, not ctx.trans_w)
+            if idx is not None:
+                r, s = x.shape[0], idx.numel()
+                pos = torch.arange(s, dtype=idx.dtype, device=idx.device)
+                keep = (idx >= 0) & (idx < r)
+                rp, ci, _ = coo_to_csr(idx[keep], pos[keep], None, r, s, merge_duplicates=False)
+                ones = torch.ones(ci.numel(), dtype=x.dtype, device=x.device)
+                d_x = spmm_csr(rp, ci, ones, r, s, d_x)
+        if ctx.needs_input_grad[1]:
+            d_w = _C.segment_matmul_grad_w(x, d_out, seg_ptr, idx)
+            if ctx.trans_w:  # w is stored [T, F_out, F_in]
+                d_w = d_w.transpose(1, 2).contiguous()
+        return d_x, d_w, None, None, None
+
+
+def segment_matmul(x, w, seg_ptr, idx=None, trans_w=False, *, out=None):
+    """A typed linear transform over rows sorted by type:
+        out[i, :] = x[idx[i], :] @ w[t]   for seg_ptr[t] <= i < seg_ptr[t+1]
+    (idx=None: x[i, :]) for x [R, F_in] and w [T, F_in, F_out] of one dtype (float32, bfloat16,
+    float16; float64 raises TypeError), seg_ptr [T+1] int32 or int64, non-decreasing from 0 to S,
+    and idx [S] of seg_ptr's dtype: RGCN, HGT, PyG's HeteroLinear / segment_matmul, DGL's
+    segment_mm; with idx = the columns of type-sorted edges, the edge-typed message
+    x[col[j]] @ w[etype[j]] without the [nnz, F_in] gathered copy.  trans_w=True takes
+    w [T, F_out, F_in] and reads it transposed (no copy).  An idx[i] outside [0, R) reads a zero
+    row.  One launch on matrix instructions, nothing read back to the host: the forward and the
+    w-gradient are safe under graph capture.  Products and sums in float32, one rounding; the
+    order of a sum is the hardware's, so GPU and CPU agree within
+    2 n 2^-24 sum|a||b| + 2^-p |ref| and bit for bit where every partial sum is
+    exact; two calls on the same inputs give the same bits.  CPU tensors also check seg_ptr.
+    Differentiable in x and w.  `out=` only when no gradient is being recorded."""
+    if _recording("segment_matmul", out, x, w):
+        return SegmentMatmulFunction.apply(x, w, seg_ptr, idx, bool(trans_w))
+    return _C.segment_matmul(x, w, seg_ptr, idx, bool(trans_w), out=out)
+
+
 FP8_MAX = {torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
 
 
@@ -1026,5 +1081,6 @@ __all__ = ["csr_transpose", "gather_values", "sddmm", "SpmmCsrFunction", "spmm",
            "SddmmCsrFunction", "EdgeSoftmaxFunction", "edge_softmax", "SpmmCsrHeadsFunction",
            "SddmmCsrHeadsFunction", "EdgeSoftmaxHeadsFunction", "GatSoftmaxFunction", "gat_softmax",
            "gat_attention", "Gatv2ScoresFunction", "gatv2_scores", "gatv2_softmax",
-           "gatv2_attention", "SpmmCsrEdgeFunction", "spmm_edge", "SpmmCsrMultiFunction",
+           "gatv2_attention", "SpmmCsrEdgeFunction", "spmm_edge", "SegmentMatmulFunction",
+           "segment_matmul", "SpmmCsrMultiFunction",
            "spmm_multi"]

@@ -355,6 +355,51 @@ def spmm_csr_multi(row_ptr, col_idx, values, b, m, k, aggr_mask, eps=1e-5, *, ou
     return out, arg_max, arg_min
 
 
+def segment_matmul(x, w, seg_ptr, idx=None, trans_w=False, *, out=None, s=None,
+                   num_threads: int = 0):
+    """The segment matmul at the C-ABI (ofx_segment_matmul on device tensors, the kCPU kernel
+    ofx_segment_matmul_cpu on host tensors): x [R, F_in] and `out` [S, F_out] with unit column
+    stride (their row strides are passed on), w [T, F_in, F_out] contiguous ([T, F_out, F_in] with
+    trans_w).  `s`: the output rows to pass instead of idx's length or R (tests)."""
+    r, t = x.shape[0], seg_ptr.numel() - 1
+    f_in, f_out = (w.shape[2], w.shape[1]) if trans_w else (w.shape[1], w.shape[2])
+    if s is None:
+        s = idx.numel() if idx is not None else r
+    if out is None:
+        out = torch.empty((s, f_out), dtype=x.dtype, device=x.device)
+    body = (dtype_code(seg_ptr.dtype), dtype_code(x.dtype), r, s, t, f_in, f_out, _nz(x),
+            x.stride(0), _nz(w), 1 if trans_w else 0, seg_ptr.data_ptr(), _nz(idx), _nz(out),
+            out.stride(0))
+    if x.device.type == "cpu":
+        check(LIB.ofx_segment_matmul_cpu(int(num_threads), *body), "segment_matmul_cpu")
+        return out
+    check(LIB.ofx_segment_matmul(current_stream_handle(x), *body, None, 0), "segment_matmul")
+    return out
+
+
+def segment_matmul_grad_w(x, dy, seg_ptr, idx=None, parts=0, *, out=None, num_threads: int = 0,
+                          workspace_bytes: int | None = None):
+    """The w-gradient of the segment matmul at the C-ABI: x [R, F_in], dy [S, F_out] with unit
+    column stride -> dw [T, F_in, F_out] contiguous.  parts: the row parts of the device launch
+    (0: chosen from the shapes)."""
+    r, t, s = x.shape[0], seg_ptr.numel() - 1, dy.shape[0]
+    f_in, f_out = x.shape[1], dy.shape[1]
+    if out is None:
+        out = torch.empty((t, f_in, f_out), dtype=x.dtype, device=x.device)
+    idt, vdt = dtype_code(seg_ptr.dtype), dtype_code(x.dtype)
+    body = (idt, vdt, r, s, t, f_in, f_out, _nz(x), x.stride(0), _nz(dy), dy.stride(0),
+            seg_ptr.data_ptr(), _nz(idx), _nz(out))
+    if x.device.type == "cpu":
+        check(LIB.ofx_segment_matmul_grad_w_cpu(int(num_threads), *body), "segment_matmul_grad_w_cpu")
+        return out
+    wbuf, ws = _workspace(x.device, "segment_matmul_grad_w",
+                          LIB.ofx_segment_matmul_grad_w_workspace_size, idt, vdt, r, s, t, f_in,
+                          f_out, int(parts), workspace_bytes=workspace_bytes)
+    check(LIB.ofx_segment_matmul_grad_w(current_stream_handle(x), *body, int(parts),
+                                        wbuf.data_ptr(), ws), "segment_matmul_grad_w")
+    return out
+
+
 def spmm_csr_heads_fp8(row_ptr, col_idx, values, b_q, b_scale, m, k, heads, *, b_format=None,
                        val_dtype=None, out=None, row_begin=0, row_end=None,
                        options: Options | None = None, num_threads: int = 0,
